@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config c2|c3|c4|c5]
                     [--scaling weak|strong] [--reduce-every I] [--collective gather|reduce] [--inproc]
+                    [--dump-outputs DIR]
 
 A *step* is one pass of the hot path over one batch of synthetic input: B iterations (samples per pixel) of the
 800x800 depth-8 Cornell box with the mirror ball (BASELINE.json configs[1], "c2"), traced as one path pool through
@@ -31,6 +32,10 @@ fp32 rate and the active-lane fraction ride along, and `roofline.timed_pass` sta
 pass's own time per step.  The counter profile (profiles/traffic.json, written by profiles/collect.py) is keyed
 by a hash of the kernel sources and compile flags: after any kernel change the counter-derived fields are null until
 the collection has been re-run.
+
+--dump-outputs DIR: right after the timed steps, the accumulation image (the running sum over the warm-up and timed
+iterations, what a caller of the path receives) is written as DIR/image.npy, float32 [H, W, 3]; a frame over 64 MB
+(c5) as a fixed sample of its pixels.  The inputs depend on the arguments alone, so two builds compare file for file.
 """
 import argparse
 import json
@@ -706,7 +711,21 @@ def main():
                          "(measured SLOWER than the tracing thread's own two-slot gather once the device was no longer the limit: "
                          "two Python threads take turns at the interpreter lock; profiles/r04/sub_exchange_check.log)")
     ap.add_argument("--no-exchange-thread", action="store_true", help="(the default now; kept for old command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the accumulation image a caller receives) to "
+                         "DIR/<name>.npy; the inputs are fixed by the arguments, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:                  # the ranks of a self-launch run with cwd = ROOT: hand them an absolute path
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = sys.argv[1:]
+        for i, a in enumerate(argv):
+            if a == "--dump-outputs" and i + 1 < len(argv):
+                argv[i + 1] = args.dump_outputs
+            elif a.startswith("--dump-outputs="):
+                argv[i] = "--dump-outputs=" + args.dump_outputs
+        sys.argv[1:] = argv
 
     # ---- `python3 bench.py --gpus N` from a plain shell: the ranks are started here, as child processes, before
     # anything in this process has imported torch or the HIP library ----
@@ -763,6 +782,10 @@ def main():
     value = rays / dt / 1e6
     put(out, "value", round(value, 2))
     put(out, "ms_per_step", round(dt * 1e3 / args.steps, 4))
+    if args.dump_outputs:
+        dumped = dump_outputs(c, s, args.dump_outputs)
+        if rank == 0:
+            put(out, "dumped_outputs", dumped)
 
     # ---- roofline of the dominant kernel: the timed region is run a second time, identically, with HIP
     # events bracketing every kernel launch on the launch stream (2 events per launch from a preallocated
@@ -901,6 +924,39 @@ def main():
     elif rank == 0:
         print(json.dumps(out))
     teardown(c)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20      # pixels kept of a frame whose image exceeds DUMP_LIMIT_BYTES (a fixed, seeded choice)
+
+
+def dump_outputs(c, s, out_dir):
+    """The frame as it stands right after the timed steps -- the running sum over the warm-up and timed iterations that a
+    caller of the path receives (N > 1: the frame rank 0 assembled; --inproc: device 0's) -- as float32 .npy files in
+    out_dir, rank 0 only.  A frame larger than DUMP_LIMIT_BYTES is written as a fixed sample of its pixels
+    (image_sample.npy) with their indices (image_sample_index.npy, float64).  Returns {name: shape} of what was written."""
+    torch = c.torch
+    s.barrier()
+    if c.inproc:
+        img = c.pt.get_image(c.npix)
+    else:
+        final = s.frame if c.dist_on else s.image
+        torch.cuda.synchronize()
+        img = final.cpu().numpy() if c.rank == 0 else None
+    if c.rank != 0:
+        return None
+    img = np.asarray(img, dtype=np.float32).reshape(c.H, c.W, 3)
+    arrays = {}
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        arrays["image"] = img
+    else:
+        idx = np.sort(np.random.default_rng(12345).choice(c.npix, size=DUMP_SAMPLE_PIXELS, replace=False))
+        arrays["image_sample"] = img.reshape(-1, 3)[idx]
+        arrays["image_sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def teardown(c):

@@ -92,6 +92,29 @@ def test_bench_digest_equals_oracle():
     assert d["config"]["rays_per_step"] == (rays[1] + rays[2]) // 2
 
 
+def test_dump_outputs_is_the_timed_frame(tmp_path):
+    """--dump-outputs: the accumulation image right after the timed steps, float32 [H, W, 3], byte for byte the frame the
+    digest is taken of (no roofline pass in between); what --steps asked for is what was timed.  Two ranks started by
+    bench.py itself (gloo, one device) dump the frame rank 0 assembled: the same array as the 1-process run's."""
+    import hashlib
+    import numpy as np
+    one = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
+               "--no-roofline", "--no-per-call", "--digest", "--dump-outputs", str(tmp_path / "one")])
+    assert one["steps"] == 3 and one["ms_per_step"] > 0 and one["dumped_outputs"] == {"image": [800, 800, 3]}
+    img = np.load(str(tmp_path / "one" / "image.npy"))
+    assert img.dtype == np.float32 and img.shape == (800, 800, 3) and img.sum() > 0
+    assert hashlib.md5(img.tobytes()).hexdigest() == one["image_md5"]
+    env = {k: os.environ.pop(k) for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT") if k in os.environ}
+    try:
+        two = run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--no-roofline",
+                   "--backend", "gloo", "--same-device", "--no-sub", "--launch-timeout", "500",
+                   "--dump-outputs", str(tmp_path / "two")])
+    finally:
+        os.environ.update(env)
+    assert two["n_gpus"] == 2 and two["dumped_outputs"] == {"image": [800, 800, 3]}
+    assert np.load(str(tmp_path / "two" / "image.npy")).tobytes() == img.tobytes()
+
+
 def test_single_gpu_line():
     d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
              "--digest", "--pcie"])

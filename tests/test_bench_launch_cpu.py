@@ -41,6 +41,28 @@ def test_print_launch_touches_neither_torch_nor_the_library():
     assert "--print-launch" not in d["launch"] and d["launch"][d["launch"].index("--nproc-per-node") + 1] == "4"
 
 
+def test_dump_outputs_dir_reaches_the_ranks_absolute_and_steps_must_be_positive(tmp_path):
+    """--dump-outputs DIR: the self-started ranks run with cwd = the repository root, so a relative DIR is handed to them
+    as the absolute path of the caller's DIR; --steps 0 (no timed step to report on) is refused before any GPU work."""
+    code = textwrap.dedent("""
+        import sys
+        sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--dump-outputs", "out", "--print-launch"]
+        import bench
+        try:
+            bench.main()
+        except SystemExit as e:
+            assert e.code in (0, None), e.code
+    """)
+    p = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, PYTHONPATH=ROOT))
+    assert p.returncode == 0, p.stdout + p.stderr
+    launch = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])["launch"]
+    assert launch[launch.index("--dump-outputs") + 1] == str(tmp_path / "out")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
 class Args:
     gpus, print_launch, launch_timeout, phase, one_launch = 2, False, 30.0, "all", False
     no_sub, shared_frame, sub_timeout = False, False, 5.0
