@@ -156,7 +156,8 @@ enum pt_flags {
                                     into it and nothing else, so the ranks assemble the frame in host memory with no exchange
                                     between them: it holds the sum after iteration i once every rank's call for i has returned.
                                     Without the flag a tiled session copies its whole accumulation buffer (zeros outside its
-                                    tile).  Needs iterations that run as one launch and a mappable buffer: PT_ERR_INVALID if not. */
+                                    tile).  Needs a mappable buffer, and iterations that run as one launch unless the call is
+                                    served from a PT_LOOKAHEAD window (whose gather writes the tile's pixels): PT_ERR_INVALID if not. */
     PT_LOOKAHEAD     = 1u << 11, /* opt-in: pt_trace TRACES AHEAD of its caller.  The reference's host calls ONE pathtrace() per
                                     iteration (main.cpp:130-140) and a path's whole life is a function of (iteration, pixelIndex,
                                     depth) alone, so the iterations to come can be traced before they are asked for.  pt_trace(iter)
@@ -177,9 +178,18 @@ enum pt_flags {
                                     ahead of its calls (iterations traced ahead and then discarded stay counted).  With a
                                     page-locked host image (PT_PIN_IMAGE | PT_HOST_SPARSE) on a 256-CU device the windows are
                                     traced on 232 compute units and the calls' gathers write the image from the other 24
-                                    (CU-masked streams of the library's own; results unchanged).  Single-device sessions that own the whole frame (tile_count <= 1) on the fused
-                                    pipelines; ignored elsewhere (PT_UNFUSED, PT_FAKE_SHADER, PT_CACHE_FIRST, two-kernel sort,
-                                    PT_ASYNC_IMAGE, max_batch < 2). */
+                                    (CU-masked streams of the library's own; results unchanged) -- only by a context that is
+                                    alone on its device: contexts of one session that share a device trace and gather on plain
+                                    streams.  Tiled sessions trace their windows over their own tile: a rank of the process
+                                    form (tile_count > 1) writes only its tile's pixels into a PT_SHARED_IMAGE frame (the frame
+                                    holds the sum after iteration i once every rank's call for i has returned, as without the
+                                    flag); in a session over several devices every context serves its tile from its own windows
+                                    and writes its pixels into the host image, with no exchange, when the call has no PBO and
+                                    the host image is page-locked for every device (PT_PIN_IMAGE) or absent (pt_get_image /
+                                    pt_device_image then assemble the frame); a call with a PBO or a pageable host image, and
+                                    every batch, takes the plain path after every context's windows are discarded.  On the
+                                    fused pipelines; ignored elsewhere (PT_UNFUSED, PT_FAKE_SHADER, PT_CACHE_FIRST, two-kernel
+                                    sort, PT_ASYNC_IMAGE, max_batch < 2). */
     PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after

@@ -163,22 +163,31 @@ static int init_impl(const pt_scene_desc *d) {
     R.map.tile_pixels = tile_rows(d->tile_index, tile_count, R.map.strip_rows, H) * W;
     if (R.map.tile_pixels <= 0) return fail(PT_ERR_INVALID, "pt_init: tile owns no rows");
     make_div_magic((uint32_t)R.map.tile_pixels, &R.map.div_magic, &R.map.div_shift);
-    {   // the magic must reproduce n / tile_pixels exactly; probe the edges of every sample and the extremes
-        const uint32_t d = (uint32_t)R.map.tile_pixels;
+    // the magic must reproduce n / d exactly; probe the edges of every multiple and the extremes
+    auto magic_holds = [](uint32_t d, uint32_t magic, uint32_t shift) {
         auto fast = [&](uint32_t n) {
             if (d == 1) return n;
-            const uint32_t q = (uint32_t)(((uint64_t)R.map.div_magic * n) >> 32);
-            return (((n - q) >> 1) + q) >> R.map.div_shift;
+            const uint32_t q = (uint32_t)(((uint64_t)magic * n) >> 32);
+            return (((n - q) >> 1) + q) >> shift;
         };
         for (uint64_t k = 0; k <= 0xffffffffull / d && k < 4096; ++k)
             for (int e = -1; e <= 1; ++e) {
                 const uint64_t n = k * d + (uint64_t)(int64_t)e;
-                if (n <= 0xffffffffull && fast((uint32_t)n) != (uint32_t)n / d)
-                    return fail(PT_ERR_INTERNAL, "pt_init: division magic failed for %u / %u", (uint32_t)n, d);
+                if (n <= 0xffffffffull && fast((uint32_t)n) != (uint32_t)n / d) return false;
             }
         const uint32_t probes[] = {0u, 1u, d - 1, d, d + 1, 0x7fffffffu, 0x80000000u, 0xfffffffeu, 0xffffffffu};
         for (uint32_t n : probes)
-            if (fast(n) != n / d) return fail(PT_ERR_INTERNAL, "pt_init: division magic failed for %u / %u", n, d);
+            if (fast(n) != n / d) return false;
+        return true;
+    };
+    if (!magic_holds((uint32_t)R.map.tile_pixels, R.map.div_magic, R.map.div_shift))
+        return fail(PT_ERR_INTERNAL, "pt_init: division magic failed for n / %d", R.map.tile_pixels);
+    if (tile_count > 1) {       // PT_LOOKAHEAD's tiled gather (k_gather_one_tiled): the strip span, divided the same way
+        const uint32_t span = (uint32_t)R.map.strip_rows * (uint32_t)W;
+        make_div_magic(span, &R.la_tg.magic, &R.la_tg.shift);
+        R.la_tg.skip = (uint32_t)(tile_count - 1) * span;
+        R.la_tg.first = (uint32_t)d->tile_index * span;
+        R.la_tiles_ok = span >= 2 && magic_holds(span, R.la_tg.magic, R.la_tg.shift);
     }
     R.max_batch = d->max_batch < 1 ? 1 : d->max_batch;
     if ((int64_t)R.max_batch * R.map.tile_pixels >= (int64_t)0x3ffffff0)
@@ -621,11 +630,24 @@ int pt_trace_mapped(int iter, float *mapped) {
 // order -- with the host-image write and the tonemap folded into that launch.  While window w is consumed, window w + 1
 // is traced on the other lane.  Window sizes grow 4, 16, 64, .. up to max_batch: the first image after a camera move
 // does not wait for 64 iterations.
+// A context that traces one tile of the frame (tile_count > 1: the multi-device layer's contexts, a rank of the process
+// form) does the same over its tile: the windows go through the tiled batch (global pixelIndex as RNG key, so every sample
+// is the single-device sample), and its calls gather with k_gather_one_tiled, which adds sample s's colours (local pixel
+// order, s * tile_pixels on) into the accumulation buffer at their global pixels.  A host frame whose other rows belong to
+// other contexts or ranks (`shared` in la_trace) only ever receives this tile's pixels.
 // ---------------------------------------------------------------------------------------------------------------------
 bool la_possible(void) {
     return (R.flags & PT_LOOKAHEAD) && !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST | PT_ASYNC_IMAGE)) &&
-           (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) && R.map.tile_count == 1 && R.max_batch >= 2 && R.ov_enabled &&
-           !R.use_graphs && !R.profiling && !R.dbg_counts;
+           (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) && (R.map.tile_count == 1 || R.la_tiles_ok) && R.max_batch >= 2 &&
+           R.ov_enabled && !R.use_graphs && !R.profiling && !R.dbg_counts;
+}
+
+// will la_trace serve this context's calls (the lanes allocated and enough of them)?  The multi-device layer asks once
+// before it sends its calls down that path.
+bool la_ready(void) {
+    if (!R.live || !la_possible()) return false;
+    if (ensure_lanes() != PT_OK) { (void)hipGetLastError(); return false; }
+    return R.ov_enabled && R.ov_lanes >= Renderer::LA_SLOTS;
 }
 
 // Forget the windows.  One that may still be tracing keeps its lane's buffers busy -- lane 0's are the session's own --
@@ -680,17 +702,25 @@ static int la_trace_ahead(void) {
     return PT_OK;
 }
 
-// `handled`: the call was served here (else the caller goes on with the plain path)
-int la_trace(uint8_t *pbo_rgba, int iter, float *host_image_sum, bool *handled) {
+// `handled`: the call was served here (else the caller goes on with the plain path).  `premapped`: host_image_sum is
+// already this device's address of a page-locked frame that the other contexts of a multi-device session share
+// (pt_trace_ahead).
+int la_trace(uint8_t *pbo_rgba, int iter, float *host_image_sum, bool *handled, bool premapped = false) {
     *handled = false;
     if (!la_possible() || iter < 1) return la_discard(LA_STREAM);
     int rc = ensure_lanes();
     if (rc) return rc;
     if (!R.ov_enabled || R.ov_lanes < Renderer::LA_SLOTS) return PT_OK;             // the lanes do not fit: the plain path
-    *handled = true;
     // the host image: the launch writes the sums that changed into the caller's page-locked buffer when that buffer holds
-    // exactly the accumulation buffer's content as of the previous call (PT_HOST_SPARSE); otherwise every pixel is copied
-    float *mapped = host_image_sum ? map_host(host_image_sum, (size_t)R.npix * 12) : nullptr;
+    // exactly the accumulation buffer's content as of the previous call (PT_HOST_SPARSE); otherwise every pixel is copied.
+    // A tile's frame whose other rows are someone else's (`shared`: the multi-device layer's, PT_SHARED_IMAGE's) gets this
+    // tile's pixels only, from the gather itself -- so it has to be mapped: if it cannot be, the plain path (which refuses it).
+    const bool tiled = R.map.tile_count > 1;
+    const bool shared = tiled && host_image_sum && (premapped || (R.flags & PT_SHARED_IMAGE));
+    float *mapped = premapped ? host_image_sum : host_image_sum ? map_host(host_image_sum, (size_t)R.npix * 12) : nullptr;
+    if (shared && !mapped) return la_discard(LA_STREAM);
+    *handled = true;
+    // (for a tile: the claim concerns this tile's pixels -- the only ones this context ever writes into a frame)
     const bool host_current = mapped && R.host_sparse_enabled && R.own_image && R.host_synced == mapped && R.host_epoch == R.image_epoch;
     if (!la_matches(R.la[R.la_cur], iter)) {
         // not the next sample of the window being consumed (whose successors on the ring continue it, so none of them
@@ -722,17 +752,31 @@ int la_trace(uint8_t *pbo_rgba, int iter, float *host_image_sum, bool *handled) 
     if (gs != R.stream) R.la_masked_calls++;
     if (host_current && R.dma_last) { HIPCHK(hipStreamWaitEvent(gs, R.dma_last, 0)); R.dma_last = nullptr; }
     {
-        const float4 *fin = reinterpret_cast<const float4 *>(lane.b.final_mem) + (size_t)s * (size_t)R.npix;
-        dim3 grid((unsigned)((R.npix + (int)LA_UNROLL * BLOCK - 1) / ((int)LA_UNROLL * BLOCK)));
+        // the window's final colours are the batch's: sample s's slice starts at s * tile_pixels, one entry per local pixel
+        const int np = R.map.tile_pixels;
+        const float4 *fin = reinterpret_cast<const float4 *>(lane.b.final_mem) + (size_t)s * (size_t)np;
+        dim3 grid((unsigned)((np + (int)LA_UNROLL * BLOCK - 1) / ((int)LA_UNROLL * BLOCK)));
         // on its own compute units: a round and a half of what they hold at once (a grid-stride kernel; 0.058 against 0.060 ms with one round)
         if (gs != R.stream) grid = dim3((unsigned)std::min<int>((int)grid.x, R.la_cus * (pt_experiment("PTMI355_LA_GWGS") ? std::max(1, atoi(pt_experiment("PTMI355_LA_GWGS"))) : 12)));
-        float *host_dev = host_current ? mapped : (float *)nullptr;
-        if (pbo_rgba) hipLaunchKernelGGL(k_gather_one<true>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)R.npix, pbo_rgba, iter);
-        else hipLaunchKernelGGL(k_gather_one<false>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)R.npix, pbo_rgba, iter);
+        if (!tiled) {
+            float *host_dev = host_current ? mapped : (float *)nullptr;
+            if (pbo_rgba) hipLaunchKernelGGL(k_gather_one<true>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)R.npix, pbo_rgba, iter);
+            else hipLaunchKernelGGL(k_gather_one<false>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)R.npix, pbo_rgba, iter);
+        } else {
+            // a shared frame that is not current gets every pixel of the tile; any other frame is written as above
+            const bool all = shared && !host_current;
+            float *host_dev = (host_current || all) ? mapped : (float *)nullptr;
+            if (all) hipLaunchKernelGGL(k_gather_one_tiled<true>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)np, R.la_tg);
+            else hipLaunchKernelGGL(k_gather_one_tiled<false>, grid, dim3(BLOCK), 0, gs, R.image, fin, host_dev, w.stamp, (uint32_t)np, R.la_tg);
+            if (pbo_rgba) {                               // the whole accumulation buffer, as the plain tiled path tonemaps it
+                HIPCHK(hipGetLastError());
+                hipLaunchKernelGGL(k_tonemap, dim3((R.npix + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, gs, pbo_rgba, R.image, R.npix, iter);
+            }
+        }
     }
     HIPCHK(hipGetLastError());
     R.image_epoch++;
-    if (host_image_sum && !host_current) {
+    if (host_image_sum && !host_current && !shared) {
         rc = enqueue_image_copy(host_image_sum);
         if (rc) return rc;
     }
@@ -753,6 +797,18 @@ int la_trace(uint8_t *pbo_rgba, int iter, float *host_image_sum, bool *handled) 
     }
     if (w.next >= w.count) { w.valid = false; R.la_cur = (R.la_cur + 1) % Renderer::LA_SLOTS; }     // consumed: on to the window traced meanwhile
     return rc;
+}
+
+// The multi-device layer's pt_trace under PT_LOOKAHEAD (pt_multi.hpp: multi_trace), on this context's thread: iteration
+// `iter` of this context's tile served from its windows; `frame` = this device's address of the caller's page-locked
+// frame (nullptr: no host image).  Asked only when la_ready() held on every context.
+int pt_trace_ahead(int iter, float *frame) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_trace: not initialised");
+    R.in_step = false;
+    bool handled = false;
+    const int rc = la_trace(nullptr, iter, frame, &handled, frame != nullptr);
+    if (rc) return rc;
+    return handled ? PT_OK : fail(PT_ERR_INTERNAL, "pt_trace: this context cannot trace ahead");
 }
 
 int pt_trace(uint8_t *pbo_rgba, int frame, int iter, float *host_image_sum) {
@@ -790,6 +846,7 @@ int pt_trace(uint8_t *pbo_rgba, int frame, int iter, float *host_image_sum) {
                            R.image, R.npix, iter);
         HIPCHK(hipGetLastError());
     }
+    // (a call that la_trace served has returned above: its gather wrote this tile's pixels into the shared frame itself)
     if (shared_frame && !gathered)
         return fail(PT_ERR_INVALID, "pt_trace: PT_SHARED_IMAGE needs iterations that run as one launch (PT_COMPACT, no material sort, no mesh, "
                                     "at most %llu paths per tile)", (unsigned long long)std::max(R.whole_max_paths, R.whole_max_host_paths));

@@ -412,10 +412,12 @@ int ensure_lanes(void) {
 // cost: 0.060-0.061 against 0.068-0.072 ms per call at 800x800, 0.40 against 0.47 at 3840x2160.  Without
 // a host image the masks only cost (-9 % on C3's and C5's frames): such calls keep the plain streams.  Sessions whose
 // windows need k_mesh's grid (PT_MESH_BVH), devices that are not 256 compute units in 8 XCDs, and a runtime that refuses
-// the masks take the plain streams as well.
+// the masks take the plain streams as well.  So do contexts that share their device with other contexts of the session
+// (devices = {0, 0, ..}): several contexts carving the same compute units into 232 + 24 is no split at all, and it would
+// multiply the streams on that device.
 bool ensure_la_masks(void) {
     if (R.la_masks_ready) return true;
-    if (R.la_masks_failed || !R.ov_ready || R.la_cus < 8 || R.cus != 256 || R.mesh_mode == MESH_BVH) return false;
+    if (R.la_masks_failed || R.la_shared_device || !R.ov_ready || R.la_cus < 8 || R.cus != 256 || R.mesh_mode == MESH_BVH) return false;
     uint32_t trace_mask[8], gather_mask[8];
     for (int b = 0; b < 8; ++b) { trace_mask[b] = 0xffffffffu; gather_mask[b] = 0; }
     for (int b = 0; b < R.la_cus; ++b) { trace_mask[b / 32] &= ~(1u << (b % 32)); gather_mask[b / 32] |= 1u << (b % 32); }

@@ -157,6 +157,11 @@ struct Renderer {
     hipEvent_t la_rs_event = nullptr;
     bool la_tracing = false;      // the batch being enqueued is a window: no k_gather, only its counters (enqueue_end)
     uint64_t la_misses = 0, la_windows = 0, la_discards = 0;   // calls that had to trace their own window first / windows enqueued / windows thrown away
+    // a tiled context (tile_count > 1): where its local pixels sit in the frame, for k_gather_one_tiled (la_tiles_ok: the
+    // division magic for the strip span holds); la_shared_device: other contexts of this session trace on the same device,
+    // so the CU masks are not taken (ensure_la_masks)
+    TileGather la_tg{};
+    bool la_tiles_ok = false, la_shared_device = false;
     Control *last_ctl = nullptr;  // the control block of the last batch (collect_stats)
     float *epi_host = nullptr;    // pt_trace: the caller's image, device-mapped, for k_iteration's own gather (this call only)
     bool epi_done = false;        // ... and k_iteration took it

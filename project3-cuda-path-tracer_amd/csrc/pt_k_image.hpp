@@ -132,7 +132,8 @@ __global__ __launch_bounds__(BLOCK) void k_tonemap(uint8_t *pbo, const float *im
 }
 
 // PT_LOOKAHEAD: finalGather (pathtrace.cu:269-278) for ONE iteration of a window traced ahead of the caller.  `fin` is that
-// sample's slice of the window's final colours (float4[pixels], index = pixel: such sessions own the whole frame): an entry
+// sample's slice of the window's final colours (float4[pixels], index = pixel: a context that owns the whole frame; tiled ones
+// take k_gather_one_tiled below): an entry
 // that carries the window's stamp is a path that ended with a non-zero colour -- image[pixel] += colour, the one addition
 // per pixel and iteration of the reference, in iteration order because the calls come in iteration order.  The other
 // pixels' sums do not change and are not even read, unless a PBO wants every pixel tonemapped (PBO = true).  `host` (the
@@ -168,6 +169,41 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(16), amdgpu_n
                 if (host) { host[3 * j + 0] = r; host[3 * j + 1] = g; host[3 * j + 2] = b; }
             }
             if (PBO) reinterpret_cast<uchar4 *>(pbo)[j] = tonemap_pixel(r, g, b, iter);
+        }
+    }
+}
+
+// ... the same for a context that traces one tile of the frame (tile_count > 1: the multi-device layer's contexts, a rank of
+// the process form).  `fin` is indexed by LOCAL pixel (the tiled batch's layout: sample s at s * tile_pixels, cf. sample_of),
+// the accumulation buffer and the host frame by GLOBAL pixel (TileGather).  `host` is a frame the context shares with the
+// others that tile it: only this tile's pixels are ever written there -- the changed ones, or with ALL (a frame that is not
+// current, e.g. the first call) every one of them.  No PBO form (tiled calls tonemap with k_tonemap).  The same register
+// budget as above, for the same reason: it runs beside this context's next windows.
+template <bool ALL>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(16), amdgpu_num_vgpr(32))) void k_gather_one_tiled(
+        float *__restrict__ image, const float4 *__restrict__ fin, float *__restrict__ host, uint32_t stamp, uint32_t n,
+        TileGather tg) {
+    const uint32_t stride = gridDim.x * BLOCK;
+    for (uint32_t j0 = blockIdx.x * BLOCK + threadIdx.x; j0 < n; j0 += LA_UNROLL * stride) {
+        float4 c[LA_UNROLL];
+#pragma unroll
+        for (int u = 0; u < (int)LA_UNROLL; ++u) {
+            const uint32_t j = j0 + (uint32_t)u * stride;
+            c[u] = j < n ? fin[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // (no entry carries stamp 0)
+        }
+#pragma unroll
+        for (int u = 0; u < (int)LA_UNROLL; ++u) {
+            const uint32_t j = j0 + (uint32_t)u * stride;
+            const bool changed = __float_as_uint(c[u].w) == stamp;
+            if (ALL ? j >= n : !changed) continue;
+            const uint32_t q = __umulhi(tg.magic, j);
+            const uint32_t pix = j + ((((j - q) >> 1) + q) >> tg.shift) * tg.skip + tg.first;
+            float r = image[3 * pix + 0], g = image[3 * pix + 1], b = image[3 * pix + 2];
+            if (changed) {
+                r += c[u].x; g += c[u].y; b += c[u].z;
+                image[3 * pix + 0] = r; image[3 * pix + 1] = g; image[3 * pix + 2] = b;
+            }
+            if (host) { host[3 * pix + 0] = r; host[3 * pix + 1] = g; host[3 * pix + 2] = b; }
         }
     }
 }

@@ -247,6 +247,7 @@ struct Group {
     float *dhost = nullptr; size_t dhost_bytes = 0;  // the registered host image
     bool frame_stale = false;  /* (set by the caller's thread, cleared by it or by the exchange thread -- always through __atomic_load_n / __atomic_store_n, relaxed: a late clear only costs one redundant exchange) */              // the device frame lacks the peers' rows of such calls: the next exchange brings them
     std::unique_ptr<Exchanger> x;               // asynchronous batches hand their exchange to this thread
+    int la_state = 0;                           // PT_LOOKAHEAD: every context can trace ahead (1) / not (-1) / not asked yet (0)
     float *frame = nullptr;                     // where the tiles are assembled: context 0's accumulation buffer -- except in the
                                                 // one-context RCCL rehearsal, where it is a buffer of its own (self_frame)
     float *self_frame = nullptr;
@@ -349,6 +350,10 @@ int enqueue_exchange(int s) {
 
 int exchange_settled(void);
 
+// A call that does not go through the windows of PT_LOOKAHEAD throws them away first, on every context (as pt_trace_batch
+// and friends do on one device): what it enqueues reuses the buffers a window may still be tracing into
+static int la_drop(void) { return (R.flags & PT_LOOKAHEAD) ? one::la_discard(one::LA_STREAM) : PT_OK; }
+
 // The frame on device 0 after calls that wrote the host image directly (multi_trace): one exchange of the running sums
 // as they are brings every peer's rows; every exchange does, so `frame_stale` falls with the next one of any kind.
 int multi_refresh(void) {
@@ -412,7 +417,8 @@ int multi_enqueue(int iter0, int count, bool overlap = false) {
                 const uint64_t t0 = g_xstats.on ? now_ns() : 0;
                 R.in_step = false;
                 R.ov_ok = true;
-                int r = enqueue_batch(iter0, count);
+                int r = la_drop();
+                if (!r) r = enqueue_batch(iter0, count);
                 R.ov_ok = false;
                 if (!r) r = worker_pack(*w, s);
                 if (g_xstats.on && w->index == 0) g_xstats.worker_ns += now_ns() - t0;
@@ -440,8 +446,10 @@ int multi_enqueue(int iter0, int count, bool overlap = false) {
     if (rc) return rc;
     rc = on_all([&](Worker &w) -> int {
         R.in_step = false;
+        int r = la_drop();
+        if (r) return r;
         R.ov_ok = overlap;
-        const int r = enqueue_batch(iter0, count);
+        r = enqueue_batch(iter0, count);
         R.ov_ok = false;
         if (r) return r;
         return worker_pack(w, s);
@@ -592,6 +600,8 @@ int multi_init(const pt_scene_desc *d, const std::vector<int> &devs) {
         if (w.index != 0) { mine.device_image = nullptr; mine.stream = nullptr; }
         const int r = one::pt_init(&mine);
         if (r) return r;
+        for (int k = 0; k < K; ++k)
+            if (k != w.index && devs[(size_t)k] == w.device) R.la_shared_device = true;
         w.map = R.map;
         w.floats = (size_t)R.map.tile_pixels * 3;
         {   // the exchange stream outranks the launch streams: its kernels (the pack's successor RCCL kernel, the unpack) are
@@ -763,7 +773,49 @@ static bool multi_pin(float *host, size_t bytes) {
     return true;
 }
 
+// PT_LOOKAHEAD: can every context serve pt_trace from its windows?  Asked once (it allocates the lanes), on the first call
+// that could go that way.
+static bool multi_la_ready(void) {
+    if (G.la_state == 0) {
+        std::vector<int> ok((size_t)G.K, 0);
+        (void)on_all([&](Worker &w) -> int { ok[(size_t)w.index] = one::la_ready() ? 1 : 0; return PT_OK; });
+        G.la_state = 1;
+        for (int v : ok) if (!v) G.la_state = -1;
+    }
+    return G.la_state > 0;
+}
+
+// this device's address of the registered host image
+static int worker_host_dev(Worker &w) {
+    if (w.host_dev_of != G.dhost) {
+        void *dp = nullptr;
+        HIPCHK(hipHostGetDevicePointer(&dp, G.dhost, 0));
+        w.host_dev = (float *)dp; w.host_dev_of = G.dhost;
+    }
+    return PT_OK;
+}
+
 static int multi_trace(uint8_t *pbo_rgba, int iter0, int count, float *host_image_sum) {
+    // PT_LOOKAHEAD, one iteration, no PBO, and a host image that is page-locked for every device (or none at all): every
+    // context serves its tile's sample from the windows it has traced ahead (pt_h_api.hpp: la_trace) and writes that tile's
+    // pixels into the caller's image itself -- as below, no exchange.  A PBO, a pageable image, batches: the paths after
+    // this one, every context's windows discarded first (la_drop).  The CU masks are only taken by a context alone on its
+    // device (ensure_la_masks).
+    const Renderer &c0 = G.w[0]->ctx;
+    if ((c0.flags & PT_LOOKAHEAD) && !pbo_rgba && count == 1 && iter0 >= 1 && !G.self_exchange && !c0.profiling &&
+        (!host_image_sum || ((c0.flags & PT_PIN_IMAGE) && multi_pin(host_image_sum, (size_t)G.npix * 12))) && multi_la_ready()) {
+        int rc = exchange_settled();
+        if (rc) return rc;
+        rc = on_all([&](Worker &w) -> int {
+            if (host_image_sum) {
+                const int r = worker_host_dev(w);
+                if (r) return r;
+            }
+            return one::pt_trace_ahead(iter0, host_image_sum ? w.host_dev : nullptr);
+        });
+        __atomic_store_n(&G.frame_stale, true, __ATOMIC_RELAXED);
+        return rc;
+    }
     // pathtrace() with the host image and no PBO, one iteration: no exchange at all -- every context's launch writes its
     // own tile's pixels (those whose sum changed) into the caller's image while it traces (pt_trace_mapped)
     if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange &&
@@ -771,11 +823,9 @@ static int multi_trace(uint8_t *pbo_rgba, int iter0, int count, float *host_imag
         int rc = exchange_settled();
         if (rc) return rc;
         rc = on_all([&](Worker &w) -> int {
-            if (w.host_dev_of != G.dhost) {
-                void *dp = nullptr;
-                HIPCHK(hipHostGetDevicePointer(&dp, G.dhost, 0));
-                w.host_dev = (float *)dp; w.host_dev_of = G.dhost;
-            }
+            int r = la_drop();
+            if (!r) r = worker_host_dev(w);
+            if (r) return r;
             return one::pt_trace_mapped(iter0, w.host_dev);
         });
         __atomic_store_n(&G.frame_stale, true, __ATOMIC_RELAXED);

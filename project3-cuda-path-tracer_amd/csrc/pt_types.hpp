@@ -125,6 +125,13 @@ __device__ __forceinline__ uint32_t sample_of(const TileMap &m, uint32_t pid) {
     return (((pid - q) >> 1) + q) >> m.div_shift;
 }
 
+// local_to_pixel for k_gather_one_tiled without its two divides: a tile is strips of span = strip_rows * W contiguous global
+// pixels, one strip in tile_count, so local pixel j sits at j + (j / span) * skip + first, with skip = (tile_count - 1) * span
+// and first = tile_index * span; j / span by the multiply-high of sample_of (magic / shift of make_div_magic, span >= 2)
+struct TileGather {
+    uint32_t magic, shift, skip, first;
+};
+
 struct Control {         // zeroed from `stamp` on by one hipMemsetAsync per batch (2 KiB)
     uint32_t iter0;                 // first iteration of the batch when the launches come from a replayed graph
     uint32_t keep[15];              //   (kernel arguments are frozen at capture time); survives the per-batch clear.

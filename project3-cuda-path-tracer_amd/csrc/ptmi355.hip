@@ -88,16 +88,33 @@ extern "C" int ptdbg_counts(unsigned int *out, int words) {
 }
 
 // diagnostics (not in include/ptmi355.h): PT_LOOKAHEAD's bookkeeping since pt_init -- out[0] = windows enqueued, out[1] = calls
-// that had to trace their own window first (misses), out[2] = windows discarded, out[3] = iterations of the window being consumed
+// that had to trace their own window first (misses), out[2] = windows discarded, out[3] = iterations of the window being consumed.
+// A multi-device session sums out[0..2] over its contexts (each traces windows of its own tile) and reports context 0's out[3].
 extern "C" int ptdbg_lookahead(unsigned long long out[4]) {
+    if (G.live) {
+        for (int k = 0; k < 4; ++k) out[k] = 0;
+        for (auto &wp : G.w) {                                 // (the contexts' threads are idle between calls)
+            const Renderer &c = wp->ctx;
+            out[0] += c.la_windows; out[1] += c.la_misses; out[2] += c.la_discards;
+        }
+        const Renderer &c0 = G.w[0]->ctx;
+        out[3] = c0.la[c0.la_cur].valid ? (unsigned long long)c0.la[c0.la_cur].count : 0ull;
+        return 0;
+    }
     if (!g_single.live) return -1;
     out[0] = g_single.la_windows; out[1] = g_single.la_misses; out[2] = g_single.la_discards;
     out[3] = g_single.la[g_single.la_cur].valid ? (unsigned long long)g_single.la[g_single.la_cur].count : 0ull;
     return 0;
 }
 
-// ... and the windows among out[0] that went to the lanes' CU-masked streams / the calls whose gather ran on the compute units set aside for it
+// ... and the windows among out[0] that went to the lanes' CU-masked streams / the calls whose gather ran on the compute units
+// set aside for it (summed over the contexts of a multi-device session)
 extern "C" int ptdbg_lookahead_masked(unsigned long long out[2]) {
+    if (G.live) {
+        out[0] = 0; out[1] = 0;
+        for (auto &wp : G.w) { out[0] += wp->ctx.la_masked_windows; out[1] += wp->ctx.la_masked_calls; }
+        return 0;
+    }
     if (!g_single.live) return -1;
     out[0] = g_single.la_masked_windows; out[1] = g_single.la_masked_calls;
     return 0;

@@ -5,6 +5,7 @@
 //   ptbench SCENEFILE.txt [--iters N] [--batch B] [--out BASENAME] [--sort] [--no-compact]
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
+//           [--per-call [--warmup W] [--no-lookahead]]
 //
 // --batch B: iterations per launch sequence (default: up to 64 and ~40 M paths, as the shim sizes its windows; 1 = one
 // pathtrace() per iteration); every batch but the last is enqueued without waiting, so consecutive batches overlap on the
@@ -23,7 +24,15 @@
 // keys unchanged), so K processes -- one per GPU, --device each -- render one frame between them; the other rows
 // of its image stay zero and the K raw sums (--pfm) add up, exactly, to the single-process image.
 //
+// --per-call: the reference's host pattern as the drop-in shim runs it -- ONE pt_trace per iteration, every call handing over
+// the page-locked host image, with the shim's flags (PT_COMPACT | PT_PIN_IMAGE | PT_HOST_SPARSE | PT_LOOKAHEAD, max_batch by the
+// shim's rule; --no-lookahead drops PT_LOOKAHEAD).  Each call is timed on the host clock (pt_trace returns with the image
+// complete); after W warm-up calls (default 64) it prints the median and mean ms per call and Grays/s = rays per iteration
+// (pt_get_stats over the whole run) over the MEAN call -- the calls that start a window wait for it, so the median alone
+// overstates what a run of calls delivers.  Works with --devices / --gpus.
+//
 // Links libptmi355.so (the HIP library) and host/pthost.cpp.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -37,12 +46,14 @@ int main(int argc, char **argv) {
     if (argc < 2) {
         printf("Usage: %s SCENEFILE.txt [--iters N] [--batch B] [--out BASE] [--sort] [--no-compact] [--cache-first] "
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
-               "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]\n", argv[0]);
+               "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
+               "[--per-call [--warmup W] [--no-lookahead]]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
     unsigned flags = PT_COMPACT | PT_PIN_IMAGE | PT_HOST_SPARSE;      // `image` below lives until pt_free and is only read here
-    bool pfm = false, save_sum = false;
+    bool pfm = false, save_sum = false, per_call = false, lookahead = true;
+    int warmup = 64;
     std::string resume;
     int start = -1;
     float lens_radius = 0.0f, focal_distance = 0.0f;
@@ -70,6 +81,9 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        else if (a == "--per-call") per_call = true;
+        else if (a == "--warmup" && i + 1 < argc) warmup = atoi(argv[++i]);
+        else if (a == "--no-lookahead") lookahead = false;
         else if (a == "--strip-rows" && i + 1 < argc) strip_rows = atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) { devices.clear(); for (int k = 0, n = atoi(argv[++i]); k < n; ++k) devices.push_back(k); }
         else if (a == "--devices" && i + 1 < argc) {
@@ -81,6 +95,10 @@ int main(int argc, char **argv) {
     pth_scene *sc = pth_load_scene(argv[1]);
     if (!sc) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     if (iters < 0) iters = sc->iterations;
+    if (per_call) {
+        flags |= PT_PIN_IMAGE | PT_HOST_SPARSE | (lookahead ? PT_LOOKAHEAD : 0u);
+        if (!resume.empty()) { fprintf(stderr, "--per-call does not combine with --resume\n"); return 1; }
+    }
     if (batch < 1) {                                      // not given: as the shim sizes its windows -- up to 64 iterations and ~40 M paths per batch
         const long long pixels = (long long)sc->camera.resolution[0] * sc->camera.resolution[1];
         const long long k = 41000000LL / (pixels > 0 ? pixels : 1);
@@ -121,6 +139,31 @@ int main(int argc, char **argv) {
     }
     const int first_iteration = iteration;
     const auto t0 = std::chrono::steady_clock::now();
+    if (per_call) {                                        // runCuda() through the shim: one pathtrace() per iteration, image every call
+        std::vector<double> ms;
+        long long served = 0;                              // rays as pt_get_stats reports them: every iteration once, whole
+        for (; iteration < iters; ++iteration) {
+            const auto c0 = std::chrono::steady_clock::now();
+            if (pt_trace(NULL, 0, iteration + 1, image.data()) != PT_OK) { fprintf(stderr, "pathtrace: %s\n", pt_last_error()); return 1; }
+            const auto c1 = std::chrono::steady_clock::now();
+            if (iteration >= warmup) ms.push_back(std::chrono::duration<double, std::milli>(c1 - c0).count());
+            pt_stats st;
+            if (pt_get_stats(&st) != PT_OK) { fprintf(stderr, "pt_get_stats: %s\n", pt_last_error()); return 1; }
+            served += st.rays;
+        }
+        if (ms.empty()) { fprintf(stderr, "--per-call: no call after %d warm-up calls (--iters %d)\n", warmup, iters); return 1; }
+        std::vector<double> sorted = ms;
+        std::sort(sorted.begin(), sorted.end());
+        const double med = sorted[sorted.size() / 2];
+        double mean = 0.0;
+        for (double v : ms) mean += v;
+        mean /= (double)ms.size();
+        const double rays_per_iter = (double)served / (double)iters;
+        printf("per-call: %zu calls after %d warm-up, median %.4f ms, mean %.4f ms, p10 %.4f, p90 %.4f; %.0f rays per iteration: "
+               "%.2f Grays/s (mean call; %.2f at the median) (lookahead %s, max_batch %d, %d device(s))\n",
+               ms.size(), warmup, med, mean, sorted[sorted.size() / 10], sorted[sorted.size() * 9 / 10], rays_per_iter,
+               rays_per_iter / (mean * 1e-3) / 1e9, rays_per_iter / (med * 1e-3) / 1e9, lookahead ? "on" : "off", batch, pt_num_devices());
+    }
     while (iteration < iters) {                            // runCuda: iteration++ ; pathtrace(pbo, 0, iteration)
         const int n = (iters - iteration < batch) ? iters - iteration : batch;
         const int last = (iteration + n == iters);
