@@ -261,14 +261,14 @@ static int init_impl(const pt_scene_desc *d) {
     R.scene.geoms = R.d_geoms; R.scene.ngeoms = d->num_geoms;
     R.scene.mats = R.d_mats; R.scene.nmats = d->num_materials;
     R.scene.tris = R.d_tris; R.scene.ntris = d->num_triangles;
-    {   // per-lane gather records (the three matrices, 4 columns x 3 rows each) and geom info words
+    {   // per-lane gather records (the matrices, 4 columns x 3 rows each; pt_k_scene.hpp: GREC_WORDS) and geom info words
         std::vector<float> gath((size_t)std::max(1, d->num_geoms) * GREC_WORDS, 0.0f);
         std::vector<uint32_t> ginfo((size_t)std::max(1, d->num_geoms), 0u);
         for (int i = 0; i < d->num_geoms; ++i) {
             const pt_geom &g = d->geoms[i];
             float *r = gath.data() + (size_t)i * GREC_WORDS;
             const pt_mat4 *ms[3] = {&g.inverseTransform, &g.transform, &g.invTranspose};
-            for (int m = 0; m < 3; ++m)
+            for (int m = 0; m < (g.type == PT_CUBE ? 2 : 3); ++m)     // a cube's words GREC_FACE..: k_face_normals below
                 for (int c = 0; c < 4; ++c)
                     for (int rr = 0; rr < 3; ++rr) r[m * 12 + c * 3 + rr] = ms[m]->m[c][rr];
             ginfo[(size_t)i] = (uint32_t)g.materialid | ((uint32_t)g.type << 28);
@@ -278,6 +278,12 @@ static int init_impl(const pt_scene_desc *d) {
         HIPCHK(hipMalloc((void **)&R.d_ginfo, ginfo.size() * 4));
         HIPCHK(hipMemcpy(R.d_grec, gath.data(), gath.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(R.d_ginfo, ginfo.data(), ginfo.size() * 4, hipMemcpyHostToDevice));
+        if (d->num_geoms > 0) {                            // the cubes' face normals, words GREC_FACE.. (on the device only)
+            hipLaunchKernelGGL(k_face_normals, dim3((d->num_geoms * 8 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream,
+                               R.d_grec, (const uint32_t *)R.d_ginfo, d->num_geoms);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(R.stream));
+        }
         R.scene.grec = R.d_grec; R.scene.ginfo = R.d_ginfo;
     }
     R.mesh_mode = MESH_NONE;

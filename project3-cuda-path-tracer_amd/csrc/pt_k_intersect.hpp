@@ -109,17 +109,26 @@ __device__ __forceinline__ void tile_result(const WaveQ &q, int par, const Scene
     const unsigned long long key = q.best(par)[lane];
     t = -1.0f; n = ptd::mk(0, 0, 0); mat = 0; outside = 1;
     int geom = -1;
+    uint32_t info = 0;
     if (key != ~0ull) {
-        const float *w = q.win(par) + lane;
-        t = __uint_as_float((uint32_t)(key >> 32)); geom = (int)((uint32_t)key >> 1); outside = (int)((uint32_t)key & 1u);
-        n = ptd::mk(w[0], w[64], w[128]);
+        const uint32_t lo = (uint32_t)key;                  // geom << 4 | code << 1 | outside
+        t = __uint_as_float((uint32_t)(key >> 32)); geom = (int)(lo >> 4); outside = (int)(lo & 1u);
+        info = acc.ginfo[geom];
+        if ((info >> 28) == (uint32_t)PT_CUBE) {            // the face table (k_face_normals)
+            const float *f = acc.grec + (size_t)geom * GREC_WORDS + GREC_FACE + 3 * ((lo >> 1) & 7u);
+            n = ptd::mk(f[0], f[1], f[2]);
+        } else {                                            // a sphere: the winner record cand_pass1 wrote
+            const float *w = q.win(par) + lane;
+            n = ptd::mk(w[0], w[64], w[128]);
+        }
     }
     if (mb.geom >= 0 && (geom < 0 || t > mb.t || (t == mb.t && mb.geom < geom))) {     // pathtrace.cu:192 across all geoms
         const float *tv = tris + (size_t)mb.tri * TRI_WORDS;
         t = mb.t; geom = mb.geom; outside = 1;
         n = ptd::normalize(ptd::cross(ptd::mk(tv[3], tv[4], tv[5]), ptd::mk(tv[6], tv[7], tv[8])));
+        info = acc.ginfo[geom];
     }
-    if (geom >= 0) mat = (int)(acc.ginfo[geom] & 0x0fffffffu);
+    if (geom >= 0) mat = (int)(info & 0x0fffffffu);
 }
 
 

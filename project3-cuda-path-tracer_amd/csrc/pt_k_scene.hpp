@@ -10,23 +10,28 @@ namespace {
 // ---------------------------------------------------------------------------
 // Dynamic LDS carve (no static __shared__: the dynamic base stays 16-B aligned, guide G17):
 //   [ctl: 16 dwords]
-//   [scene block, SLDS only: materials nmats*12 | ginfo ngeoms (padded to 4) | gather records ngeoms*36]
+//   [scene block, SLDS only: materials nmats*12 | ginfo ngeoms (padded to 4) | gather records ngeoms*52]
 //   [per wave: PW_WORDS]  [per wave: TRQ_WORDS, the triangle candidate ring + best keys (MESH_TILES only)]
 // What every lane of a wave reads alike (the cull boxes, mesh records) comes through wave-uniform scalar
 // loads from global memory; what lanes gather individually (the matrices of the primitive a candidate names,
 // the material of a winner) is staged in LDS when the scene fits (SLDS) and read from global memory through
 // the vector cache when it does not (any number of primitives / materials).
 constexpr int LDS_CTL_WORDS = 32;    // [0] last-block flag, [8..11] traced counts, [16..31] the last workgroup's scan scratch (two steps x two sums x four waves)
-constexpr int GREC_WORDS = 36;       // gather record per geom: inverseTransform[12] transform[12] invTranspose[12], each
-                                     // 4 columns x 3 rows.  Stride 36 words: records of 16 consecutive geoms start in
-                                     // distinct 4-bank slots, so a ds_read_b128 by 64 lanes naming different geoms does
-                                     // not conflict (the r01 layout, stride 32, put every geom on the same banks: 24 %
-                                     // of the LDS cycles were bank conflicts)
+constexpr int GREC_WORDS = 52;       // gather record per geom: inverseTransform[12] transform[12], each 4 columns x 3 rows,
+                                     // then by type a sphere's invTranspose[12] or a cube's face normals[8][3].
+                                     // Stride 52 words = 13 4-bank slots, odd: records of 16 consecutive geoms start in
+                                     // distinct slots, so a ds_read_b128 by 64 lanes naming different geoms does not
+                                     // conflict (the r01 layout, stride 32, put every geom on the same banks: 24 % of
+                                     // the LDS cycles were bank conflicts)
+constexpr int GREC_FACE = 24;        // cube: + 3 * code: normalize(transform * face_from_code(code)), x y z (k_face_normals),
+                                     // in the words where a sphere keeps its invTranspose: 52 words, not 36 + 24, keep the
+                                     // scene block small enough for six workgroups of the fused bounce kernel per CU
+                                     // beside the Cornell scenes
 // per-wave block: candidate ring + two tiles in flight (rays, best keys, winner records)
 constexpr int Q_SLOTS = 128;         // candidate ring entries (a tile's cull adds <= 64 per geom while < 64 wait)
 constexpr int PW_RING = 0;                               // u32[128]: lane | parity << 6 | type << 7 | geom << 9
-constexpr int PW_BEST = PW_RING + Q_SLOTS;               // u64[2][64]: (bits(t) << 32) | geom << 1 | outside, ~0 = nothing hit
-constexpr int PW_WIN = PW_BEST + 2 * 64 * 2;             // float[2][3][64]: winner's normal x, y, z (the outside flag rides in the key)
+constexpr int PW_BEST = PW_RING + Q_SLOTS;               // u64[2][64]: (bits(t) << 32) | geom << 4 | code << 1 | outside, ~0 = nothing hit
+constexpr int PW_WIN = PW_BEST + 2 * 64 * 2;             // float[2][3][64]: a sphere winner's normal x, y, z (cubes: the face table)
 constexpr int PW_RAYS = PW_WIN + 2 * 64 * 3;             // float[2][6][64]: ro.xyz rd.xyz of the tile's paths
 constexpr int PW_WORDS = PW_RAYS + 2 * 6 * 64;           // 1536 dwords = 6 KiB per wave: six workgroups fit a CU's 160 KiB beside a
                                                          // Cornell-sized scene block (round 2: 6.5 KiB, float4 winner records, five)
@@ -65,6 +70,22 @@ __device__ __forceinline__ SceneAcc stage_scene(float *lds_scene, const SceneDev
     __syncthreads();
     acc.mats = mats; acc.ginfo = ginfo; acc.grec = grec;
     return acc;
+}
+
+// A cube's surface normal, normalize(transform * (face, 0)) (intersections.h:89), depends on the geom and the face code
+// alone.  The exact-test pass used to evaluate it for every cube hit before it knew whether the hit wins; now it is
+// evaluated once per (geom, code) at pt_init, by the very device functions the pass used (bit-identical by
+// construction), into words GREC_FACE.. of the cubes' gather records, and only the winner's entry is read (tile_result).
+// Thread k: geom k / 8, code k % 8 (code 7 = the zero vector included; 6 never comes out of cube_slabs).
+__global__ __launch_bounds__(BLOCK) void k_face_normals(float *grec, const uint32_t *ginfo, int ngeoms) {
+    const int k = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (k >= ngeoms * 8) return;
+    const int g = k >> 3, code = k & 7;
+    float *r = grec + (size_t)g * GREC_WORDS;
+    if ((ginfo[g] >> 28) != (uint32_t)PT_CUBE) return;
+    const f3 n = ptd::normalize(ptd::mv_dir(r + 12, ptd::face_from_code(code)));
+    float *f = r + GREC_FACE + 3 * code;
+    f[0] = n.x; f[1] = n.y; f[2] = n.z;
 }
 
 // Geom-uniform records are read through the CONSTANT address space: the arrays are immutable for the
@@ -267,26 +288,25 @@ __device__ __forceinline__ void cand_pass1(const WaveQ &q, const SceneAcc &acc, 
             }
             f3 obj_p;
             const float t = ptd::world_distance(m, ro, qo, qd, t_obj, obj_p);
-            // normal: cube = normalize(transform * (face, 0)), sphere = +-normalize(invTranspose * (objP, 0))
-            f3 nv = obj_p;
-            if (type == PT_CUBE) {
-                nv = ptd::face_from_code(code);
-            } else {
-                const float4 a = rec4[6], b = rec4[7], c = rec4[8];
-                m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
-                m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
-            }
-            f3 n = ptd::normalize(ptd::mv_dir(m, nv));
-            if (type != PT_CUBE && !outside) n = ptd::neg(n);
             if (t > 0.0f) {                                                // pathtrace.cu:192
-                // positive floats order like their bit patterns; geom << 1 | outside: the lowest geom wins a tie in t
-                // (the flag belongs to the geom: it cannot reorder two different geoms)
-                const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | (g << 1) | (uint32_t)(outside & 1);
+                // positive floats order like their bit patterns; geom << 4 | code << 1 | outside: the lowest geom wins a
+                // tie in t (code and flag belong to the geom: they cannot reorder two different geoms; a sphere's code is 7)
+                const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | (g << 4) |
+                                               ((uint32_t)code << 1) | (uint32_t)(outside & 1);
                 unsigned long long *bk = q.best(par) + origin;
                 __hip_atomic_fetch_min(bk, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                // LDS operations of one wave execute in order: every min of this pass precedes this read
-                if (*bk == key) { float *w = q.win(par) + origin; w[0] = n.x; w[64] = n.y; w[128] = n.z; }
+                // a cube's normal is the face table's entry (geom, code), read for the winner only (tile_result); a sphere's,
+                // +-normalize(invTranspose * (objP, 0)), depends on the ray: the lane whose key is the minimum writes it
+                if (type != PT_CUBE) {
+                    const float4 a = rec4[6], b = rec4[7], c = rec4[8];
+                    m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
+                    m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
+                    f3 n = ptd::normalize(ptd::mv_dir(m, obj_p));
+                    if (!outside) n = ptd::neg(n);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    // LDS operations of one wave execute in order: every min of this pass precedes this read
+                    if (*bk == key) { float *w = q.win(par) + origin; w[0] = n.x; w[64] = n.y; w[128] = n.z; }
+                }
             }
         }
     }
