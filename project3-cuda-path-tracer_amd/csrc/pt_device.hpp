@@ -500,9 +500,11 @@ struct PathState {
     f3 o, d, c;
 };
 
-// returns true when the path stays alive; on false `ps.c` is the final colour
+// returns true when the path stays alive; on false `ps.c` is the final colour.  `defer_diffuse`: a diffuse survivor
+// keeps the hit normal in `ps.d` and sets `*deferred` -- hemisphere(n, seeded_engine(iter, pixel, depth)) is left to
+// whoever reads the path next (the next bounce's load, or the export); everything else is as without it
 PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, const float *mats,
-                       int iter, int pixel, int depth, bool last_bounce) {
+                       int iter, int pixel, int depth, bool last_bounce, bool defer_diffuse = false, bool *deferred = nullptr) {
     if (t > 0.0f) {
         const float *m = mats + matId * MAT_WORDS;
         f3 mcol = mk(m[0], m[1], m[2]);
@@ -517,15 +519,18 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
             ps.c = mk(0.0f, 0.0f, 0.0f);
             return false;
         }
-        uint32_t rng = seeded_engine(iter, pixel, depth);
+        // the engine on the lanes that draw: dielectrics, and diffuse survivors that are not deferred (one instance)
+        const bool mirror = m[6] > 0.0f, glass = m[7] > 0.0f;
+        uint32_t rng = 0;
+        if (!mirror && (glass || !defer_diffuse)) rng = seeded_engine(iter, pixel, depth);
         f3 P = point_on_ray(ps.o, ps.d, t);
         f3 I = ps.d;
         f3 scol = mk(m[3], m[4], m[5]);
-        if (m[6] > 0.0f) {                                 // mirror
+        if (mirror) {                                      // mirror
             ps.d = reflect(I, n);
             ps.o = P;
             ps.c = mul(ps.c, scol);
-        } else if (m[7] > 0.0f) {                          // Fresnel dielectric
+        } else if (glass) {                                // Fresnel dielectric
             float d0 = dot(I, n);
             f3 nn = d0 > 0.0f ? neg(n) : n;
             float ior = m[8];
@@ -554,7 +559,8 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
             }
             ps.c = mul(ps.c, scol);
         } else {                                           // diffuse
-            ps.d = hemisphere(n, rng);
+            if (defer_diffuse) { ps.d = n; *deferred = true; }
+            else ps.d = hemisphere(n, rng);
             ps.o = P;
             ps.c = mul(ps.c, mcol);
         }

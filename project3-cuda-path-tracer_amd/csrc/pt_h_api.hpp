@@ -153,6 +153,8 @@ static int init_impl(const pt_scene_desc *d) {
     R.epi_enabled = true;
     if (const char *e = pt_experiment("PTMI355_HOST_EPILOGUE")) R.epi_enabled = atoi(e) != 0;
     if (const char *e = pt_experiment("PTMI355_EPI_DIRECT")) R.epi_direct_enabled = atoi(e) != 0;
+    R.defer_enabled = true;
+    if (const char *e = pt_experiment("PTMI355_DEFER_DIR")) R.defer_enabled = atoi(e) != 0;
     R.host_sparse_enabled = (d->flags & (PT_HOST_SPARSE | PT_SHARED_IMAGE)) != 0;
     if (const char *e = pt_experiment("PTMI355_ASYNC_DIRECT")) R.async_direct_enabled = atoi(e) != 0;
     R.pin_enabled = true;
@@ -931,7 +933,7 @@ int pt_export_paths(pt_path_segment *host_paths, int capacity, int *n_live) {
         }
         hipLaunchKernelGGL(k_export_paths, dim3((n + 255) / 256), dim3(256), 0, R.stream, R.pool[R.cur], R.map, n,
                            live, R.trace_depth - R.step_depth, (pt_path_segment *)R.scratch,
-                           tile_dir(packed ? R.cur_dir : -1), span);
+                           tile_dir(packed ? R.cur_dir : -1), span, R.step_iter0, R.step_depth - 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(host_paths, R.scratch, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost, R.stream));
         HIPCHK(hipStreamSynchronize(R.stream));

@@ -209,6 +209,13 @@ int enqueue_bounce(int depth) {
         return PT_OK;
     }
     const bool cached0 = depth == 0 && !unfused && (R.flags & PT_CACHE_FIRST);
+    // Diffuse survivors leave their direction to the next bounce (pt_types.hpp: PENDING_DIR) when that bounce is the fused
+    // compacting k_bounce without mesh pre-pass or material keys, the one kernel that draws it when it loads the path
+    // (tile_load<RESOLVE>).  The pipeline is fixed for the session (pt_init's flags), so the next bounce of this batch --
+    // stepped or not -- is that kernel here; pt_export_paths draws pending directions itself.  Every other reader (k_mesh,
+    // k_intersect, the sort kernels, k_iteration's own pools) gets the eager form.
+    a.defer_dir = (compact && !unfused && R.mesh_mode == MESH_NONE && R.sort_keys == 0 && depth + 1 < R.trace_depth &&
+                   R.defer_enabled) ? 1 : 0;
     if (cached0 && !R.cache_valid) {
         StageTimer tm(PT_STAGE_INTERSECT);
         const Isect cache{R.cache_mem, (uint32_t)R.map.tile_pixels};

@@ -166,6 +166,7 @@ struct Renderer {
     float *epi_host = nullptr;    // pt_trace: the caller's image, device-mapped, for k_iteration's own gather (this call only)
     bool epi_done = false;        // ... and k_iteration took it
     bool epi_direct_enabled = true;   // PTMI355_EPI_DIRECT=0: such launches keep the final-colour buffer and gather per wave at their end
+    bool defer_enabled = true;    // PTMI355_DEFER_DIR=0: every scatter stores its direction (no PENDING_DIR slots; the A/B control)
     bool host_sparse_enabled = false; // PT_HOST_SPARSE (implied by PT_SHARED_IMAGE): only the pixels whose sum changed are written to a host image the launch wrote last
     uint64_t image_epoch = 0;     // bumped by everything that changes the accumulation buffer
     float *host_synced = nullptr; // the (device-mapped) host image that held exactly the buffer's content at epoch host_epoch

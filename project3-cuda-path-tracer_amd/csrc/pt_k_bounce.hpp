@@ -66,8 +66,12 @@ struct TileRegs {
 
 // First half of one 64-path tile of one bounce: load (or generate) the paths.  `i` = logical path index (what
 // MODE_ISECT planes and the mesh mask are keyed by), `src` = pool slot.
-template <bool GEN>
-__device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c, const Pool &in,
+// RESOLVE: the pool may hold diffuse survivors whose direction the bounce that wrote it left pending (PENDING_DIR in the
+// pid, the hit normal in the direction row): they draw it here, with the same engine (that bounce's depth) and the same
+// sampler, so the ray is the one the writer would have stored.  The tile is compacted, so this runs ~60 lanes wide where
+// the writer's scatter ran ~46 (misses and light hits end in the same tiles as the survivors).
+template <bool GEN, bool RESOLVE = false>
+__device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c, const Pool &in, int depth,
                                           uint32_t tile, uint32_t i, uint32_t src, bool have, bool active,
                                           TileRegs &tr, f3 &ro, f3 &rd) {
     constexpr bool gen_rays = GEN;
@@ -89,6 +93,8 @@ __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c,
             if (tr.pid == DEAD_PID) active = false;
         }
     }
+    bool pending = false;
+    if (RESOLVE && active) { pending = (tr.pid & PENDING_DIR) != 0u; tr.pid &= ~PENDING_DIR; }
     if (active) {
         if (c.kmisc) {
             const TileMap map = karg_struct<TileMap>(offsetof(BounceArgs, map));
@@ -101,6 +107,10 @@ __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c,
             tr.pixel = local_to_pixel(a.map, (int)(tr.pid - tr.smp * (uint32_t)a.map.tile_pixels));
             if (gen_rays) camera_ray(a.cam, a.lens, a.trace_depth, c.iter0 + (int)tr.smp, tr.pixel, a.map.W, ro, rd);
         }
+    }
+    if (RESOLVE && pending) {
+        uint32_t rng = ptd::seeded_engine(c.iter0 + (int)tr.smp, tr.pixel, depth - 1);
+        rd = ptd::hemisphere(rd, rng);
     }
     tr.active = active;
 }
@@ -133,18 +143,20 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 
 // SORT (PT_SORT_MATERIAL, fused form): the survivors of key (= material hit) k go to the wave's span of range
 // k * W + w -- `key_stride` slots further per key -- and `packed` is per LANE: lane k counts the wave's key-k survivors.
-template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false>
+// DEFER: BounceArgs::defer_dir is honoured (the launch plan sets it only where the next bounce resolves)
+template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = false>
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
                                            uint32_t n, uint32_t dst_base, uint32_t &packed, uint32_t &traced,
                                            uint32_t key_stride = 0) {
     const int lane = c.lane;
-    bool alive = false;
+    bool alive = false, deferred = false;
     ptd::PathState ps;
     ps.o = ro; ps.d = rd; ps.c = tr.col;
     if (tr.active) {
+        const bool defer = DEFER && (c.kargs ? karg_field<int>(offsetof(BounceArgs, defer_dir)) : a.defer_dir) != 0;
         alive = ptd::shade_scatter(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
-                                   depth == a.trace_depth - 1);
+                                   depth == a.trace_depth - 1, defer, &deferred);
         if (!alive) {
             if (c.epi_direct) {
                 // finalGather for this path, here (pathtrace.cu:380-392 at one sample per pixel): image[pixel] += colour, the
@@ -184,7 +196,7 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
         pf(p, 0) = ps.o.x; pf(p, 1) = ps.o.y; pf(p, 2) = ps.o.z;
         pf(p, 3) = ps.d.x; pf(p, 4) = ps.d.y; pf(p, 5) = ps.d.z;
         pf(p, 6) = ps.c.x; pf(p, 7) = ps.c.y; pf(p, 8) = ps.c.z;
-        ppid(p) = tr.pid;
+        ppid(p) = deferred ? (tr.pid | PENDING_DIR) : tr.pid;
         // mesh pre-pass of the NEXT bounce: flag the slot when the new ray can reach a mesh at all (~11 % of them on
         // C4), so that k_mesh neither scans nor loads the other 89 %
         if (MESH == MESH_PRE) {
@@ -203,7 +215,7 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
 
 // the tile with parity `par` has been fully tested: read its rays back from the wave's LDS block, fold the
 // winner and shade
-template <bool COMPACT, int MESH, bool SORT = false>
+template <bool COMPACT, int MESH, bool SORT = false, bool DEFER = false>
 __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &c, const WaveQ &q, int par, const Pool &in,
                                             const Pool &out, int depth, const TileRegs &tr, uint32_t n, uint32_t dst_base,
                                             uint32_t &packed, uint32_t &traced, uint32_t key_stride = 0) {
@@ -212,7 +224,7 @@ __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &
     const f3 rd = ptd::mk(ry[192], ry[256], ry[320]);
     float t = -1.0f; f3 nrm = ptd::mk(0, 0, 0); int mat = 0, outside = 1;
     if (tr.active) tile_result(q, par, c.acc, a.scene.tris, tr.mb, t, nrm, mat, outside);
-    tile_shade<COMPACT, MESH, SORT>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride);
+    tile_shade<COMPACT, MESH, SORT, DEFER>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride);
 }
 
 // The tiles [first, first + count) of one wave's run at one bounce, two in flight (see the intersection stages
@@ -230,7 +242,9 @@ struct WgSpans {
 // GEN: bounce 0 of a batch generates the camera rays in registers (a compile-time switch: the camera, the lens and
 // the candidate masks then never occupy scalar registers in the kernels of the other bounces, and the pool's input
 // side never does in bounce 0's)
-template <int MODE, bool COMPACT, int MESH, bool GEN, bool SORT = false>
+// DEFER / RESOLVE: this kernel may leave diffuse directions pending in its output (tile_shade) / draws the pending ones
+// of its input (tile_load)
+template <int MODE, bool COMPACT, int MESH, bool GEN, bool SORT = false, bool DEFER = false, bool RESOLVE = false>
 __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c, WaveQ &q, const Pool &in, const Pool &out,
                                           int depth, uint32_t first_tile, uint32_t count, uint32_t tiles,
                                           uint32_t n, bool packed_in, uint32_t span_in, uint32_t &cur, uint32_t dst_base,
@@ -285,7 +299,7 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
         }
         TileRegs tr;
         f3 ro, rd;
-        tile_load<GEN>(a, c, in, tile, i, src, have, active, tr, ro, rd);
+        tile_load<GEN, RESOLVE>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd);
         if (MODE == MODE_FUSED) {
             const float4 *pre_hit = nullptr;
             if (MESH == MESH_PRE && tr.active) {
@@ -303,7 +317,7 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
             const uint32_t ticket = q.total;
             if (pending) {
                 drain_to(q, c.acc, prev_ticket);
-                tile_finish<COMPACT, MESH, SORT>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+                tile_finish<COMPACT, MESH, SORT, DEFER>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
             }
             prev = tr; prev_ticket = ticket; pending = true; par ^= 1;
         } else {
@@ -316,12 +330,12 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
                 const int m = at(a.isect.mat(), k);
                 mat = m & 0x7fffffff; outside = (m < 0) ? 0 : 1;
             }
-            tile_shade<COMPACT>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced);
+            tile_shade<COMPACT, MESH_NONE, false, DEFER>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced);
         }
     }
     if (pending) {
         drain_to(q, c.acc, prev_ticket);
-        tile_finish<COMPACT, MESH, SORT>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+        tile_finish<COMPACT, MESH, SORT, DEFER>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
     }
 }
 
@@ -359,6 +373,10 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
     const int lane = threadIdx.x & 63;
     c.lane = lane;
     const uint32_t Wp = gridDim.x * WAVES;                        // waves of the grid
+    // deferred diffuse directions (BounceArgs::defer_dir): the compacting kernels without mesh pre-pass or material keys may
+    // leave them pending; the fused one of bounces >= 1 -- the only reader the launch plan lets them reach -- draws them
+    constexpr bool DEFER = COMPACT && MESH == MESH_NONE && !SORT && MODE != MODE_ISECT;
+    constexpr bool RESOLVE = MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE && !SORT && !GEN;
     // runs of tiles the pool is cut into: one per wave -- or, with the material sort, several (RangeDir::W = S * Wp).
     // Consecutive logical tiles of a sorted pool hold paths that all hit the SAME material at the last bounce, and what a
     // path costs depends on where it has just been (a run of paths that left the glass ball is all sphere candidates):
@@ -387,7 +405,7 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
             cur = aligned ? find_range(a.dir_in.tbase(), a.dir_in.nr, wid * R) : find_range(a.dir_in.base(), a.dir_in.nr, wid * R * TILE);
         STAMP(2);
         // the run's R consecutive 64-path tiles; no workgroup barrier inside the loop
-        run_tiles<MODE, COMPACT, MESH, GEN, SORT>(a, c, q, a.in, a.out, a.depth, wid * R, R, tiles, n, packed_in, span_in,
+        run_tiles<MODE, COMPACT, MESH, GEN, SORT, DEFER, RESOLVE>(a, c, q, a.in, a.out, a.depth, wid * R, R, tiles, n, packed_in, span_in,
                                                   cur, wid * R * TILE, false, WgSpans{}, packed, traced, W * R * TILE, aligned);
         if (COMPACT) {
             // every run publishes its range count(s); the last workgroup out scans them

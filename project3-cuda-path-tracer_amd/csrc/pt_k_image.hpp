@@ -208,9 +208,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(16), amdgpu_n
     }
 }
 
-// pool <-> reference AoS (debug / parity export and pt_intersect_once)
+// pool <-> reference AoS (debug / parity export and pt_intersect_once).  A slot whose direction is pending (PENDING_DIR)
+// gets it drawn here as the next bounce's load would: `iter0` = the batch's first iteration, `wdepth` = the depth of the
+// bounce that wrote the pool.
 __global__ void k_export_paths(Pool p, TileMap map, uint32_t n_total, uint32_t n_live, int remaining,
-                               pt_path_segment *out, RangeDir dir, uint32_t span) {
+                               pt_path_segment *out, RangeDir dir, uint32_t span, int iter0, int wdepth) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
     uint32_t src = i;
@@ -227,12 +229,19 @@ __global__ void k_export_paths(Pool p, TileMap map, uint32_t n_total, uint32_t n
     s.ray.origin = {p.f(src, 0), p.f(src, 1), p.f(src, 2)};
     s.ray.direction = {p.f(src, 3), p.f(src, 4), p.f(src, 5)};
     s.color = {p.f(src, 6), p.f(src, 7), p.f(src, 8)};
-    const uint32_t pid = p.pid(src);
+    uint32_t pid = p.pid(src);
     if (pid == DEAD_PID) { s.pixelIndex = -1; s.remainingBounces = 0; }
     else {
+        const bool pending = (pid & PENDING_DIR) != 0u;
+        pid &= ~PENDING_DIR;
         const uint32_t sm = sample_of(map, pid);
         s.pixelIndex = local_to_pixel(map, (int)(pid - sm * (uint32_t)map.tile_pixels));
         s.remainingBounces = i < n_live ? remaining : 0;
+        if (pending) {
+            uint32_t rng = ptd::seeded_engine(iter0 + (int)sm, s.pixelIndex, wdepth);
+            const ptd::f3 d = ptd::hemisphere(ptd::mk(s.ray.direction.x, s.ray.direction.y, s.ray.direction.z), rng);
+            s.ray.direction = {d.x, d.y, d.z};
+        }
     }
     out[i] = s;
 }

@@ -44,6 +44,10 @@ enum { MESH_NONE = 0, MESH_TILES = 1, MESH_BVH = 2, MESH_PRE = 3 };   // how tri
                                            // of the lane-dense mesh pre-pass (k_mesh) read back
 constexpr int MAX_DEPTH = 64;
 constexpr uint32_t DEAD_PID = 0xffffffffu;
+// bit 31 of a live slot's pid: the slot's direction row holds the hit normal of a diffuse scatter whose direction is
+// still to be drawn.  pids stay below 2^30 (pt_init: cap * 4 < 2^32), so DEAD_PID is the only
+// word with this bit set that is not a pending slot.
+constexpr uint32_t PENDING_DIR = 0x80000000u;
 
 // ---------------------------------------------------------------------------
 // device-side parameter blocks (few pointers: every extra pointer pair costs
@@ -332,6 +336,9 @@ struct BounceArgs {
     // material sort, two-kernel form: table[key][workgroup] of k_sort_hist / k_shade_sorted; keys = materials + 1 (misses)
     uint32_t *sort_table;
     int nbins;
+    // diffuse survivors leave their direction to the next bounce, which draws it when it loads them (PENDING_DIR): set by
+    // the launch plan only when that bounce is a k_bounce that resolves (tile_load<RESOLVE>)
+    int defer_dir;
 };
 
 // what k_intersect needs to generate bounce 0's camera rays itself (sorted batches: no k_raygen, no pool to read)
