@@ -23,7 +23,7 @@
  * pt_last_error() then describes the failure.  The library never falls back
  * to a CPU path: without a HIP device every call fails with PT_ERR_DEVICE.
  *
- * Environment.  The shipped library reads exactly these ten variables, at
+ * Environment.  The shipped library reads exactly these nine variables, at
  * pt_init (PTMI355_RCCL_LIB: when RCCL is first needed).  NONE of them changes a
  * result: images, per-bounce statistics and path order are bit-identical under
  * every setting (each is exercised against the default by a `-m gpu` test, named
@@ -42,7 +42,6 @@
  *                                   0 = strictly one after the other)        [test_overlapped_small_batches]
  *   PTMI355_OVERLAP_GB=<GB>         memory the lanes' extra path pools may take (they are dropped when it does
  *                                   not suffice)                             [test_overlapped_small_batches]
- *   PTMI355_GRAPH=1                 batches captured once and replayed with hipGraphLaunch  [test_graph_replay_equals_direct_launches]
  *   PTMI355_CULL0=0|1               the per-camera bounce-0 candidate masks (k_cull0_mask) off / on  [test_bounce0_candidate_masks]
  *   PTMI355_SCENE_LDS=0             scene records read through the vector cache instead of staged in LDS (what
  *                                   scenes too large for LDS get anyway)     [test_scene_gathers_from_global_memory]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """trace_overlap.py KERNEL_TRACE.csv STEPS [LAUNCHES_PER_STEP]: the timed steps of a bench.py run in a rocprofv3 kernel
-trace, when consecutive steps OVERLAP on the device (the default: csrc/ptmi355.hip, enqueue_batch_direct).
+trace, when consecutive steps OVERLAP on the device (the default: csrc/pt_h_enqueue.hpp: enqueue_batch).
 
 Under overlap a kernel's own duration says little (two launches share the chip, each takes longer) and the SUM of the
 durations exceeds the wall time.  What can be held against bench.py's ms_per_step is the timeline: the span from the

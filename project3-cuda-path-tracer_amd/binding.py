@@ -180,7 +180,7 @@ def version():
 
 def has_experiments():
     """True for a -DPT_EXPERIMENTS build (profiles/tools/build_variant.sh, loaded through PTMI355_LIB): the library then
-    reads the experiment / test-hook environment variables of rounds 1-4; the shipped build reads the ten documented in
+    reads the experiment / test-hook environment variables of rounds 1-4; the shipped build reads the nine documented in
     include/ptmi355.h and nothing else."""
     return "+experiments" in version()
 

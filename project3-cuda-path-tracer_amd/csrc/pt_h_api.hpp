@@ -40,7 +40,6 @@ void pt_free(void) {
     if (R.d_grec) (void)hipFree(R.d_grec);
     if (R.d_tri_bound) (void)hipFree(R.d_tri_bound);
     if (R.d_ginfo) (void)hipFree(R.d_ginfo);
-    drop_graphs();
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -137,7 +136,6 @@ static int init_impl(const pt_scene_desc *d) {
     R = Renderer{};
     R.desc = *d; R.cam = d->camera; R.trace_depth = d->trace_depth; R.flags = d->flags; R.device = d->device;
     R.lens = Lens{(d->flags & PT_AA_JITTER) ? 1 : 0, d->lens_radius, d->focal_distance};
-    if (const char *ug = getenv("PTMI355_GRAPH")) R.use_graphs = atoi(ug) != 0;
     R.whole_max_paths = 6000000;     // measured at 800x800 (r02): 1 spp +38 %, 4 spp +20 %, 8 spp +8 %, 16 spp -4 %
     if (const char *wm = getenv("PTMI355_WHOLE_MAX")) R.whole_max_paths = strtoull(wm, nullptr, 10);
     R.whole_max_host_paths = 16000000;
@@ -503,7 +501,7 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
     if (trace_depth < 1 || trace_depth > MAX_DEPTH)
         return fail(PT_ERR_INVALID, "pt_set_camera: trace_depth %d outside [1, %d]", trace_depth, MAX_DEPTH);
     if (memcmp(&R.cam, camera, sizeof R.cam) != 0) {
-        R.cache_valid = false; drop_graphs();                  // refill the bounce-0 cache
+        R.cache_valid = false;                                  // refill the bounce-0 cache
         // windows traced ahead for the old camera are void, and what follows rewrites masks and boxes their launches read
         const int rc = la_discard(LA_HOST);
         if (rc) return rc;
@@ -515,12 +513,10 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
         if (std::isfinite(reach) && reach > (double)R.scene.rmax && reach != R.cull_eye_reach) {
             const int rc = upload_cull(&R.desc, *camera);
             if (rc != PT_OK) return rc;
-            drop_graphs();
             recull = true;
         }
     }
     if (trace_depth != R.trace_depth) {
-        drop_graphs();
         // the per-batch clear covers the election buckets of the bounces that can run
         R.ctl_bytes = offsetof(Control, bucket) - offsetof(Control, stamp) +
                       (size_t)trace_depth * sizeof(((Control *)nullptr)->bucket[0]);
@@ -542,14 +538,11 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
         const int rc = upload_bvh(&R.desc, R.grec_keep);
         if (rc != PT_OK) return rc;
         HIPCHK(hipMemcpy(R.d_geoms, R.grec_keep.data(), R.grec_keep.size() * 4, hipMemcpyHostToDevice));
-        drop_graphs();
     }
     if ((moved || recull) && R.mesh_mode == MESH_BVH) {
-        const bool had = R.cam_mask_valid;
         HIPCHK(hipStreamSynchronize(R.stream));                  // launches in flight still read the old mask
         const int rc = update_cam_mask();
         if (rc != PT_OK) return rc;
-        if (had != R.cam_mask_valid) drop_graphs();              // the mask pointer is a (frozen) kernel argument
     }
     return PT_OK;
 }
@@ -559,7 +552,6 @@ int pt_set_lens(float lens_radius, float focal_distance) {
     if (lens_radius > 0.0f && !(focal_distance > 0.0f)) return fail(PT_ERR_INVALID, "pt_set_lens: a lens needs focal_distance > 0");
     if (lens_radius > 0.0f && (R.flags & PT_CACHE_FIRST))
         return fail(PT_ERR_INVALID, "pt_set_lens: PT_CACHE_FIRST cannot be combined with a lens");
-    if (R.lens.radius != lens_radius || R.lens.focal != focal_distance) drop_graphs();
     R.lens.radius = lens_radius; R.lens.focal = focal_distance;
     return PT_OK;
 }
@@ -602,7 +594,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.epi_enabled && !R.use_graphs &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 
@@ -647,7 +639,7 @@ int pt_trace_mapped(int iter, float *mapped) {
 bool la_possible(void) {
     return (R.flags & PT_LOOKAHEAD) && !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST | PT_ASYNC_IMAGE)) &&
            (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) && (R.map.tile_count == 1 || R.la_tiles_ok) && R.max_batch >= 2 &&
-           R.ov_enabled && !R.use_graphs && !R.profiling && !R.dbg_counts;
+           R.ov_enabled && !R.profiling && !R.dbg_counts;
 }
 
 // will la_trace serve this context's calls (the lanes allocated and enough of them)?  The multi-device layer asks once
@@ -834,7 +826,7 @@ int pt_trace(uint8_t *pbo_rgba, int frame, int iter, float *host_image_sum) {
     const bool async_image = host_image_sum && (R.flags & PT_ASYNC_IMAGE);
     // (a tile of a larger frame writes only its own pixels: into a frame its ranks share, PT_SHARED_IMAGE)
     const bool shared_frame = host_image_sum && (R.flags & PT_SHARED_IMAGE) && R.map.tile_count > 1;
-    if (host_image_sum && (!async_image || R.async_direct_enabled) && R.epi_enabled && !R.use_graphs && (R.map.tile_count == 1 || shared_frame))
+    if (host_image_sum && (!async_image || R.async_direct_enabled) && R.epi_enabled && (R.map.tile_count == 1 || shared_frame))
         R.epi_host = map_host(host_image_sum, (size_t)R.npix * 12);
     if (shared_frame && !R.epi_host)
         return fail(PT_ERR_INVALID, "pt_trace: PT_SHARED_IMAGE needs a host frame of 1 MiB or more that can be page-locked and mapped");

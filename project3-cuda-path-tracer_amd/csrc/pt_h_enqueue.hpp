@@ -16,10 +16,10 @@ BounceArgs bounce_args(int depth) {
     a.dir_in = tile_dir((R.flags & PT_COMPACT) ? R.cur_dir : -1);
     a.dir_out = tile_dir(depth);
     a.fin = R.final_mem;
-    a.fin_stamp = R.capturing ? 0u : R.fin_serial;
+    a.fin_stamp = R.fin_serial;
     a.cam = R.cam;
     a.lens = R.lens;
-    a.depth = depth; a.trace_depth = R.trace_depth; a.iter0 = R.capturing ? -1 : R.step_iter0;
+    a.depth = depth; a.trace_depth = R.trace_depth; a.iter0 = R.step_iter0;
     a.pool_n = (uint32_t)R.map.tile_pixels * (uint32_t)R.step_count;
     a.gen_rays = (depth == 0 && R.gen_fused) ? 1 : 0;
     a.mesh_hit = R.mesh_hit;
@@ -35,8 +35,7 @@ BounceArgs bounce_args(int depth) {
     return a;
 }
 
-// every batch stamps the final colours it writes with a fresh serial number (put_final / k_gather); under graph replay
-// the kernels read it from Control::keep[0]
+// every batch stamps the final colours it writes with a fresh serial number (put_final / k_gather)
 int next_fin_stamp(void) {
     if (++R.fin_serial == 0) {                                    // 2^32 batches later: forget every old stamp
         HIPCHK(hipMemsetAsync(R.final_mem, 0, (size_t)R.cap * 16, R.stream));
@@ -60,11 +59,12 @@ int enqueue_begin(int iter0, int count, bool stepping, bool clear = true) {
     R.step_iter0 = iter0; R.step_count = count; R.step_depth = 0; R.cur = 0; R.cur_dir = -1;
     R.ov_active = false;          // (every overlapped batch's gather is on the launch stream: what follows is ordered after them)
     R.last_ctl = R.ctl;
-    if (!R.capturing) { const int rc = next_fin_stamp(); if (rc) return rc; }
+    const int rc = next_fin_stamp();
+    if (rc) return rc;
     R.sorted_isects = false;
     R.mesh_marked = false;
     R.self_gathered = false; R.host_stats_serial = 0;
-    if (clear) HIPCHK(hipMemsetAsync(&R.ctl->stamp, 0, R.ctl_bytes, R.stream));      // everything but Control::iter0
+    if (clear) HIPCHK(hipMemsetAsync(&R.ctl->stamp, 0, R.ctl_bytes, R.stream));      // everything but Control::keep
     if (R.mesh_mode == MESH_BVH)
         for (int k = 0; k < 2; ++k)
             HIPCHK(hipMemsetAsync(R.mesh_flags[k], 0, R.flag_words * sizeof(unsigned long long), R.stream));
@@ -77,7 +77,7 @@ int enqueue_begin(int iter0, int count, bool stepping, bool clear = true) {
     const uint32_t total = (uint32_t)R.map.tile_pixels * (uint32_t)count;
     StageTimer tm(PT_STAGE_RAYGEN);
     hipLaunchKernelGGL(k_raygen, dim3((total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, R.pool[0], R.cam,
-                       R.lens, R.map, count, R.capturing ? -1 : iter0, R.trace_depth, R.ctl);
+                       R.lens, R.map, count, iter0, R.trace_depth, R.ctl);
     HIPCHK(hipGetLastError());
     return PT_OK;
 }
@@ -108,7 +108,7 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
     RayGen gen{};
     if (generate) {
         gen.cam = R.cam; gen.lens = R.lens; gen.map = R.map; gen.trace_depth = R.trace_depth;
-        gen.iter0 = R.capturing ? -1 : R.step_iter0;
+        gen.iter0 = R.step_iter0;
         PT_MESH_DISPATCH(hipLaunchKernelGGL((k_intersect<MESH, SLDS, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, in,
                                             R.isect, R.scene, n_ptr, n_fixed, dir, nprev, R.ctl, cull0, R.cull0_tiles, gen));
         return;
@@ -258,7 +258,7 @@ int enqueue_fake(void) {
     launch_intersect(R.pool[R.cur], nullptr, total, tile_dir(-1), nullptr);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_shade_fake, dim3((total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, R.pool[R.cur],
-                       R.isect, R.scene.mats, R.map, R.step_iter0, total, R.final_mem, R.fin_serial, R.ctl);
+                       R.isect, R.scene.mats, R.map, R.step_iter0, total, R.final_mem, R.fin_serial);
     HIPCHK(hipGetLastError());
     R.step_depth = 1;
     return PT_OK;
@@ -289,7 +289,7 @@ int enqueue_end(void) {
                        R.final_mem, R.cap, R.map,
                        R.step_count, R.ctl, R.persist, (R.flags & PT_FAKE_SHADER) ? 0 : R.trace_depth,
                        (R.flags & PT_FAKE_SHADER) ? (uint32_t)R.map.tile_pixels * (uint32_t)R.step_count : 0u,
-                       R.whole ? 1 : 0, R.epi_done ? 1 : 0, R.capturing ? 0u : R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
+                       R.whole ? 1 : 0, R.epi_done ? 1 : 0, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
                        (R.whole && R.host_stats_serial) ? R.d_stats : (HostStats *)nullptr);
     R.whole = false;
     R.image_epoch++;
@@ -448,7 +448,7 @@ bool ensure_la_masks(void) {
 // the fused pipelines only: the unfused / two-kernel-sort / fake-shader ones keep intersection planes and sort tables
 // (one set), the first-bounce cache is filled by the first batch that needs it
 bool overlap_eligible(int count) {
-    return R.ov_ok && R.ov_enabled && !R.capturing && !R.use_graphs && !R.profiling && !R.epi_host && !R.dbg_counts &&
+    return R.ov_ok && R.ov_enabled && !R.profiling && !R.epi_host && !R.dbg_counts &&
            !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) &&
            count >= 1 && count <= R.max_batch;
 }
@@ -492,7 +492,8 @@ int enqueue_on_lane(Renderer::Lane &l, int iter0, int count) {
     return rc;
 }
 
-int enqueue_batch_direct(int iter0, int count) {
+// one batch: on a lane when it may overlap the batches around it (overlap_eligible), otherwise on the launch stream
+int enqueue_batch(int iter0, int count) {
     if (!overlap_eligible(count)) return enqueue_batch_serial(iter0, count);
     int rc = ensure_lanes();
     if (rc) return rc;
@@ -561,7 +562,7 @@ int enqueue_batch_serial(int iter0, int count) {
         // workgroup that traces a pixel's path also does finalGather for it -- image[pixel] += colour inside the launch
         // (a second launch's waves adding to the same pixels at the same time would lose updates, and the order of the
         // float additions is part of the result) -- and, with a page-locked host image, writes the new sums there.
-        if (count == 1 && !R.lane_cur && !R.capturing && !R.use_graphs && R.epi_enabled) {
+        if (count == 1 && !R.lane_cur && R.epi_enabled) {
             a.epi_image = R.image; a.epi_host = R.epi_host;
             // path by path (BounceArgs::epi_direct) when nothing but this library has written the accumulation buffer since
             // the host's copy was complete -- otherwise every pixel is written once more by the launch's epilogue.  A
@@ -574,7 +575,7 @@ int enqueue_batch_serial(int iter0, int count) {
         }
         // a synchronous call's statistics go straight to page-locked host memory: written by whoever folds the counts, this
         // launch's last workgroup (own finalGather) or k_gather's first
-        if (R.want_host_stats && !R.capturing && !R.use_graphs && R.d_stats) { a.host_stats = R.d_stats; R.host_stats_serial = R.fin_serial; }
+        if (R.want_host_stats && R.d_stats) { a.host_stats = R.d_stats; R.host_stats_serial = R.fin_serial; }
         R.grid_iter_cur = iter_grid_for((uint64_t)R.map.tile_pixels * (uint64_t)count, R.lane_cur != nullptr);
         if (R.scene_lds) hipLaunchKernelGGL(k_iteration<true>, dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
         else hipLaunchKernelGGL(k_iteration<false>, dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
@@ -588,60 +589,6 @@ int enqueue_batch_serial(int iter0, int count) {
         }
     }
     return enqueue_end();
-}
-
-void drop_graphs(void) {
-    for (auto &g : R.graphs) (void)hipGraphExecDestroy(g.second.exec);
-    R.graphs.clear();
-}
-
-// A batch is the same sequence of launches every time (per-batch clear, ray generation, one kernel
-// per bounce, gather) and differs only in its first iteration number, so it can be captured once per
-// batch size and replayed with a single hipGraphLaunch; the iteration number travels through
-// Control::iter0, written on the stream ahead of the graph.  Anything that changes a frozen launch
-// argument (camera, lens, trace depth) drops the captured graphs.  Opt-in (PTMI355_GRAPH=1): on
-// ROCm 7.2 / MI355X replay measured 4.5 % SLOWER than the ten direct launches at 1 spp per call
-// (0.240 vs 0.230 ms) and 0.5 % slower at 16 spp, so direct launches stay the default.
-int enqueue_batch(int iter0, int count) {
-    const bool graphable = R.use_graphs && !R.profiling && !(R.flags & PT_FAKE_SHADER) &&
-                           !((R.flags & PT_CACHE_FIRST) && !R.cache_valid);
-    if (!graphable) return enqueue_batch_direct(iter0, count);
-    if (count < 1 || count > R.max_batch)
-        return fail(PT_ERR_INVALID, "batch count %d outside [1, max_batch=%d]", count, R.max_batch);
-    // makeSeededRandomEngine ORs the iteration into a word that holds the depth from bit 22 up (pathtrace.cu:41-45);
-    // past 2^22 iterations the streams of different depths collide in the reference too -- reproduced, not refused
-    if (iter0 < 0 || (int64_t)iter0 + count - 1 > 0x7fffffff)
-        return fail(PT_ERR_INVALID, "iteration %d (+%d) outside [0, 2^31)", iter0, count);
-    auto it = R.graphs.find(count);
-    if (it == R.graphs.end()) {
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(R.stream, hipStreamCaptureModeRelaxed));
-        R.capturing = true;
-        const int rc = enqueue_batch_direct(iter0, count);
-        R.capturing = false;
-        const hipError_t ce = hipStreamEndCapture(R.stream, &graph);
-        if (rc != PT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess || !graph) return fail(PT_ERR_DEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-        Renderer::BatchGraph g{};
-        const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail(PT_ERR_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-        g.cur = R.cur; g.cur_dir = R.cur_dir; g.step_depth = R.step_depth;
-        g.sorted_isects = R.sorted_isects; g.gen_fused = R.gen_fused;
-        it = R.graphs.emplace(count, g).first;
-    }
-    const Renderer::BatchGraph &g = it->second;
-    {
-        const int rc = next_fin_stamp();
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&R.ctl->iter0, iter0, 1, R.stream));
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&R.ctl->keep[0], (int)R.fin_serial, 1, R.stream));
-    HIPCHK(hipGraphLaunch(g.exec, R.stream));
-    R.step_iter0 = iter0; R.step_count = count;
-    R.cur = g.cur; R.cur_dir = g.cur_dir; R.step_depth = g.step_depth;
-    R.sorted_isects = g.sorted_isects; R.gen_fused = g.gen_fused;
-    return PT_OK;
 }
 
 }  // namespace

@@ -272,8 +272,7 @@ static int upload_bvh(const pt_scene_desc *d, std::vector<float> &grec) {
 // root tests and walks in k_mesh.  No mask (nullptr) when a corner is not in front of the camera, the frame does
 // not tile by 64 pixels, or a thin lens is on (then rays do not start at the eye).
 // (re)build the bounce-0 candidate masks for the current camera and cull boxes: one launch on the stream, ordered
-// behind whatever still reads the old masks and ahead of everything enqueued later (the buffer never moves, so
-// captured graphs stay valid)
+// behind whatever still reads the old masks and ahead of everything enqueued later
 static int update_cull0() {
     if (!R.cull0_tiles) return PT_OK;
     hipLaunchKernelGGL(k_cull0_mask, dim3((R.cull0_tiles + WAVES - 1) / WAVES), dim3(BLOCK), 0, R.stream, R.scene, R.cam,

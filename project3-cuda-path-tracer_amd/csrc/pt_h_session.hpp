@@ -99,13 +99,10 @@ struct Renderer {
     bool gen_fused = false;       // bounce 0 of the current batch generates its own rays
     bool gen_sort = false;        // ... in the sorted pipeline (k_intersect + k_shade_sorted_w), no k_raygen either
     Lens lens{0, 0.0f, 0.0f};     // PT_AA_JITTER / thin lens (pt_scene_desc, pt_set_lens)
-    // one captured graph per batch size: memset + every launch of a batch replayed with one hipGraphLaunch
-    struct BatchGraph { hipGraphExec_t exec; int cur, cur_dir, step_depth; bool sorted_isects, gen_fused; };
-    std::map<int, BatchGraph> graphs;
     uint64_t whole_max_paths = 6000000;  // batches up to this many paths run as ONE launch (k_iteration); PTMI355_WHOLE_MAX
     uint64_t whole_max_host_paths = 16000000;   // ... one iteration with a page-locked host image: up to this many (PTMI355_WHOLE_MAX_HOST)
     bool whole = false;           // the current batch did
-    // Batches whose caller does not wait for them overlap on the device (enqueue_batch_direct): each runs on a LANE --
+    // Batches whose caller does not wait for them overlap on the device (enqueue_batch): each runs on a LANE --
     // a launch stream of its own and its own set of the buffers a batch in flight owns
     struct Bufs {
         float *pool_mem[2]; Pool pool[2]; float *final_mem; Control *ctl; uint32_t *dir_mem;
@@ -173,8 +170,6 @@ struct Renderer {
     uint64_t host_epoch = 0;
     bool epi_enabled = true;      // PTMI355_HOST_EPILOGUE=0: always copy after the iteration
     bool pin_enabled = true;      // PTMI355_PIN=0: never page-lock caller buffers (copies take the runtime's pageable path)
-    bool use_graphs = false;      // PTMI355_GRAPH=1 turns replay on (measured slower than direct launches on ROCm 7.2: DESIGN.md 6.10)
-    bool capturing = false;
     int mesh_mode = MESH_NONE;    // MESH_TILES: every triangle per ray; MESH_BVH: PT_MESH_BVH culling
     float *d_bvh_nodes = nullptr, *d_bvh_tris = nullptr, *d_bvh_top = nullptr;
     std::vector<float> mesh_grids;           // per mesh: lo xyz, hi xyz of its box grid (contains every box of its tree)

@@ -385,8 +385,8 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
     const uint32_t W = (SORT && COMPACT) ? a.dir_out.W : Wp;
     const uint32_t runs_per_wave = (SORT && COMPACT) ? W / Wp : 1u;
     const uint32_t wid0 = run_id();
-    c.iter0 = a.iter0 >= 0 ? a.iter0 : (int)a.ctl->iter0;       // graph replay: arguments are frozen
-    c.stamp = batch_stamp(a.fin_stamp, a.ctl);
+    c.iter0 = a.iter0;
+    c.stamp = a.fin_stamp;
     const uint32_t n = (COMPACT && !GEN) ? a.ctl->nlive[a.depth] : a.pool_n;
     const bool packed_in = COMPACT && !GEN && a.dir_in.mem != nullptr;
     // an unsorted packed pool is read in tiles aligned to its ranges (pt_types.hpp: RangeDir): `tiles` counts those
@@ -537,8 +537,8 @@ __global__ __launch_bounds__(BLOCK, PT_ITER_WAVES) void k_iteration(BounceArgs a
     c.lane = lane;
     const uint32_t W = gridDim.x * WAVES;
     const uint32_t wid = run_id();
-    c.iter0 = a.iter0 >= 0 ? a.iter0 : (int)a.ctl->iter0;
-    c.stamp = batch_stamp(a.fin_stamp, a.ctl);
+    c.iter0 = a.iter0;
+    c.stamp = a.fin_stamp;
     const uint32_t n = a.pool_n;
     const uint32_t tiles = (n + TILE - 1) / TILE;
     const uint32_t R = range_tiles(n, W);

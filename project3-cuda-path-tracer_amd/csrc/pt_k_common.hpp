@@ -49,7 +49,5 @@ __device__ __forceinline__ void put_final(float *fin, uint32_t pid, f3 c, uint32
     if (!(c.x == 0.0f && c.y == 0.0f && c.z == 0.0f))                       // NaN compares false: written
         reinterpret_cast<float4 *>(fin)[pid] = make_float4(c.x, c.y, c.z, __uint_as_float(stamp));
 }
-// the stamp of the current batch: a launch argument, or (graph replay: arguments are frozen) Control::keep[0]
-__device__ __forceinline__ uint32_t batch_stamp(uint32_t arg, const Control *ctl) { return arg ? arg : ctl->keep[0]; }
 
 }  // namespace

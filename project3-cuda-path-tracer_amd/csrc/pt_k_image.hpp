@@ -17,7 +17,6 @@ __global__ __launch_bounds__(BLOCK) void k_raygen(Pool p, pt_camera cam, Lens le
     if (i >= total) return;
     const uint32_t smp = i / (uint32_t)map.tile_pixels;
     const uint32_t j = i - smp * (uint32_t)map.tile_pixels;
-    if (iter0 < 0) iter0 = (int)ctl->iter0;                  // graph replay
     f3 o, d;
     camera_ray(cam, lens, trace_depth, iter0 + (int)smp, local_to_pixel(map, (int)j), map.W, o, d);
     const SlotPtr q = p.slot(i);
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(BLOCK) void k_raygen(Pool p, pt_camera cam, Lens le
 
 // shadeFakeMaterial (pathtrace.cu:224-266): one bounce, never spawns a ray
 __global__ __launch_bounds__(BLOCK) void k_shade_fake(Pool p, Isect is, const float *mats_g, TileMap map,
-                                                      int iter0, uint32_t n, float *fin, uint32_t stamp_arg, const Control *ctl) {
+                                                      int iter0, uint32_t n, float *fin, uint32_t stamp) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint32_t pid = p.pid(i);
@@ -56,20 +55,20 @@ __global__ __launch_bounds__(BLOCK) void k_shade_fake(Pool p, Isect is, const fl
         c = ptd::mk(0.0f, 0.0f, 0.0f);
     }
     p.f(i, 6) = c.x; p.f(i, 7) = c.y; p.f(i, 8) = c.z;
-    put_final(fin, pid, c, batch_stamp(stamp_arg, ctl));
+    put_final(fin, pid, c, stamp);
 }
 
 // finalGather (pathtrace.cu:269-278): image[pixelIndex] += colour, one add per
 // pixel per iteration, samples added in iteration order
 __global__ __launch_bounds__(BLOCK) void k_gather(float *image, const float *fin, uint32_t cap, TileMap map,
                                                   int count, Control *ctl, Persist *per, int depths,
-                                                  uint32_t fake_rays, int partial_counts, int counters_only, uint32_t stamp_arg,
+                                                  uint32_t fake_rays, int partial_counts, int counters_only, uint32_t stamp,
                                                   const uint32_t *iter_counts, uint32_t iter_grid, HostStats *host_stats) {
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
     if (partial_counts) {            // the batch ran as ONE launch (k_iteration): its per-workgroup counts are added up here
         __shared__ uint32_t fold_lds[BLOCK / 32];
         if (blockIdx.x == 0)
-            fold_iter_counts(iter_counts, iter_grid, depths, ctl, per, host_stats, (uint32_t)count, batch_stamp(stamp_arg, ctl), fold_lds);
+            fold_iter_counts(iter_counts, iter_grid, depths, ctl, per, host_stats, (uint32_t)count, stamp, fold_lds);
     } else if (j == 0) {             // fold this batch's ray count into the persistent counters (batches of different lanes may
                                      // run side by side, hence atomics)
         unsigned long long r = fake_rays;
@@ -84,7 +83,6 @@ __global__ __launch_bounds__(BLOCK) void k_gather(float *image, const float *fin
     // samples are added in iteration order (one add per pixel per iteration, as the reference does); the loads of
     // eight samples are issued together, the adds stay in order
     // an entry counts when it carries this batch's stamp; the others are paths that ended with colour 0 (put_final)
-    const uint32_t stamp = batch_stamp(stamp_arg, ctl);
     const float4 *f4 = reinterpret_cast<const float4 *>(fin) + j;
     int s = 0;
     for (; s + 8 <= count; s += 8) {

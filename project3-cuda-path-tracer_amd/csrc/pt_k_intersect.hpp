@@ -202,8 +202,7 @@ __global__ __launch_bounds__(BLOCK, PT_ISECT_WAVES) void k_intersect(Pool in, Is
         if (GEN && active) {
             const uint32_t smp = sample_of(gen.map, i);
             const int pixel = local_to_pixel(gen.map, (int)(i - smp * (uint32_t)gen.map.tile_pixels));
-            const int it0 = gen.iter0 >= 0 ? gen.iter0 : (int)ctl->iter0;
-            camera_ray(gen.cam, gen.lens, gen.trace_depth, it0 + (int)smp, pixel, gen.map.W, ro, rd);
+            camera_ray(gen.cam, gen.lens, gen.trace_depth, gen.iter0 + (int)smp, pixel, gen.map.W, ro, rd);
         } else if (!GEN && active) {
             const SlotPtr p = in.slot(src);
             if (ppid(p) == DEAD_PID) active = false;

@@ -355,7 +355,7 @@ __global__ __launch_bounds__(MESH_BLOCK, PT_MESH_WAVES) void k_mesh(BounceArgs a
     uint32_t *mi = reinterpret_cast<uint32_t *>(mq);
     const int lane = threadIdx.x & 63;
     const uint32_t wid = run_id();
-    const int iter0 = a.iter0 >= 0 ? a.iter0 : (int)a.ctl->iter0;
+    const int iter0 = a.iter0;
     // bounce 0 of a batch: nlive[0] is written by that bounce's own kernel, so the count comes from the host
     const uint32_t n = (COMPACT && !a.gen_rays) ? a.ctl->nlive[a.depth] : a.pool_n;
     const uint32_t tiles = (n + TILE - 1) / TILE;

@@ -207,8 +207,8 @@ __global__ __launch_bounds__(BLOCK) void k_shade_sorted(BounceArgs a) {
     float *mats = reinterpret_cast<float *>(keyl + SORT_CHUNK);       // materials (when they fit: a.nbins <= 64)
     const bool mats_lds = a.nbins <= 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int iter0 = a.iter0 >= 0 ? a.iter0 : (int)a.ctl->iter0;
-    const uint32_t stamp = batch_stamp(a.fin_stamp, a.ctl);
+    const int iter0 = a.iter0;
+    const uint32_t stamp = a.fin_stamp;
     const uint32_t n = (COMPACT && a.depth > 0) ? a.ctl->nlive[a.depth] : a.pool_n;
     const bool last_bounce = a.depth == a.trace_depth - 1;
     uint32_t first, count;
@@ -367,8 +367,8 @@ __global__ __launch_bounds__(BLOCK, GEN ? 6 : 8) void k_shade_sorted_w(BounceArg
     uint32_t *xch = sctl + LDS_CTL_WORDS;                    // [2][WAVES][64]: per-key counts of each wave, by chunk parity
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float *mats = reinterpret_cast<float *>(xch + 2 * WAVES * 64);
-    const int iter0 = a.iter0 >= 0 ? a.iter0 : (int)a.ctl->iter0;
-    const uint32_t stamp = batch_stamp(a.fin_stamp, a.ctl);
+    const int iter0 = a.iter0;
+    const uint32_t stamp = a.fin_stamp;
     const uint32_t n = (COMPACT && a.depth > 0) ? a.ctl->nlive[a.depth] : a.pool_n;
     const bool last_bounce = a.depth == a.trace_depth - 1;
     uint32_t first, count;

@@ -371,7 +371,7 @@ int multi_refresh(void) {
 
 // the launches of one call on every device, the packing of the tiles, then the exchange
 // `overlap`: the caller does not wait for this call (pt_trace_batch_async): consecutive batches may overlap on each
-// device's lanes (pt_h_enqueue.hpp: enqueue_batch_direct); their gathers stay on the launch stream, which the packing waits on
+// device's lanes (pt_h_enqueue.hpp: enqueue_batch); their gathers stay on the launch stream, which the packing waits on
 // the exchange thread has enqueued everything it was given (an error of its own is the caller's now)
 int exchange_settled(void) {
     if (!G.x) return PT_OK;

@@ -1,5 +1,5 @@
-"""GPU parity, launch plans that overlap or replay: consecutive asynchronous batches on the lanes (csrc/ptmi355.hip:
-enqueue_batch_direct), the final-colour stamps they rely on, hipGraph replay -- each equal to the serial plan and to the oracle."""
+"""GPU parity, launch plans that overlap: consecutive asynchronous batches on the lanes (csrc/pt_h_enqueue.hpp:
+enqueue_batch) and the final-colour stamps they rely on -- each equal to the serial plan and to the oracle."""
 import hashlib
 import os
 import sys
@@ -49,7 +49,7 @@ def test_c2_one_iteration_per_call_overlapped(pt, scenes, monkeypatch):
 
 def test_overlapped_small_batches(pt, po, scenes, monkeypatch):
     """Consecutive small batches whose caller does not wait (pt_trace_batch_async, PT_ASYNC_IMAGE) overlap on lanes
-    that share two launch streams (csrc/pt_h_enqueue.hpp: enqueue_batch_direct).  The image after every call, the ray counters and the
+    that share two launch streams (csrc/pt_h_enqueue.hpp: enqueue_batch).  The image after every call, the ray counters and the
     per-bounce statistics equal the serial plan's and the oracle's: batch sizes mixed with larger (serial) batches,
     the camera moved and the trace depth changed in between, synchronous calls in between, a second session."""
     s = scenes["cornell_64"]
@@ -183,18 +183,13 @@ def test_overlapped_async_image(pt, scenes, monkeypatch):
     pt.pathtraceFree()
 
 
-@pytest.mark.parametrize("graph", [False, True])
-def test_final_colour_stamps(pt, po, scenes, monkeypatch, graph):
-    """(Run with direct launches and under hipGraph replay, PTMI355_GRAPH=1: the stamp then travels through
-    Control::keep[0] because kernel arguments are frozen at capture.)
-    Paths that end with colour 0 write nothing; k_gather tells this batch's entries from stale ones by the batch's
+def test_final_colour_stamps(pt, po, scenes, monkeypatch):
+    """Paths that end with colour 0 write nothing; k_gather tells this batch's entries from stale ones by the batch's
     stamp (a per-session serial number in the entry's fourth component).  The same iteration traced again after
     clear_image, batches of different sizes over the same entries, and the serial's wrap-around at 2^32 (the buffer
     is cleared and the serial restarts) all give the oracle's sums."""
     s = scenes["cornell_64"]
     n = 64 * 64
-    if graph:
-        monkeypatch.setenv("PTMI355_GRAPH", "1")
     for start in (None, "0xfffffffd") if pt.has_experiments() else (None,):    # the second run wraps after three batches (test hook of a -DPT_EXPERIMENTS build)
         if start:
             monkeypatch.setenv("PTMI355_FIN_SERIAL", start)
@@ -215,36 +210,3 @@ def test_final_colour_stamps(pt, po, scenes, monkeypatch, graph):
         assert img.tobytes() == ref.image.tobytes()
         pt.pathtraceFree()
     monkeypatch.delenv("PTMI355_FIN_SERIAL", raising=False)
-
-
-@pytest.mark.parametrize("sort", [False, True])
-def test_graph_replay_equals_direct_launches(pt, scenes, monkeypatch, sort):
-    """PTMI355_GRAPH=1: a batch captured once and replayed with hipGraphLaunch (iteration number through
-    Control::iter0) gives the same image as direct launches, across batch sizes and a camera change -- fused, and with
-    the material sort (whose bounce-0 kernels generate the camera rays themselves)."""
-    s = scenes["cornell_glass_64"]
-    scene = pt.Scene(s["geoms"], s["materials"], s["camera"], s["depth"])
-    n = scene.resolution[0] * scene.resolution[1]
-
-    def run():
-        img = np.zeros((n, 3), dtype=np.float32)
-        pt.pathtraceInit(scene, flags=pt.PT_COMPACT | (pt.PT_SORT_MATERIAL if sort else 0), max_batch=4)
-        for it in (1, 2, 3):
-            pt.pathtrace(None, 0, it)                 # batch size 1, three replays
-        pt.trace_batch(4, 4, img)                     # batch size 4
-        pt.trace_batch(8, 4, img)
-        pt.trace_batch(12, 3, img)                    # a third size
-        rays = pt.get_stats().total_rays
-        cam = scene.camera.copy()
-        cam["position"][0][0] += 0.5                  # frozen launch arguments change: graphs are re-captured
-        pt.set_camera(cam, s["depth"])
-        pt.trace_batch(15, 4, img)
-        pt.pathtraceFree()
-        return img, rays
-
-    monkeypatch.delenv("PTMI355_GRAPH", raising=False)
-    direct = run()
-    monkeypatch.setenv("PTMI355_GRAPH", "1")
-    replay = run()
-    assert direct[1] == replay[1]
-    assert direct[0].tobytes() == replay[0].tobytes()
