@@ -386,6 +386,11 @@ int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]);
  * the pair is a candidate when the sign bit is set.  Returns the record count; count == 0 launches nothing. */
 int pt_probe_tri_form(const pt_triangle *triangles, int count, float origin_bound, const float *origins, const float *directions, int n,
                       uint16_t *ray_slots, int32_t *ray_class, float *form);
+/* pt_probe_own_surface_plan: the launch plan's decision (host only, no device) whether a batch of `paths` paths of a scene
+ * of `ngeoms` primitives takes the own-surface form of the fused bounce kernel's cull -- the primitive a path has just left
+ * travels in bits 26..29 of its pid as geom + 1 -- given that the pipeline is the plain fused compacting one (plain_fused:
+ * PT_COMPACT without PT_UNFUSED, PT_SORT_MATERIAL, PT_CACHE_FIRST or triangle meshes).  1: yes, 0: no. */
+int pt_probe_own_surface_plan(uint64_t paths, int ngeoms, int plain_fused);
 /* devices of the current session (0: not initialised) and how their tiles reach devices[0]: "rccl", "peer"
  * (hipMemcpyPeerAsync) or "none" (one device) */
 int pt_num_devices(void);

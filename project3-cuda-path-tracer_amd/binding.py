@@ -155,6 +155,7 @@ def library():
             L.pt_probe_sqrt.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
             L.pt_probe_clock.argtypes = [C.c_int, C.POINTER(C.c_double)]
             L.pt_probe_tri_form.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_probe_own_surface_plan.argtypes = [C.c_uint64, C.c_int, C.c_int]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -472,6 +473,12 @@ def probe_tri_form(triangles, origin_bound, origins, directions):
     got = _chk(library().pt_probe_tri_form(_p(t), len(t), float(origin_bound), _p(o), _p(d), n, _p(slots), _p(cls), _p(form)))
     assert got == n64, (got, n64)
     return slots, cls, form
+
+
+def probe_own_surface_plan(paths, ngeoms, plain_fused=True):
+    """The launch plan's decision (host only): does a batch of `paths` paths of a scene of `ngeoms` primitives take the
+    own-surface form of the fused bounce kernel's cull (the primitive left travels in the pid)?"""
+    return bool(library().pt_probe_own_surface_plan(int(paths), int(ngeoms), 1 if plain_fused else 0))
 
 
 def probe_hemisphere(normals, seeds):

@@ -153,6 +153,8 @@ static int init_impl(const pt_scene_desc *d) {
     if (const char *e = pt_experiment("PTMI355_EPI_DIRECT")) R.epi_direct_enabled = atoi(e) != 0;
     R.defer_enabled = true;
     if (const char *e = pt_experiment("PTMI355_DEFER_DIR")) R.defer_enabled = atoi(e) != 0;
+    R.own_enabled = true;
+    if (const char *e = pt_experiment("PTMI355_OWN_SURFACE")) R.own_enabled = atoi(e) != 0;
     R.host_sparse_enabled = (d->flags & (PT_HOST_SPARSE | PT_SHARED_IMAGE)) != 0;
     if (const char *e = pt_experiment("PTMI355_ASYNC_DIRECT")) R.async_direct_enabled = atoi(e) != 0;
     R.pin_enabled = true;
@@ -271,6 +273,11 @@ static int init_impl(const pt_scene_desc *d) {
             for (int m = 0; m < (g.type == PT_CUBE ? 2 : 3); ++m)     // a cube's words GREC_FACE..: k_face_normals below
                 for (int c = 0; c < 4; ++c)
                     for (int rr = 0; rr < 3; ++rr) r[m * 12 + c * 3 + rr] = ms[m]->m[c][rr];
+            // words GREC_ROW..: the reject row, as upload_cull puts it into the cull record (zeros: none)
+            if (g.type == PT_CUBE && !pt_experiment("PTMI355_NO_AXIS_REJECT")) {
+                const int ax = ptcull::reject_row(&g.inverseTransform.m[0][0], r + GREC_ROW);
+                if (ax == 4 && pt_experiment("PTMI355_NO_ROW_REJECT")) r[GREC_ROW] = r[GREC_ROW + 1] = r[GREC_ROW + 2] = r[GREC_ROW + 3] = 0.0f;
+            }
             ginfo[(size_t)i] = (uint32_t)g.materialid | ((uint32_t)g.type << 28);
         }
         if (d->num_materials >= (1 << 28)) return fail(PT_ERR_INVALID, "pt_init: at most 2^28 materials");
@@ -393,7 +400,10 @@ static int init_impl(const pt_scene_desc *d) {
         if (R.mesh_mode == MESH_BVH) { fns[0] = bounce_fn<MESH_PRE>(R.scene_lds, false, false); fns[1] = bounce_fn<MESH_PRE>(R.scene_lds, true, false); }
         else if (R.mesh_mode == MESH_TILES) { fns[0] = bounce_fn<MESH_TILES>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_TILES>(R.scene_lds, true, sorted); }
         else { fns[0] = bounce_fn<MESH_NONE>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE>(R.scene_lds, true, sorted); }
-        for (const void *f : fns) {
+        // (a session may launch the own-surface form of the plain kernel, batch by batch: enqueue_bounce)
+        const bool own = R.mesh_mode == MESH_NONE && !sorted;
+        const void *fns_own[2] = {own ? bounce_fn<MESH_NONE>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE>(R.scene_lds, true, false, true) : fns[1]};
+        for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1]}) {
             int n = 0;
             HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
             per_cu = std::min(per_cu, n);
@@ -925,7 +935,7 @@ int pt_export_paths(pt_path_segment *host_paths, int capacity, int *n_live) {
         }
         hipLaunchKernelGGL(k_export_paths, dim3((n + 255) / 256), dim3(256), 0, R.stream, R.pool[R.cur], R.map, n,
                            live, R.trace_depth - R.step_depth, (pt_path_segment *)R.scratch,
-                           tile_dir(packed ? R.cur_dir : -1), span, R.step_iter0, R.step_depth - 1);
+                           tile_dir(packed ? R.cur_dir : -1), span, R.step_iter0, R.step_depth - 1, R.pool_own ? OWN_MASK : 0u);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(host_paths, R.scratch, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost, R.stream));
         HIPCHK(hipStreamSynchronize(R.stream));

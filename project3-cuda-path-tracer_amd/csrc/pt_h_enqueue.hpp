@@ -57,6 +57,7 @@ int enqueue_begin(int iter0, int count, bool stepping, bool clear = true) {
     if (iter0 < 0 || (int64_t)iter0 + count - 1 > 0x7fffffff)
         return fail(PT_ERR_INVALID, "iteration %d (+%d) outside [0, 2^31)", iter0, count);
     R.step_iter0 = iter0; R.step_count = count; R.step_depth = 0; R.cur = 0; R.cur_dir = -1;
+    R.pool_own = false;
     R.ov_active = false;          // (every overlapped batch's gather is on the launch stream: what follows is ordered after them)
     R.last_ctl = R.ctl;
     const int rc = next_fin_stamp();
@@ -122,7 +123,13 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // (the hierarchy is never walked inline by k_bounce) and generates bounce 0's rays itself in batches (GEN).
 // the fused compacting kernel that launch_bounce_at picks for (scene in LDS, ray generation, material keys)
 template <int MESH>
-const void *bounce_fn(bool slds, bool gen, bool sorted) {
+const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false) {
+    if constexpr (MESH == MESH_NONE) {
+        if (own && !sorted) {
+            if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, false, true>;
+            return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, false, true>;
+        }
+    }
     if constexpr (MESH != MESH_PRE) {
         if (sorted) {
             if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, true>;
@@ -138,6 +145,13 @@ void launch_bounce_at(const BounceArgs &a) {
         if (R.sort_keys > 0) {                                // PT_SORT_MATERIAL, fused: survivors placed by material
             if (R.scene_lds) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, true, GEN, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
             else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, false, GEN, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+            return;
+        }
+    }
+    if constexpr (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE) {
+        if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce)
+            if (R.scene_lds) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+            else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
             return;
         }
     }
@@ -160,6 +174,7 @@ void launch_bounce(const BounceArgs &a) {
 
 int enqueue_bounce(int depth) {
     BounceArgs a = bounce_args(depth);
+    R.own_form = false;
     const bool compact = (R.flags & PT_COMPACT) != 0;
     const bool sort2 = (R.flags & PT_SORT_MATERIAL) && R.sort_keys == 0;      // the two-kernel form of the sort
     const bool unfused = (R.flags & PT_UNFUSED) != 0 || sort2;
@@ -216,6 +231,16 @@ int enqueue_bounce(int depth) {
     // k_intersect, the sort kernels, k_iteration's own pools) gets the eager form.
     a.defer_dir = (compact && !unfused && R.mesh_mode == MESH_NONE && R.sort_keys == 0 && depth + 1 < R.trace_depth &&
                    R.defer_enabled) ? 1 : 0;
+    // The own-surface form of the cull (pt_types.hpp: OWN_MASK): survivors carry the primitive they leave in their pid and
+    // the next bounce tests that primitive's row once per ray.  Writer and reader must both be the plain fused compacting
+    // k_bounce -- no mesh pre-pass, no material keys, no first-bounce cache (it keeps no primitive number) -- the batch's pids
+    // must leave the bits free and the primitives must fit the code.  All of that is fixed for the batch, so every bounce of
+    // it takes the same form: a bounce of this form reads what one of this form (or k_raygen: plain pids below 2^26) wrote.
+    // The last bounce writes no survivors, so "a next bounce exists" needs no case of its own.  Every other reader of a
+    // pool only ever sees plain pids.
+    R.own_form = own_surface_plan((uint64_t)a.pool_n, R.scene.ngeoms,
+                                  compact && !unfused && R.mesh_mode == MESH_NONE && R.sort_keys == 0 &&
+                                  !(R.flags & PT_CACHE_FIRST) && R.own_enabled);
     if (cached0 && !R.cache_valid) {
         StageTimer tm(PT_STAGE_INTERSECT);
         const Isect cache{R.cache_mem, (uint32_t)R.map.tile_pixels};
@@ -248,6 +273,7 @@ int enqueue_bounce(int depth) {
         R.mesh_marked = !cached0 && !unfused;
     }
     if (compact) { R.cur ^= 1; R.cur_dir = depth; }
+    R.pool_own = R.own_form;
     R.step_depth = depth + 1;
     return PT_OK;
 }

@@ -164,6 +164,9 @@ struct Renderer {
     bool epi_done = false;        // ... and k_iteration took it
     bool epi_direct_enabled = true;   // PTMI355_EPI_DIRECT=0: such launches keep the final-colour buffer and gather per wave at their end
     bool defer_enabled = true;    // PTMI355_DEFER_DIR=0: every scatter stores its direction (no PENDING_DIR slots; the A/B control)
+    bool own_enabled = true;      // PTMI355_OWN_SURFACE=0: every bounce culls with the per-primitive row test (no OWN_MASK bits; the A/B control)
+    bool own_form = false;        // the launch being enqueued is k_bounce's own-surface form (enqueue_bounce decides, launch_bounce_at reads)
+    bool pool_own = false;        // pool[cur]'s pids carry OWN_MASK bits (pt_export_paths strips them)
     bool host_sparse_enabled = false; // PT_HOST_SPARSE (implied by PT_SHARED_IMAGE): only the pixels whose sum changed are written to a host image the launch wrote last
     uint64_t image_epoch = 0;     // bumped by everything that changes the accumulation buffer
     float *host_synced = nullptr; // the (device-mapped) host image that held exactly the buffer's content at epoch host_epoch

@@ -70,10 +70,12 @@ struct TileRegs {
 // pid, the hit normal in the direction row): they draw it here, with the same engine (that bounce's depth) and the same
 // sampler, so the ray is the one the writer would have stored.  The tile is compacted, so this runs ~60 lanes wide where
 // the writer's scatter ran ~46 (misses and light hits end in the same tiles as the survivors).
-template <bool GEN, bool RESOLVE = false>
+// OWN: the pid's bits OWN_MASK hold the primitive the path left (pt_types.hpp), handed out as `own` (geom + 1, 0: none).
+template <bool GEN, bool RESOLVE = false, bool OWN = false>
 __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c, const Pool &in, int depth,
                                           uint32_t tile, uint32_t i, uint32_t src, bool have, bool active,
-                                          TileRegs &tr, f3 &ro, f3 &rd) {
+                                          TileRegs &tr, f3 &ro, f3 &rd, uint32_t &own) {
+    own = 0u;
     constexpr bool gen_rays = GEN;
     tr.have = have; tr.i = i; tr.src = src; tr.tile = tile;
     tr.pid = DEAD_PID; tr.smp = 0; tr.pixel = 0;
@@ -95,6 +97,7 @@ __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c,
     }
     bool pending = false;
     if (RESOLVE && active) { pending = (tr.pid & PENDING_DIR) != 0u; tr.pid &= ~PENDING_DIR; }
+    if (OWN && !GEN && active) { own = (tr.pid & OWN_MASK) >> OWN_SHIFT; tr.pid &= ~OWN_MASK; }
     if (active) {
         if (c.kmisc) {
             const TileMap map = karg_struct<TileMap>(offsetof(BounceArgs, map));
@@ -144,11 +147,12 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 // SORT (PT_SORT_MATERIAL, fused form): the survivors of key (= material hit) k go to the wave's span of range
 // k * W + w -- `key_stride` slots further per key -- and `packed` is per LANE: lane k counts the wave's key-k survivors.
 // DEFER: BounceArgs::defer_dir is honoured (the launch plan sets it only where the next bounce resolves)
+// `own_bits`: what a survivor's pid carries to the next bounce besides PENDING_DIR (the primitive it leaves, OWN kernels)
 template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = false>
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
                                            uint32_t n, uint32_t dst_base, uint32_t &packed, uint32_t &traced,
-                                           uint32_t key_stride = 0) {
+                                           uint32_t key_stride = 0, uint32_t own_bits = 0) {
     const int lane = c.lane;
     bool alive = false, deferred = false;
     ptd::PathState ps;
@@ -196,7 +200,7 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
         pf(p, 0) = ps.o.x; pf(p, 1) = ps.o.y; pf(p, 2) = ps.o.z;
         pf(p, 3) = ps.d.x; pf(p, 4) = ps.d.y; pf(p, 5) = ps.d.z;
         pf(p, 6) = ps.c.x; pf(p, 7) = ps.c.y; pf(p, 8) = ps.c.z;
-        ppid(p) = deferred ? (tr.pid | PENDING_DIR) : tr.pid;
+        ppid(p) = (deferred ? (tr.pid | PENDING_DIR) : tr.pid) | own_bits;
         // mesh pre-pass of the NEXT bounce: flag the slot when the new ray can reach a mesh at all (~11 % of them on
         // C4), so that k_mesh neither scans nor loads the other 89 %
         if (MESH == MESH_PRE) {
@@ -215,7 +219,7 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
 
 // the tile with parity `par` has been fully tested: read its rays back from the wave's LDS block, fold the
 // winner and shade
-template <bool COMPACT, int MESH, bool SORT = false, bool DEFER = false>
+template <bool COMPACT, int MESH, bool SORT = false, bool DEFER = false, bool OWN = false>
 __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &c, const WaveQ &q, int par, const Pool &in,
                                             const Pool &out, int depth, const TileRegs &tr, uint32_t n, uint32_t dst_base,
                                             uint32_t &packed, uint32_t &traced, uint32_t key_stride = 0) {
@@ -223,8 +227,11 @@ __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &
     const f3 ro = ptd::mk(ry[0], ry[64], ry[128]);
     const f3 rd = ptd::mk(ry[192], ry[256], ry[320]);
     float t = -1.0f; f3 nrm = ptd::mk(0, 0, 0); int mat = 0, outside = 1;
-    if (tr.active) tile_result(q, par, c.acc, a.scene.tris, tr.mb, t, nrm, mat, outside);
-    tile_shade<COMPACT, MESH, SORT, DEFER>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride);
+    int geom = -1;
+    if (tr.active) tile_result(q, par, c.acc, a.scene.tris, tr.mb, t, nrm, mat, outside, geom);
+    // OWN: the launch plan admits scenes of up to OWN_MAX_GEOMS primitives, so geom + 1 fits the pid's four bits
+    tile_shade<COMPACT, MESH, SORT, DEFER>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
+                                           OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u);
 }
 
 // The tiles [first, first + count) of one wave's run at one bounce, two in flight (see the intersection stages
@@ -244,7 +251,8 @@ struct WgSpans {
 // side never does in bounce 0's)
 // DEFER / RESOLVE: this kernel may leave diffuse directions pending in its output (tile_shade) / draws the pending ones
 // of its input (tile_load)
-template <int MODE, bool COMPACT, int MESH, bool GEN, bool SORT = false, bool DEFER = false, bool RESOLVE = false>
+// OWN: the own-surface form of the cull (cull_scene); the pids of its input and of its output carry the primitive left
+template <int MODE, bool COMPACT, int MESH, bool GEN, bool SORT = false, bool DEFER = false, bool RESOLVE = false, bool OWN = false>
 __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c, WaveQ &q, const Pool &in, const Pool &out,
                                           int depth, uint32_t first_tile, uint32_t count, uint32_t tiles,
                                           uint32_t n, bool packed_in, uint32_t span_in, uint32_t &cur, uint32_t dst_base,
@@ -299,7 +307,8 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
         }
         TileRegs tr;
         f3 ro, rd;
-        tile_load<GEN, RESOLVE>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd);
+        uint32_t own;
+        tile_load<GEN, RESOLVE, OWN>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd, own);
         if (MODE == MODE_FUSED) {
             const float4 *pre_hit = nullptr;
             if (MESH == MESH_PRE && tr.active) {
@@ -313,11 +322,13 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
                 // hipMemsetAsync per bounce (eight extra launches per batch: profiles/r05/rocprof_r05_c4_bvh_summary.txt).
                 if (word != 0ull && (uint32_t)lane == (uint32_t)__builtin_ctzll((unsigned long long)ballot64(tr.active))) fl[src >> 6] = 0ull;
             }
-            cull_scene<MESH>(a.scene, c.acc, q, par, c.tri_lds, tr.active, ro, rd, tr.mb, pre_hit, masked, gmask);
+            // (after the load has drawn a pending direction: the row test needs the ray as it is traced)
+            cull_scene<MESH, OWN>(a.scene, c.acc, q, par, c.tri_lds, tr.active, ro, rd, tr.mb, pre_hit, masked, gmask,
+                                  (OWN && !GEN) ? own_surface_miss(c.acc, own, ro, rd) : 0xffffffffu);
             const uint32_t ticket = q.total;
             if (pending) {
                 drain_to(q, c.acc, prev_ticket);
-                tile_finish<COMPACT, MESH, SORT, DEFER>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+                tile_finish<COMPACT, MESH, SORT, DEFER, OWN>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
             }
             prev = tr; prev_ticket = ticket; pending = true; par ^= 1;
         } else {
@@ -335,7 +346,7 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
     }
     if (pending) {
         drain_to(q, c.acc, prev_ticket);
-        tile_finish<COMPACT, MESH, SORT, DEFER>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+        tile_finish<COMPACT, MESH, SORT, DEFER, OWN>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
     }
 }
 
@@ -346,8 +357,9 @@ __device__ unsigned long long g_wave_times[8][8192][2];
 __device__ uint32_t g_wave_hw[8][8192];
 #endif
 
-template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN = false, bool SORT = false>
+template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN = false, bool SORT = false, bool OWN = false>
 __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
+    static_assert(!OWN || (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE && !SORT), "own-surface form: the plain fused compacting kernel");
 #ifdef PT_WAVE_TIMES
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -405,7 +417,7 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
             cur = aligned ? find_range(a.dir_in.tbase(), a.dir_in.nr, wid * R) : find_range(a.dir_in.base(), a.dir_in.nr, wid * R * TILE);
         STAMP(2);
         // the run's R consecutive 64-path tiles; no workgroup barrier inside the loop
-        run_tiles<MODE, COMPACT, MESH, GEN, SORT, DEFER, RESOLVE>(a, c, q, a.in, a.out, a.depth, wid * R, R, tiles, n, packed_in, span_in,
+        run_tiles<MODE, COMPACT, MESH, GEN, SORT, DEFER, RESOLVE, OWN>(a, c, q, a.in, a.out, a.depth, wid * R, R, tiles, n, packed_in, span_in,
                                                   cur, wid * R * TILE, false, WgSpans{}, packed, traced, W * R * TILE, aligned);
         if (COMPACT) {
             // every run publishes its range count(s); the last workgroup out scans them

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(16), amdgpu_n
 // gets it drawn here as the next bounce's load would: `iter0` = the batch's first iteration, `wdepth` = the depth of the
 // bounce that wrote the pool.
 __global__ void k_export_paths(Pool p, TileMap map, uint32_t n_total, uint32_t n_live, int remaining,
-                               pt_path_segment *out, RangeDir dir, uint32_t span, int iter0, int wdepth) {
+                               pt_path_segment *out, RangeDir dir, uint32_t span, int iter0, int wdepth, uint32_t own_mask) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
     uint32_t src = i;
@@ -231,7 +231,7 @@ __global__ void k_export_paths(Pool p, TileMap map, uint32_t n_total, uint32_t n
     if (pid == DEAD_PID) { s.pixelIndex = -1; s.remainingBounces = 0; }
     else {
         const bool pending = (pid & PENDING_DIR) != 0u;
-        pid &= ~PENDING_DIR;
+        pid &= ~(PENDING_DIR | own_mask);                     // own_mask: OWN_MASK when the pool's pids carry the primitive left
         const uint32_t sm = sample_of(map, pid);
         s.pixelIndex = local_to_pixel(map, (int)(pid - sm * (uint32_t)map.tile_pixels));
         s.remainingBounces = i < n_live ? remaining : 0;

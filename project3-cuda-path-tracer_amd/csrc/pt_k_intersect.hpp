@@ -8,10 +8,16 @@ namespace {
 // Stages 1 + 2 for one tile (parity `par` of the wave's LDS block): store the rays, reset the best keys, test every
 // primitive's cull box and queue the candidates; passes run as the ring fills.  Triangle meshes keep their own
 // paths (every triangle through LDS tiles / the hierarchy inline / the k_mesh pre-pass) and fold into `mb`.
-template <int MESH>
+// OWN (the fused compacting k_bounce between two bounces of its own kind, scenes without meshes): the exact early miss has
+// been evaluated once per ray against the primitive the path left (`own_key`, own_surface_miss; ~0 for a camera ray), and a
+// primitive's step is the box test and one integer compare -- its row words are not loaded.  The candidates are those of
+// the other form plus, rarely, a primitive whose padded box holds the origin of a path that left ANOTHER one (a corner,
+// within the pad): the exact test decides, as for every candidate.
+template <int MESH, bool OWN = false>
 __device__ __forceinline__ void cull_scene(const SceneDev &sc, const SceneAcc &acc, WaveQ &q, int par, float *tri_lds,
                                            bool active, f3 ro, f3 rd, MeshBest &mb, const float4 *pre_hit,
-                                           bool masked = false, unsigned long long gmask = 0) {
+                                           bool masked = false, unsigned long long gmask = 0, uint32_t own_key = 0xffffffffu) {
+    static_assert(!OWN || MESH == MESH_NONE, "the own-surface form serves analytic scenes");
     const int lane = threadIdx.x & 63;
     {
         float *ry = q.rays(par) + lane;
@@ -76,7 +82,9 @@ __device__ __forceinline__ void cull_scene(const SceneDev &sc, const SceneAcc &a
             }
             continue;
         }
-        const uint64_t m = m_act & cull_candidates(cr, m_wild, ro, rd, cb[0], cb[1], cb[2], cb[3], cb[4], cb[5], tw, cb[7], cb[8], cb[9], cb[10]);
+        uint64_t m;
+        if (OWN) m = m_act & ((ballot64(cull_box(cr, cb[0], cb[1], cb[2], cb[3], cb[4], cb[5])) & ~ballot64(own_key == ent)) | m_wild);
+        else m = m_act & cull_candidates(cr, m_wild, ro, rd, cb[0], cb[1], cb[2], cb[3], cb[4], cb[5], tw, cb[7], cb[8], cb[9], cb[10]);
         if (m) {
             if (lane_of(m)) {
                 const uint32_t s = (q.total + rank_below(m)) & (Q_SLOTS - 1);
@@ -102,13 +110,14 @@ __device__ __forceinline__ void drain_to(WaveQ &q, const SceneAcc &acc, uint32_t
     }
 }
 
-// the winner of lane's path of the tile with parity `par`: t (-1: miss), normal, materialId, outside flag
+// the winner of lane's path of the tile with parity `par`: t (-1: miss), normal, materialId, outside flag and the
+// primitive's number (-1: miss)
 __device__ __forceinline__ void tile_result(const WaveQ &q, int par, const SceneAcc &acc, const float *__restrict__ tris,
-                                            const MeshBest &mb, float &t, f3 &n, int &mat, int &outside) {
+                                            const MeshBest &mb, float &t, f3 &n, int &mat, int &outside, int &geom) {
     const int lane = threadIdx.x & 63;
     const unsigned long long key = q.best(par)[lane];
     t = -1.0f; n = ptd::mk(0, 0, 0); mat = 0; outside = 1;
-    int geom = -1;
+    geom = -1;
     uint32_t info = 0;
     if (key != ~0ull) {
         const uint32_t lo = (uint32_t)key;                  // geom << 4 | code << 1 | outside
@@ -129,6 +138,11 @@ __device__ __forceinline__ void tile_result(const WaveQ &q, int par, const Scene
         info = acc.ginfo[geom];
     }
     if (geom >= 0) mat = (int)(info & 0x0fffffffu);
+}
+__device__ __forceinline__ void tile_result(const WaveQ &q, int par, const SceneAcc &acc, const float *__restrict__ tris,
+                                            const MeshBest &mb, float &t, f3 &n, int &mat, int &outside) {
+    int geom;
+    tile_result(q, par, acc, tris, mb, t, n, mat, outside, geom);
 }
 
 

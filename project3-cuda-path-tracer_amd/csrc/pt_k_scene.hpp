@@ -27,6 +27,9 @@ constexpr int GREC_FACE = 24;        // cube: + 3 * code: normalize(transform * 
                                      // in the words where a sphere keeps its invTranspose: 52 words, not 36 + 24, keep the
                                      // scene block small enough for six workgroups of the fused bounce kernel per CU
                                      // beside the Cornell scenes
+constexpr int GREC_ROW = 48;         // the record's last four words (16-B aligned): the reject row of the cull record, m_k0 m_k1 m_k2 m_k3
+                                     // (zeros where the cull record has none), for the per-lane own-surface test (own_surface_miss)
+static_assert(GREC_FACE + 8 * 3 <= GREC_ROW && GREC_ROW + 4 == GREC_WORDS, "gather record layout");
 // per-wave block: candidate ring + two tiles in flight (rays, best keys, winner records)
 constexpr int Q_SLOTS = 128;         // candidate ring entries (a tile's cull adds <= 64 per geom while < 64 wait)
 constexpr int PW_RING = 0;                               // u32[128]: lane | parity << 6 | type << 7 | geom << 9
@@ -167,6 +170,10 @@ __device__ __forceinline__ bool cull_box(const CullRay &c, float cx, float hx, f
 // its candidates: its origin sits 1e-6 above the wall it just left, well inside any box the float error
 // allows, and would otherwise cost every bounce ray one object-space test (C2: 0.24 candidates per ray).
 // One function for k_bounce / k_intersect and for k_cull0_mask, which memoises "some lane" per camera tile.
+// The row test does useful work only for a primitive whose padded box holds the ray's origin -- the surface the path has
+// just left; one the ray merely heads away from fails the box test (tn = max(.., 0) > tf).  The fused compacting k_bounce
+// therefore carries that primitive's number in the pid and evaluates the row test ONCE per ray (own_surface_miss below,
+// cull_scene<.., OWN>); every other kernel, and every session the launch plan keeps off that form, uses this function.
 // Returns the WAVE MASK of the candidate lanes: every compare goes straight to a scalar register pair and the
 // combination -- box and not(early miss) or wild -- is scalar mask arithmetic, not per-lane selects.
 #ifndef PT_CULL_ROW
@@ -221,6 +228,24 @@ __device__ __forceinline__ uint64_t cull_candidates(const CullRay &cr, uint64_t 
     }
 #endif
     return keep | m_wild;
+}
+
+// The same early miss for ONE primitive per lane: `own` = geom + 1 of the primitive the path left (0: none), its row
+// gathered from the last words of the gather record.  The straight-line form (PT_CULL_ROW == 2 above): the row differs by
+// lane, so there is no wave-uniform mode to dispatch on, and for the rows of modes 0..3 it has the value of the per-mode
+// forms (their off-diagonal entries are exact zeros: (m_kk o_k + 0) + (0 + m_k3) rounds twice, like fl(fl(m_kk o_k) + m_k3);
+// a row of zeros gives q_k = 0, never beyond the slab).  Returns the cull record's ring entry (word 11: type << 7 |
+// geom << 9; only a cube has a row) of the primitive this ray certainly misses, or ~0: cull_scene compares it with each
+// record's entry, one integer compare per primitive.
+__device__ __forceinline__ uint32_t own_surface_miss(const SceneAcc &acc, uint32_t own, f3 ro, f3 rd) {
+    uint32_t key = 0xffffffffu;
+    if (own != 0u) {
+        const float4 m = *reinterpret_cast<const float4 *>(acc.grec + (size_t)(own - 1u) * GREC_WORDS + GREC_ROW);
+        const float qk = (m.x * ro.x + m.y * ro.y) + (m.z * ro.z + m.w);
+        const float vk = (m.x * rd.x + m.y * rd.y) + m.z * rd.z;
+        if (__builtin_fabsf(qk) > 0.5f && qk * vk > 0.0f) key = ((uint32_t)PT_CUBE << 7) | ((own - 1u) << 9);
+    }
+    return key;
 }
 
 struct WaveQ {                        // wave-uniform ring cursors + the wave's LDS block

@@ -1006,6 +1006,7 @@ int pt_probe_sincos(const float *x, uint32_t first_bits, uint32_t n, float *s, f
 int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, float *dirs) { return one::pt_probe_hemisphere(normals, seeds, n, dirs); }
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
 int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }
+int pt_probe_own_surface_plan(uint64_t paths, int ngeoms, int plain_fused) { return one::pt_probe_own_surface_plan(paths, ngeoms, plain_fused); }
 int pt_probe_tri_form(const pt_triangle *triangles, int count, float origin_bound, const float *origins, const float *directions, int n,
                       uint16_t *ray_slots, int32_t *ray_class, float *form) {
     return one::pt_probe_tri_form(triangles, count, origin_bound, origins, directions, n, ray_slots, ray_class, form);

@@ -202,6 +202,10 @@ int pt_probe_clock(int microseconds, double *ghz) {
     return PT_OK;
 }
 
+int pt_probe_own_surface_plan(uint64_t paths, int ngeoms, int plain_fused) {
+    return own_surface_plan(paths, ngeoms, plain_fused != 0) ? 1 : 0;
+}
+
 int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, float *dirs) {
     if (n < 0 || (n > 0 && (!normals || !seeds || !dirs))) return fail(PT_ERR_INVALID, "pt_probe_hemisphere: bad argument");
     if (n == 0) return PT_OK;

@@ -48,6 +48,21 @@ constexpr uint32_t DEAD_PID = 0xffffffffu;
 // still to be drawn.  pids stay below 2^30 (pt_init: cap * 4 < 2^32), so DEAD_PID is the only
 // word with this bit set that is not a pending slot.
 constexpr uint32_t PENDING_DIR = 0x80000000u;
+// bits 26..29 of a live slot's pid, between two fused compacting bounces only: the primitive the path has just left, as
+// geom + 1 (0 = none), so that the next bounce runs the own-surface early miss once per ray against that primitive's row
+// instead of once per primitive (pt_k_intersect.hpp: cull_scene<.., OWN>).  The launch plan takes
+// the form only for batches whose pids leave the bits free and scenes whose primitives fit the code (own_surface_plan);
+// tile_load and pt_export_paths strip them where they strip PENDING_DIR.  Bits and not an eleventh pool row: a row costs
+// every survivor 4 B out and 4 B in, and the batches that matter stay below 2^26 paths.
+constexpr int OWN_SHIFT = 26;
+constexpr uint32_t OWN_MASK = 0xfu << OWN_SHIFT;
+constexpr int OWN_MAX_GEOMS = 15;                          // codes 1..15
+constexpr uint64_t OWN_MAX_PATHS = 1ull << OWN_SHIFT;      // pids of a batch are below its path count
+// `plain_fused`: writer and reader are the fused compacting k_bounce without mesh pre-pass, material keys or first-bounce
+// cache (the cache keeps no primitive number)
+inline bool own_surface_plan(uint64_t paths, int ngeoms, bool plain_fused) {
+    return plain_fused && ngeoms >= 1 && ngeoms <= OWN_MAX_GEOMS && paths <= OWN_MAX_PATHS;
+}
 
 // ---------------------------------------------------------------------------
 // device-side parameter blocks (few pointers: every extra pointer pair costs
