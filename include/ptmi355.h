@@ -302,6 +302,35 @@ int pt_clear_image(void);
  * (dev_image, pathtrace.cu:71,84,389; the iteration number is the caller's).  Synchronises the session first. */
 int pt_set_image(const float *host_image_sum);
 float *pt_device_image(void);                        /* device pointer of the accumulation buffer */
+
+/* ---- first-hit G-buffer and edge-avoiding A-trous filter (Dammertz et al. 2010) of the accumulated image -------------
+ * What the course's next project adds to this renderer: a usable picture after 10-20 samples.  All arithmetic is binary32,
+ * one rounding per operation, no FMA (DESIGN.md section 6.14 has the complete specification; tests/atrous_model.py is its
+ * numpy form, and the device's result equals it bit for bit).
+ * G-buffer: for every pixel of the CURRENT camera (pt_set_camera) the first hit of the reference's generateRayFromCamera
+ * ray -- pinhole, unjittered, the same every iteration, also in sessions with PT_AA_JITTER or a lens -- found by the
+ * production cull / exact-test code: t (-1 on a miss), surface normal, materialId (-1 on a miss) and position = origin +
+ * direction * t (one multiply, one add per component; normal = position = 0 on a miss).  Computed once per camera and kept.
+ * Filter: c_0 = running sum / (float)iter; level l = 0 .. levels - 1 is a 5 x 5 B3-spline kernel {1/16, 1/4, 3/8, 1/4, 1/16}^2 with
+ * taps 2^l pixels apart (taps outside the image are skipped), each weighted by exp_neg(|dc|^2 / sc^2) exp_neg(|dn|^2 / sn^2)
+ * exp_neg(|dp|^2 / sp^2) with sc = sigma_color * 2^-l, sn = sigma_normal, sp = sigma_position, normalised by the sum of
+ * the weights.  levels = 0 returns the mean.
+ * Both calls are synchronous, run on the session's stream after everything enqueued before them (asynchronous batches
+ * included) and READ the session only: accumulation buffer, path pools, statistics and counters (G-buffer rays are not
+ * counted), host image and the PT_LOOKAHEAD windows stay exactly as they were.  Their buffers (G-buffer, two colour
+ * planes) are allocated on first use and released by pt_free.  Under PT_LOOKAHEAD the sum filtered is the one the last
+ * served call left (what pt_get_image returns).
+ * PT_ERR_INVALID: before pt_init; params == NULL; levels outside [0, 10]; a sigma that is not a finite number > 0 or whose
+ * square at any level (sigma_color * 2^-l included) is not a normal binary32 number; iter < 1; a tiled session (tile_count > 1)
+ * or one over several devices -- those hold a tile, not the frame; extending the filter to them is a later change. */
+typedef struct pt_denoise_params { int32_t levels; float sigma_color, sigma_normal, sigma_position; } pt_denoise_params;
+/* first hits of the current camera's pinhole rays; every output optional (host pointers): normals, positions W*H*3
+ * floats, t W*H floats, material W*H int32 */
+int pt_gbuffer(float *normals, float *positions, float *t, int32_t *material);
+/* A-trous filter of the running sum after `iter` iterations; host_rgb (W*H*3 floats, the denoised MEAN) and
+ * host_rgba (W*H*4 bytes: sendImageToPBO's rule with divisor 1) optional; the result also stays on the device */
+int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8_t *host_rgba);
+float *pt_denoised_device_image(void);   /* device pointer of the last result (W*H*3 floats), NULL before the first pt_denoise */
 int pt_get_stats(pt_stats *stats);
 /* rays traced since pt_init, read from the device-side counter (includes
  * asynchronous batches); synchronises the stream.  Negative = pt_status. */

@@ -10,6 +10,7 @@ from .binding import (  # noqa: F401
     set_camera, set_lens, synchronize, tonemap, trace_batch, trace_batch_async, trace_begin, trace_bounce,
     trace_end, clear_image, version, has_experiments, set_profiling, get_profile, STAGES, total_rays, counters, cull_boxes, num_devices, exchange_transport, tri_bounds, tri_records,
     set_image, probe_rng, probe_sincos, probe_sincos_sums, probe_hemisphere, probe_sqrt, probe_clock, probe_tri_form, probe_own_surface_plan,
+    gbuffer, denoise, denoised_device_ptr, DenoiseParams,
 )
 from .build import build  # noqa: F401
 from . import sharding  # noqa: F401,E402

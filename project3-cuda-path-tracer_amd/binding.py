@@ -74,6 +74,11 @@ class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 6), ("launches", C.c_int64 * 6)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float)]
+
+
 STAGES = ("raygen", "bounce", "intersect", "sort", "gather", "mesh")
 
 
@@ -156,6 +161,9 @@ def library():
             L.pt_probe_clock.argtypes = [C.c_int, C.POINTER(C.c_double)]
             L.pt_probe_tri_form.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_probe_own_surface_plan.argtypes = [C.c_uint64, C.c_int, C.c_int]
+            L.pt_gbuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_denoise.argtypes = [C.POINTER(DenoiseParams), C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_denoised_device_image.restype = C.c_void_p
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -318,6 +326,37 @@ def set_image(image_sum):
     """Resume an accumulation: the running sum becomes `image_sum` (W*H*3 floats)."""
     img = np.ascontiguousarray(image_sum, dtype=np.float32)
     _chk(library().pt_set_image(_p(img)))
+
+
+def gbuffer():
+    """First hits of the current camera's pinhole rays (include/ptmi355.h: pt_gbuffer): {"normal": [npix, 3] float32,
+    "position": [npix, 3] float32, "t": [npix] float32 (-1: miss), "materialId": [npix] int32 (-1: miss)}."""
+    if _scene is None:
+        _chk(library().pt_gbuffer(None, None, None, None))          # raises "not initialised"
+    w, h = _scene.resolution
+    n = w * h
+    out = {"normal": np.zeros((n, 3), dtype=np.float32), "position": np.zeros((n, 3), dtype=np.float32),
+           "t": np.zeros(n, dtype=np.float32), "materialId": np.zeros(n, dtype=np.int32)}
+    _chk(library().pt_gbuffer(_p(out["normal"]), _p(out["position"]), _p(out["t"]), _p(out["materialId"])))
+    return out
+
+
+def denoise(iteration, levels=5, sigma_color=1.0, sigma_normal=0.35, sigma_position=0.5, rgba=False):
+    """Edge-avoiding A-trous filter of the running sum after `iteration` iterations (include/ptmi355.h: pt_denoise):
+    the denoised MEAN as [npix, 3] float32; with rgba=True also its RGBA8 form, (mean, [npix, 4] uint8)."""
+    if _scene is None:
+        _chk(library().pt_denoise(None, int(iteration), None, None))   # raises "not initialised"
+    w, h = _scene.resolution
+    prm = DenoiseParams(int(levels), float(sigma_color), float(sigma_normal), float(sigma_position))
+    img = np.zeros((w * h, 3), dtype=np.float32)
+    px = np.zeros((w * h, 4), dtype=np.uint8) if rgba else None
+    _chk(library().pt_denoise(C.byref(prm), int(iteration), _p(img), _p(px)))
+    return (img, px) if rgba else img
+
+
+def denoised_device_ptr():
+    """Device pointer of the last denoise() result (W*H*3 floats), None before the first."""
+    return library().pt_denoised_device_image()
 
 
 def device_image_ptr():

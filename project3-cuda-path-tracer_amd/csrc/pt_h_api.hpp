@@ -57,6 +57,9 @@ void pt_free(void) {
     if (R.iter_counts) (void)hipFree(R.iter_counts);
     if (R.h_stats) (void)hipHostFree(R.h_stats);
     if (R.scratch) (void)hipFree(R.scratch);
+    if (R.gb_mem) (void)hipFree(R.gb_mem);
+    for (int k = 0; k < 2; ++k) if (R.dn_plane[k]) (void)hipFree(R.dn_plane[k]);
+    if (R.dn_rgba) (void)hipFree(R.dn_rgba);
     if (R.dbg_counts) (void)hipFree(R.dbg_counts);
     if (R.copy_stream) (void)hipStreamSynchronize(R.copy_stream);
     for (auto &h : R.host_regs) (void)hipHostUnregister(h.ptr);

@@ -205,6 +205,16 @@ struct Renderer {
     bool async_direct_enabled = true;     // PTMI355_ASYNC_DIRECT=0: always snapshot + copy engine
     unsigned int *dbg_counts = nullptr;   // PTMI355_DBG_COUNTS=<words>: buffer for an instrumented kernel build's block counts (BounceArgs::dbg_counts)
     size_t dbg_words = 0;
+    // pt_gbuffer / pt_denoise (pt_h_denoise.hpp): buffers of their own, allocated on first use.  The G-buffer is the one of
+    // camera gb_cam and is kept until the camera differs; the filter's levels ping-pong between the two colour planes
+    // (packed float3), dn_result = the plane the last pt_denoise left its result in.
+    float4 *gb_mem = nullptr;     // gA[npix] {normal, t}, then gB[npix] {position, materialId}
+    bool gb_valid = false;
+    pt_camera gb_cam{};
+    float *dn_plane[2] = {nullptr, nullptr};
+    uint8_t *dn_rgba = nullptr;
+    float *dn_result = nullptr;
+    uint64_t dn_launches[3] = {0, 0, 0};   // k_gbuffer / k_atrous / k_denoise_mean launches since pt_init (ptdbg_denoise)
     void *scratch = nullptr;      // export / import staging
     size_t scratch_bytes = 0;
     // stepping state

@@ -891,6 +891,18 @@ int pt_get_image(float *host_image_sum) {
     return on_one(0, [&](Worker &) -> int { return one::pt_get_image(host_image_sum); });      // context 0's buffer is the frame
 }
 
+// first-hit G-buffer and A-trous filter: single-device, whole-frame sessions (a context of a session over several devices
+// holds a tile, not the frame)
+int pt_gbuffer(float *normals, float *positions, float *t, int32_t *material) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_gbuffer: this session tiles the frame over %d devices; the G-buffer needs a single-device session", G.K);
+    return one::pt_gbuffer(normals, positions, t, material);
+}
+int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8_t *host_rgba) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_denoise: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_denoise(params, iter, host_rgb, host_rgba);
+}
+float *pt_denoised_device_image(void) { return G.live ? nullptr : one::pt_denoised_device_image(); }
+
 int pt_tonemap(uint8_t *host_rgba, int iter) {
     if (!G.live) return one::pt_tonemap(host_rgba, iter);
     const int rc = multi_sync();

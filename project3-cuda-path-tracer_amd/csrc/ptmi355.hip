@@ -71,6 +71,7 @@ static inline const char *pt_experiment(const char *name) {
 #include "pt_h_enqueue.hpp"
 #include "pt_h_image.hpp"
 #include "pt_h_api.hpp"       // (includes pt_h_scene.hpp between pt_free and pt_init)
+#include "pt_h_denoise.hpp"
 
 
 #include "pt_probe.hpp"
@@ -117,6 +118,20 @@ extern "C" int ptdbg_lookahead_masked(unsigned long long out[2]) {
     if (!g_single.live) return -1;
     out[0] = g_single.la_masked_windows; out[1] = g_single.la_masked_calls;
     return 0;
+}
+
+// diagnostics (not in include/ptmi355.h): launches of k_gbuffer / k_atrous / k_denoise_mean since pt_init (single-device sessions)
+extern "C" int ptdbg_denoise(unsigned long long out[3]) {
+    if (!g_single.live) return -1;
+    for (int k = 0; k < 3; ++k) out[k] = g_single.dn_launches[k];
+    return 0;
+}
+
+// diagnostics (not in include/ptmi355.h): device times of k_gbuffer, every level of k_atrous and a device-to-device copy of the
+// bytes one level moves, `reps` rounds (pt_h_denoise.hpp: denoise_times; profiles/denoise/measure.py).  Single-device sessions.
+extern "C" int ptdbg_denoise_times(const pt_denoise_params *params, int iter, int reps, float *ms) {
+    if (G.live) return fail(PT_ERR_INVALID, "ptdbg_denoise_times: single-device sessions");
+    return one::denoise_times(params, iter, reps, ms);
 }
 
 #ifdef PT_WAVE_TIMES

@@ -5,7 +5,11 @@
 //   ptbench SCENEFILE.txt [--iters N] [--batch B] [--out BASENAME] [--sort] [--no-compact]
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
-//           [--per-call [--warmup W] [--no-lookahead]]
+//           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP]
+//
+// --denoise LEVELS,SC,SN,SP: after the last iteration, the edge-avoiding A-trous filter (pt_denoise: LEVELS levels, sigmas
+// of colour / normal / position) of the accumulated image; BASE.<N>samp.denoised.png is written beside the image through the
+// same saveImage pipeline (clamp, x255, truncate -- on the denoised mean), and one line reports the filter's time.
 //
 // --batch B: iterations per launch sequence (default: up to 64 and ~40 M paths, as the shim sizes its windows; 1 = one
 // pathtrace() per iteration); every batch but the last is enqueued without waiting, so consecutive batches overlap on the
@@ -47,13 +51,15 @@ int main(int argc, char **argv) {
         printf("Usage: %s SCENEFILE.txt [--iters N] [--batch B] [--out BASE] [--sort] [--no-compact] [--cache-first] "
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
-               "[--per-call [--warmup W] [--no-lookahead]]\n", argv[0]);
+               "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
     unsigned flags = PT_COMPACT | PT_PIN_IMAGE | PT_HOST_SPARSE;      // `image` below lives until pt_free and is only read here
     bool pfm = false, save_sum = false, per_call = false, lookahead = true;
     int warmup = 64;
+    bool denoise = false;
+    pt_denoise_params dn = {0, 0.0f, 0.0f, 0.0f};
     std::string resume;
     int start = -1;
     float lens_radius = 0.0f, focal_distance = 0.0f;
@@ -84,6 +90,14 @@ int main(int argc, char **argv) {
         else if (a == "--per-call") per_call = true;
         else if (a == "--warmup" && i + 1 < argc) warmup = atoi(argv[++i]);
         else if (a == "--no-lookahead") lookahead = false;
+        else if (a == "--denoise" && i + 1 < argc) {
+            int lv = 0;
+            if (sscanf(argv[++i], "%d,%f,%f,%f", &lv, &dn.sigma_color, &dn.sigma_normal, &dn.sigma_position) != 4) {
+                fprintf(stderr, "--denoise wants LEVELS,SIGMA_COLOR,SIGMA_NORMAL,SIGMA_POSITION\n");
+                return 1;
+            }
+            dn.levels = lv; denoise = true;
+        }
         else if (a == "--strip-rows" && i + 1 < argc) strip_rows = atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) { devices.clear(); for (int k = 0, n = atoi(argv[++i]); k < n; ++k) devices.push_back(k); }
         else if (a == "--devices" && i + 1 < argc) {
@@ -188,6 +202,22 @@ int main(int argc, char **argv) {
     pth_image_to_rgb8(image.data(), W, H, (float)iteration, rgb.data());
     if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     printf("Saved %s.\n", name);
+    if (denoise) {
+        // the first call computes the G-buffer of this camera as well; the second is the filter alone
+        std::vector<float> mean((size_t)W * H * 3);
+        const auto d0 = std::chrono::steady_clock::now();
+        if (pt_denoise(&dn, iteration, NULL, NULL) != PT_OK) { fprintf(stderr, "pt_denoise: %s\n", pt_last_error()); return 1; }
+        const auto d1 = std::chrono::steady_clock::now();
+        if (pt_denoise(&dn, iteration, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise: %s\n", pt_last_error()); return 1; }
+        const auto d2 = std::chrono::steady_clock::now();
+        printf("denoise: %d levels, sigmas %g / %g / %g: %.3f ms with the G-buffer, %.3f ms the filter alone (with the copy of the result)\n",
+               dn.levels, dn.sigma_color, dn.sigma_normal, dn.sigma_position, std::chrono::duration<double, std::milli>(d1 - d0).count(),
+               std::chrono::duration<double, std::milli>(d2 - d1).count());
+        snprintf(name, sizeof name, "%s.%dsamp.denoised.png", out.c_str(), iteration);
+        pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+    }
     if (pfm) {
         snprintf(name, sizeof name, "%s.%dsamp.pfm", out.c_str(), iteration);
         pth_write_pfm(name, image.data(), W, H, (float)iteration);
