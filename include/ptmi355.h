@@ -331,6 +331,41 @@ int pt_gbuffer(float *normals, float *positions, float *t, int32_t *material);
  * host_rgba (W*H*4 bytes: sendImageToPBO's rule with divisor 1) optional; the result also stays on the device */
 int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8_t *host_rgba);
 float *pt_denoised_device_image(void);   /* device pointer of the last result (W*H*3 floats), NULL before the first pt_denoise */
+
+/* ---- the filter with history: what earlier cameras accumulated, reprojected through the G-buffers --------------------
+ * A host that moves the camera (pt_set_camera + pt_clear_image) starts again at one sample per pixel, where the filter
+ * has nothing to work with.  The pixels of a diffuse surface do not depend on the view: pt_denoise_temporal looks up, for
+ * every pixel of the current camera, what the previous temporal call's camera had accumulated at the same surface point,
+ * blends it in weighted by its sample count, and filters that (DESIGN.md section 6.15 has the complete specification,
+ * binary32, one rounding per operation, no FMA; tests/temporal_model.py is its numpy form, equal bit for bit).
+ * State: `cur` = {camera, G-buffer, colours C, sample counts N} of the last temporal call, and the history Hc, Hn in the
+ * grid of cur's camera; none after pt_init and after pt_history_reset.  A call with the session's camera K:
+ *   1. cur exists with other camera bytes than K: Hc, Hn = cur reprojected into K's grid.  Pixel P with first hit {n, p, t,
+ *      mat} gets history only if mat >= 0 is neither reflective nor refractive; v = p - cur.position, z = dot(v, cur.view) > 0;
+ *      fx = floorf(W * 0.5f - dot(v, cur.right) / (z * cur.pixelLength[0]) + 0.5f) in [0, W), fy likewise with up / H (the
+ *      inverse of generateRayFromCamera, nearest pixel Q); cur's first hit at Q has the same material, a position within
+ *      position_tolerance * t of p and a normal within normal_tolerance of n.  Then Hc[P] = C[Q], Hn[P] = min(N[Q],
+ *      max_history); Hc[P] = Hn[P] = 0 otherwise.  The same camera bytes: Hc, Hn stay (this camera's samples are in the
+ *      running sum; a pt_clear_image without a camera change drops them and keeps what came before).
+ *   2. c0 = (sum + Hc * Hn) / ((float)iter + Hn) per channel; cur = {K, its G-buffer, C = c0, N = (float)iter + Hn}.
+ *   3. pt_denoise's levels on c0.  With Hn = 0 everywhere the call equals pt_denoise bit for bit.
+ * Synchronous, on the session's stream, and READS the session exactly as pt_denoise does; pt_denoise neither reads nor
+ * disturbs the history, and the two may be interleaved freely.  80 bytes per pixel (a second G-buffer, two colour and two
+ * length planes, the history) are allocated by the first temporal call and released by pt_free, which ends the history.
+ * PT_ERR_INVALID: everything pt_denoise refuses; temporal == NULL; max_history outside [0, 1 << 20]; a tolerance that is
+ * not a finite number > 0 or whose square is not a normal binary32 number; pt_history before the first temporal call. */
+typedef struct pt_temporal_params {
+    int32_t max_history;          /* cap on the sample count history may weigh in with, [0, 1 << 20]; 0 = history never used */
+    float   position_tolerance;   /* relative to the hit distance t of the new view; finite, > 0 */
+    float   normal_tolerance;     /* on |n_new - n_old|; finite, > 0 */
+} pt_temporal_params;
+/* pt_denoise with history: same outputs, same validation of `params`, same refusals (tiled / multi-device sessions) */
+int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_params *temporal, int iter,
+                        float *host_rgb, uint8_t *host_rgba);
+/* the history as the last pt_denoise_temporal used it, in the grid of that call's camera; both optional host pointers:
+ * rgb W*H*3 floats, length W*H floats (0 = no history for the pixel) */
+int pt_history(float *rgb, float *length);
+int pt_history_reset(void);       /* forget everything; the next temporal call equals pt_denoise bit for bit */
 int pt_get_stats(pt_stats *stats);
 /* rays traced since pt_init, read from the device-side counter (includes
  * asynchronous batches); synchronises the stream.  Negative = pt_status. */

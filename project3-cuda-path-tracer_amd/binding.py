@@ -79,6 +79,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("position_tolerance", C.c_float), ("normal_tolerance", C.c_float)]
+
+
 STAGES = ("raygen", "bounce", "intersect", "sort", "gather", "mesh")
 
 
@@ -164,6 +168,8 @@ def library():
             L.pt_gbuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_denoise.argtypes = [C.POINTER(DenoiseParams), C.c_int, C.c_void_p, C.c_void_p]
             L.pt_denoised_device_image.restype = C.c_void_p
+            L.pt_denoise_temporal.argtypes = [C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_history.argtypes = [C.c_void_p, C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -352,6 +358,38 @@ def denoise(iteration, levels=5, sigma_color=1.0, sigma_normal=0.35, sigma_posit
     px = np.zeros((w * h, 4), dtype=np.uint8) if rgba else None
     _chk(library().pt_denoise(C.byref(prm), int(iteration), _p(img), _p(px)))
     return (img, px) if rgba else img
+
+
+def denoise_temporal(iteration, params=None, temporal=None, rgba=False):
+    """denoise() with the history of earlier cameras blended in (include/ptmi355.h: pt_denoise_temporal).  `params`: a
+    DenoiseParams (default 5, 1.0, 0.35, 0.5), `temporal`: a TemporalParams (default 64, 0.1, 0.1).  The denoised MEAN as
+    [npix, 3] float32; with rgba=True also its RGBA8 form."""
+    if _scene is None:
+        _chk(library().pt_denoise_temporal(None, None, int(iteration), None, None))   # raises "not initialised"
+    w, h = _scene.resolution
+    prm = params if params is not None else DenoiseParams(5, 1.0, 0.35, 0.5)
+    tmp = temporal if temporal is not None else TemporalParams(64, 0.1, 0.1)
+    img = np.zeros((w * h, 3), dtype=np.float32)
+    px = np.zeros((w * h, 4), dtype=np.uint8) if rgba else None
+    _chk(library().pt_denoise_temporal(C.byref(prm), C.byref(tmp), int(iteration), _p(img), _p(px)))
+    return (img, px) if rgba else img
+
+
+def history():
+    """The history as the last denoise_temporal() used it, in the grid of that call's camera (include/ptmi355.h: pt_history):
+    ([npix, 3] float32 colours, [npix] float32 sample counts; 0 = no history for the pixel)."""
+    if _scene is None:
+        _chk(library().pt_history(None, None))                              # raises "not initialised"
+    w, h = _scene.resolution
+    rgb = np.zeros((w * h, 3), dtype=np.float32)
+    length = np.zeros(w * h, dtype=np.float32)
+    _chk(library().pt_history(_p(rgb), _p(length)))
+    return rgb, length
+
+
+def history_reset():
+    """Forget the history: the next denoise_temporal() equals denoise() bit for bit."""
+    _chk(library().pt_history_reset())
 
 
 def denoised_device_ptr():

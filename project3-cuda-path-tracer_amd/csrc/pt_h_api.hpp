@@ -60,6 +60,13 @@ void pt_free(void) {
     if (R.gb_mem) (void)hipFree(R.gb_mem);
     for (int k = 0; k < 2; ++k) if (R.dn_plane[k]) (void)hipFree(R.dn_plane[k]);
     if (R.dn_rgba) (void)hipFree(R.dn_rgba);
+    if (R.gb_alt) (void)hipFree(R.gb_alt);
+    for (int k = 0; k < 2; ++k) {
+        if (R.tp_c[k]) (void)hipFree(R.tp_c[k]);
+        if (R.tp_n[k]) (void)hipFree(R.tp_n[k]);
+    }
+    if (R.tp_hc) (void)hipFree(R.tp_hc);
+    if (R.tp_hn) (void)hipFree(R.tp_hn);
     if (R.dbg_counts) (void)hipFree(R.dbg_counts);
     if (R.copy_stream) (void)hipStreamSynchronize(R.copy_stream);
     for (auto &h : R.host_regs) (void)hipHostUnregister(h.ptr);

@@ -1,5 +1,7 @@
 // pt_h_denoise.hpp -- pt_gbuffer / pt_denoise / pt_denoised_device_image of ONE context (namespace one): the first-hit G-buffer of
-// the current camera and the edge-avoiding A-trous filter of the running sum (kernels: pt_k_denoise.hpp)
+// the current camera and the edge-avoiding A-trous filter of the running sum (kernels: pt_k_denoise.hpp);
+// pt_denoise_temporal / pt_history / pt_history_reset: the same filter on the sum blended with what earlier cameras had
+// accumulated, looked up through the two cameras' G-buffers
 // (one of the host-side headers of libptmi355.so, included by ptmi355.hip -- the only translation unit -- in dependency order)
 #pragma once
 
@@ -20,7 +22,11 @@ static int denoise_session_ok(const char *who) {
 // the G-buffer of R.cam: computed once per camera, kept until the camera's bytes differ
 static int ensure_gbuffer(void) {
     if (!R.gb_mem) HIPCHK(hipMalloc((void **)&R.gb_mem, (size_t)R.npix * 2 * sizeof(float4)));
-    if (R.gb_valid && memcmp(&R.gb_cam, &R.cam, sizeof R.cam) == 0) return PT_OK;
+    const bool same = memcmp(&R.gb_cam, &R.cam, sizeof R.cam) == 0;
+    if (R.gb_valid && same) return PT_OK;
+    // the record of the last temporal call refers to this allocation and to another camera: it keeps it, the new camera's
+    // G-buffer goes to the second allocation (which exists: only a temporal call sets tp_cur)
+    if (!same && R.tp_cur && R.tp_gb == R.gb_mem) std::swap(R.gb_mem, R.gb_alt);
     float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
     const int blocks = std::min(R.grid, (R.npix + BLOCK - 1) / BLOCK);
     PT_MESH_DISPATCH(hipLaunchKernelGGL((k_gbuffer<MESH, SLDS>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream, gA, gB, R.scene,
@@ -32,12 +38,15 @@ static int ensure_gbuffer(void) {
 }
 
 // level l of the filter: step 2^l, from the accumulation buffer (l = 0: the mean is formed as it is read) or the plane the
-// level before wrote, into plane l & 1
-static int launch_atrous(int l, float div, float sc2, float sn2, float sp2, uint8_t *rgba) {
+// level before wrote, into plane l & 1.  `c0` (l = 0 of a temporal call): the blended colours, read as they are.
+static int launch_atrous(int l, float div, float sc2, float sn2, float sp2, uint8_t *rgba, const float *c0 = nullptr) {
     const float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
     const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
     const int out = l & 1;
-    if (l == 0)
+    if (l == 0 && c0)
+        hipLaunchKernelGGL(k_atrous<false>, grid, dim3(BLOCK), 0, R.stream, c0, gA, gB, R.dn_plane[out], rgba, R.map.W, R.map.H, 1, 1.0f,
+                           sc2, sn2, sp2);
+    else if (l == 0)
         hipLaunchKernelGGL(k_atrous<true>, grid, dim3(BLOCK), 0, R.stream, (const float *)R.image, gA, gB, R.dn_plane[out], rgba,
                            R.map.W, R.map.H, 1, div, sc2, sn2, sp2);
     else
@@ -68,32 +77,38 @@ int pt_gbuffer(float *normals, float *positions, float *t, int32_t *material) {
     return PT_OK;
 }
 
-int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8_t *host_rgba) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_denoise: not initialised");
-    if (!params) return fail(PT_ERR_INVALID, "pt_denoise: params is null");
+// what pt_denoise and pt_denoise_temporal (`who`) refuse, in this order; the squares the kernels divide by
+static int denoise_args_ok(const char *who, const pt_denoise_params *params, int iter, float sc2[10], float &sn2, float &sp2) {
+    if (!R.live) return fail(PT_ERR_INVALID, "%s: not initialised", who);
+    if (!params) return fail(PT_ERR_INVALID, "%s: params is null", who);
     const int levels = params->levels;
-    if (levels < 0 || levels > 10) return fail(PT_ERR_INVALID, "pt_denoise: levels %d outside [0, 10]", levels);
+    if (levels < 0 || levels > 10) return fail(PT_ERR_INVALID, "%s: levels %d outside [0, 10]", who, levels);
     const float sig[3] = {params->sigma_color, params->sigma_normal, params->sigma_position};
     const char *names[3] = {"sigma_color", "sigma_normal", "sigma_position"};
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(sig[k]) || !(sig[k] > 0.0f))
-            return fail(PT_ERR_INVALID, "pt_denoise: %s = %g is not a finite number > 0", names[k], (double)sig[k]);
-    // the squares the kernels divide by: sigma_color halves with every level (Dammertz; exact), the others stay.  Each must
-    // be a normal number: 0 / 0 at the centre tap otherwise.
-    float sc2[10];
-    const float sn2 = sig[1] * sig[1], sp2 = sig[2] * sig[2];
-    if (!std::isnormal(sn2)) return fail(PT_ERR_INVALID, "pt_denoise: sigma_normal = %g: its square is not a normal binary32 number", (double)sig[1]);
-    if (!std::isnormal(sp2)) return fail(PT_ERR_INVALID, "pt_denoise: sigma_position = %g: its square is not a normal binary32 number", (double)sig[2]);
+            return fail(PT_ERR_INVALID, "%s: %s = %g is not a finite number > 0", who, names[k], (double)sig[k]);
+    // sigma_color halves with every level (Dammertz; exact), the others stay.  Each square must be a normal number: 0 / 0 at
+    // the centre tap otherwise.
+    sn2 = sig[1] * sig[1]; sp2 = sig[2] * sig[2];
+    if (!std::isnormal(sn2)) return fail(PT_ERR_INVALID, "%s: sigma_normal = %g: its square is not a normal binary32 number", who, (double)sig[1]);
+    if (!std::isnormal(sp2)) return fail(PT_ERR_INVALID, "%s: sigma_position = %g: its square is not a normal binary32 number", who, (double)sig[2]);
     for (int l = 0; l < std::max(1, levels); ++l) {
         const float s = sig[0] * ldexpf(1.0f, -l);
         const float s2 = s * s;
         if (!std::isnormal(s2))
-            return fail(PT_ERR_INVALID, "pt_denoise: sigma_color = %g: the square of sigma_color * 2^-%d is not a normal binary32 number", (double)sig[0], l);
+            return fail(PT_ERR_INVALID, "%s: sigma_color = %g: the square of sigma_color * 2^-%d is not a normal binary32 number", who, (double)sig[0], l);
         sc2[l] = s2;
     }
-    if (iter < 1) return fail(PT_ERR_INVALID, "pt_denoise: iter %d < 1", iter);
-    int rc = denoise_session_ok("pt_denoise");
+    if (iter < 1) return fail(PT_ERR_INVALID, "%s: iter %d < 1", who, iter);
+    return denoise_session_ok(who);
+}
+
+int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8_t *host_rgba) {
+    float sc2[10], sn2, sp2;
+    int rc = denoise_args_ok("pt_denoise", params, iter, sc2, sn2, sp2);
     if (rc) return rc;
+    const int levels = params->levels;
     const size_t n = (size_t)R.npix;
     for (int k = 0; k < 2; ++k)
         if (!R.dn_plane[k]) HIPCHK(hipMalloc((void **)&R.dn_plane[k], n * 3 * sizeof(float)));
@@ -123,6 +138,128 @@ int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8
 }
 
 float *pt_denoised_device_image(void) { return R.live ? R.dn_result : nullptr; }
+
+// ---- history across camera moves ----------------------------------------------------------------
+// cur (camera `A`, G-buffer gb, colours C, sample counts N) reprojected into the grid of R.cam, whose G-buffer is R.gb_mem
+static int launch_reproject(const pt_camera &A, const float4 *gb, const float *C, const float *N, const pt_temporal_params &tp) {
+    const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
+    hipLaunchKernelGGL(k_reproject, grid, dim3(BLOCK), 0, R.stream, (const float4 *)R.gb_mem, (const float4 *)(R.gb_mem + R.npix), gb,
+                       gb + R.npix, C, N, R.scene.mats, R.scene.nmats, A, R.tp_hc, R.tp_hn, R.map.W, R.map.H, (float)tp.max_history,
+                       tp.position_tolerance, tp.normal_tolerance * tp.normal_tolerance);
+    HIPCHK(hipGetLastError());
+    R.tp_launches[0]++;
+    return PT_OK;
+}
+
+// the running sum blended with the history into C / N: one launch
+static int launch_blend(float div, float *C, float *N, uint8_t *rgba) {
+    const uint32_t n = (uint32_t)R.npix;
+    if (((uintptr_t)R.image & 15) == 0)         // (a caller's accumulation buffer, pt_scene_desc::device_image, may sit anywhere)
+        hipLaunchKernelGGL(k_temporal_blend<true>, dim3((n / 4 + 3 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, (const float *)R.image,
+                           (const float *)R.tp_hc, (const float *)R.tp_hn, C, N, rgba, n, div);
+    else
+        hipLaunchKernelGGL(k_temporal_blend<false>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, (const float *)R.image,
+                           (const float *)R.tp_hc, (const float *)R.tp_hn, C, N, rgba, n, div);
+    HIPCHK(hipGetLastError());
+    R.tp_launches[1]++;
+    return PT_OK;
+}
+
+static int temporal_args_ok(const char *who, const pt_temporal_params *tp) {
+    if (!tp) return fail(PT_ERR_INVALID, "%s: temporal is null", who);
+    if (tp->max_history < 0 || tp->max_history > (1 << 20))
+        return fail(PT_ERR_INVALID, "%s: max_history %d outside [0, %d]", who, tp->max_history, 1 << 20);
+    const float tol[2] = {tp->position_tolerance, tp->normal_tolerance};
+    const char *names[2] = {"position_tolerance", "normal_tolerance"};
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(tol[k]) || !(tol[k] > 0.0f))
+            return fail(PT_ERR_INVALID, "%s: %s = %g is not a finite number > 0", who, names[k], (double)tol[k]);
+        if (!std::isnormal(tol[k] * tol[k]))
+            return fail(PT_ERR_INVALID, "%s: %s = %g: its square is not a normal binary32 number", who, names[k], (double)tol[k]);
+    }
+    return PT_OK;
+}
+
+// the temporal call's buffers: the second G-buffer, two colour and two length planes, the history (80 bytes per pixel
+// with the first G-buffer)
+static int ensure_temporal(void) {
+    if (R.tp_ready) return PT_OK;
+    const size_t n = (size_t)R.npix;
+    if (!R.gb_alt) HIPCHK(hipMalloc((void **)&R.gb_alt, n * 2 * sizeof(float4)));
+    for (int k = 0; k < 2; ++k) {
+        if (!R.tp_c[k]) HIPCHK(hipMalloc((void **)&R.tp_c[k], n * 3 * sizeof(float)));
+        if (!R.tp_n[k]) HIPCHK(hipMalloc((void **)&R.tp_n[k], n * sizeof(float)));
+    }
+    if (!R.tp_hc) HIPCHK(hipMalloc((void **)&R.tp_hc, n * 3 * sizeof(float)));
+    if (!R.tp_hn) HIPCHK(hipMalloc((void **)&R.tp_hn, n * sizeof(float)));
+    HIPCHK(hipMemsetAsync(R.tp_hc, 0, n * 3 * sizeof(float), R.stream));
+    HIPCHK(hipMemsetAsync(R.tp_hn, 0, n * sizeof(float), R.stream));
+    R.tp_cur = false; R.tp_k = 0;
+    R.tp_ready = true;
+    return PT_OK;
+}
+
+int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_params *temporal, int iter, float *host_rgb,
+                        uint8_t *host_rgba) {
+    float sc2[10], sn2, sp2;
+    int rc = denoise_args_ok("pt_denoise_temporal", params, iter, sc2, sn2, sp2);
+    if (rc) return rc;
+    rc = temporal_args_ok("pt_denoise_temporal", temporal);
+    if (rc) return rc;
+    const int levels = params->levels;
+    const size_t n = (size_t)R.npix;
+    for (int k = 0; k < 2; ++k)
+        if (!R.dn_plane[k]) HIPCHK(hipMalloc((void **)&R.dn_plane[k], n * 3 * sizeof(float)));
+    if (host_rgba && !R.dn_rgba) HIPCHK(hipMalloc((void **)&R.dn_rgba, n * 4));
+    uint8_t *rgba = host_rgba ? R.dn_rgba : (uint8_t *)nullptr;
+    rc = ensure_temporal();
+    if (rc) return rc;
+    rc = ensure_gbuffer();                      // (a camera other than cur's: into the allocation cur does not refer to)
+    if (rc) return rc;
+    if (R.tp_cur && memcmp(&R.tp_cam, &R.cam, sizeof R.cam) != 0) {
+        rc = launch_reproject(R.tp_cam, R.tp_gb, R.tp_c[R.tp_k], R.tp_n[R.tp_k], *temporal);
+        if (rc) return rc;
+        R.tp_k ^= 1;                            // the planes the history was read from stay whole until the next camera change
+    }
+    float *c0 = R.tp_c[R.tp_k];
+    rc = launch_blend((float)iter, c0, R.tp_n[R.tp_k], levels == 0 ? rgba : (uint8_t *)nullptr);
+    if (rc) return rc;
+    R.tp_cur = true; R.tp_cam = R.cam; R.tp_gb = R.gb_mem;
+    int out = 0;
+    for (int l = 0; l < levels; ++l) {
+        out = l & 1;
+        rc = launch_atrous(l, 1.0f, sc2[l], sn2, sp2, l == levels - 1 ? rgba : (uint8_t *)nullptr, c0);
+        if (rc) return rc;
+    }
+    R.dn_result = levels == 0 ? c0 : R.dn_plane[out];
+    if (host_rgb) HIPCHK(hipMemcpyAsync(host_rgb, R.dn_result, n * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (host_rgba) HIPCHK(hipMemcpyAsync(host_rgba, R.dn_rgba, n * 4, hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_history(float *rgb, float *length) {
+    int rc = denoise_session_ok("pt_history");
+    if (rc) return rc;
+    if (!R.tp_ready) return fail(PT_ERR_INVALID, "pt_history: no pt_denoise_temporal call since pt_init");
+    const size_t n = (size_t)R.npix;
+    if (rgb) HIPCHK(hipMemcpyAsync(rgb, R.tp_hc, n * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (length) HIPCHK(hipMemcpyAsync(length, R.tp_hn, n * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_history_reset(void) {
+    int rc = denoise_session_ok("pt_history_reset");
+    if (rc) return rc;
+    if (!R.tp_ready) return PT_OK;              // nothing to forget
+    const size_t n = (size_t)R.npix;
+    HIPCHK(hipMemsetAsync(R.tp_hc, 0, n * 3 * sizeof(float), R.stream));
+    HIPCHK(hipMemsetAsync(R.tp_hn, 0, n * sizeof(float), R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    R.tp_cur = false; R.tp_gb = nullptr;
+    return PT_OK;
+}
 
 // diagnostics (ptdbg_denoise_times, not in include/ptmi355.h): device times of the filter's launches, HIP events on the
 // session's stream.  After one pt_denoise(params, iter) as warm-up, `reps` rounds of: k_gbuffer (forced), every level of
@@ -173,6 +310,68 @@ int denoise_times(const pt_denoise_params *params, int iter, int reps, float *ms
     rc = run();
     cleanup();
     return rc;
+}
+
+// diagnostics (ptdbg_temporal_times, not in include/ptmi355.h): device times of the temporal call's launches, HIP events on
+// the session's stream.  Called where a temporal call would reproject (a record of another camera exists): after one
+// warm-up round, `reps` rounds of k_reproject, k_temporal_blend, level 0 from the blended plane (k_atrous<false>, step 1),
+// level 0 from the running sum (k_atrous<true>, what pt_denoise runs), level 1 (k_atrous<false>, step 2) and
+// device-to-device copies of the bytes the two new kernels move (96 and 44 per pixel).  ms[rep * 7 + k] in that order.
+// Every launch writes what the pt_denoise_temporal call at the end writes again: the state afterwards is that call's.
+int temporal_times(const pt_denoise_params *params, const pt_temporal_params *temporal, int iter, int reps, float *ms) {
+    float sc2[10], sn2, sp2;
+    int rc = denoise_args_ok("ptdbg_temporal_times", params, iter, sc2, sn2, sp2);
+    if (rc) return rc;
+    rc = temporal_args_ok("ptdbg_temporal_times", temporal);
+    if (rc) return rc;
+    if (reps < 1 || !ms || params->levels < 2) return fail(PT_ERR_INVALID, "ptdbg_temporal_times: reps >= 1, levels >= 2 and a buffer");
+    if (!R.tp_ready || !R.tp_cur || memcmp(&R.tp_cam, &R.cam, sizeof R.cam) == 0)
+        return fail(PT_ERR_INVALID, "ptdbg_temporal_times: needs the record of a temporal call at another camera");
+    constexpr int items = 7;
+    const size_t n = (size_t)R.npix;
+    for (int k = 0; k < 2; ++k)
+        if (!R.dn_plane[k]) HIPCHK(hipMalloc((void **)&R.dn_plane[k], n * 3 * sizeof(float)));
+    rc = ensure_gbuffer();
+    if (rc) return rc;
+    const size_t copy_bytes[2] = {n * 96, n * 44};
+    void *src = nullptr, *dst = nullptr;
+    std::vector<hipEvent_t> ev((size_t)2 * items, nullptr);
+    auto cleanup = [&] {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (src) (void)hipFree(src);
+        if (dst) (void)hipFree(dst);
+    };
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc(&src, copy_bytes[0]));
+        HIPCHK(hipMalloc(&dst, copy_bytes[0]));
+        HIPCHK(hipMemsetAsync(src, 0, copy_bytes[0], R.stream));
+        for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+        float *c0 = R.tp_c[R.tp_k ^ 1], *n0 = R.tp_n[R.tp_k ^ 1];
+        for (int rep = -1; rep < reps; ++rep) {
+            int r = PT_OK;
+            for (int k = 0; k < items && r == PT_OK; ++k) {
+                HIPCHK(hipEventRecord(ev[2 * k], R.stream));
+                switch (k) {
+                case 0: r = launch_reproject(R.tp_cam, R.tp_gb, R.tp_c[R.tp_k], R.tp_n[R.tp_k], *temporal); break;
+                case 1: r = launch_blend((float)iter, c0, n0, nullptr); break;
+                case 2: r = launch_atrous(0, 1.0f, sc2[0], sn2, sp2, nullptr, c0); break;
+                case 3: r = launch_atrous(0, (float)iter, sc2[0], sn2, sp2, nullptr); break;
+                case 4: r = launch_atrous(1, 1.0f, sc2[1], sn2, sp2, nullptr); break;
+                default: HIPCHK(hipMemcpyAsync(dst, src, copy_bytes[k - 5], hipMemcpyDeviceToDevice, R.stream)); break;
+                }
+                HIPCHK(hipEventRecord(ev[2 * k + 1], R.stream));
+            }
+            if (r) return r;
+            HIPCHK(hipStreamSynchronize(R.stream));
+            if (rep < 0) continue;
+            for (int k = 0; k < items; ++k) HIPCHK(hipEventElapsedTime(&ms[(size_t)rep * items + k], ev[2 * k], ev[2 * k + 1]));
+        }
+        return PT_OK;
+    };
+    rc = run();
+    cleanup();
+    if (rc) return rc;
+    return one::pt_denoise_temporal(params, temporal, iter, nullptr, nullptr);
 }
 
 }  // namespace one

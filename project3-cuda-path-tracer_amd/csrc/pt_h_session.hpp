@@ -215,6 +215,18 @@ struct Renderer {
     uint8_t *dn_rgba = nullptr;
     float *dn_result = nullptr;
     uint64_t dn_launches[3] = {0, 0, 0};   // k_gbuffer / k_atrous / k_denoise_mean launches since pt_init (ptdbg_denoise)
+    // pt_denoise_temporal (pt_h_denoise.hpp), allocated by the first temporal call.  `cur` = what the
+    // last temporal call saw: its camera, its G-buffer (tp_gb: gb_mem or gb_alt -- when the camera changes while cur refers
+    // to gb_mem, ensure_gbuffer swaps the two allocations instead of overwriting it), the blended colour tp_c[tp_k] and its
+    // sample count tp_n[tp_k]; the other pair is what the next camera change blends into.  tp_hc / tp_hn: the history in the
+    // grid of cur's camera, all zero whenever there is no cur.
+    float4 *gb_alt = nullptr, *tp_gb = nullptr;
+    bool tp_ready = false, tp_cur = false;
+    pt_camera tp_cam{};
+    float *tp_c[2] = {nullptr, nullptr}, *tp_n[2] = {nullptr, nullptr};
+    int tp_k = 0;
+    float *tp_hc = nullptr, *tp_hn = nullptr;
+    uint64_t tp_launches[2] = {0, 0};      // k_reproject / k_temporal_blend launches since pt_init (ptdbg_temporal)
     void *scratch = nullptr;      // export / import staging
     size_t scratch_bytes = 0;
     // stepping state

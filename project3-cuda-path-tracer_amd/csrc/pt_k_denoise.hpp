@@ -160,4 +160,100 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_mean(const float *__restrict_
     if (rgba) reinterpret_cast<uchar4 *>(rgba)[i] = tonemap_pixel(r, g, b, 1);
 }
 
+// ---- history across camera moves (pt_denoise_temporal) -------------------------------------------
+// Reprojection: for pixel P of the NEW camera's grid (its G-buffer gA / gB), the pixel Q of the OLD camera `A` that saw the
+// same surface point -- the inverse of generateRayFromCamera, nearest pixel -- and, when Q's first hit is that point (same
+// material, position within ptol * t, normal within ntol: ntol2 = ntol * ntol), the old view's colour and sample count
+// (capped) as P's history; Hc = Hn = 0 otherwise.  Specular first hits carry none (what they show depends on the view):
+// the material's hasReflective / hasRefractive words of the scene's staged records.  One lane per pixel, a wave = 64
+// consecutive pixels of a row (k_atrous's layout): the own records are two contiguous 1-KiB requests, the gather at Q is
+// 32 + 12 + 4 bytes per lane, issued together before any of the tests reads them.  Neighbouring lanes land on neighbouring
+// Q wherever the surface is smooth.  Every Q is inside the old grid by the test on fx / fy; a material index outside the
+// table reads nothing.
+__global__ __launch_bounds__(BLOCK) void k_reproject(const float4 *__restrict__ gA, const float4 *__restrict__ gB,
+                                                     const float4 *__restrict__ oA, const float4 *__restrict__ oB,
+                                                     const float *__restrict__ oC, const float *__restrict__ oN,
+                                                     const float *__restrict__ mats, int nmats, pt_camera A,
+                                                     float *__restrict__ Hc, float *__restrict__ Hn, int W, int H, float cap,
+                                                     float ptol, float ntol2) {
+    const int x = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63);
+    const int y = (int)blockIdx.y * WAVES + (int)(threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t P = (size_t)y * (size_t)W + (size_t)x;
+    const float4 n = gA[P], p = gB[P];
+    const int mat = __float_as_int(p.w);
+    float hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f;
+    bool ok = mat >= 0 && mat < nmats;
+    if (ok) ok = mats[(size_t)mat * ptd::MAT_WORDS + 6] == 0.0f && mats[(size_t)mat * ptd::MAT_WORDS + 7] == 0.0f;
+    if (ok) {
+        const float vx = p.x - A.position.x, vy = p.y - A.position.y, vz = p.z - A.position.z;
+        const float z = vx * A.view.x + vy * A.view.y + vz * A.view.z;
+        if (z > 0.0f) {
+            const float xs = (float)W * 0.5f - (vx * A.right.x + vy * A.right.y + vz * A.right.z) / (z * A.pixelLength[0]);
+            const float ys = (float)H * 0.5f - (vx * A.up.x + vy * A.up.y + vz * A.up.z) / (z * A.pixelLength[1]);
+            const float fx = floorf(xs + 0.5f), fy = floorf(ys + 0.5f);
+            if (fx >= 0.0f && fx < (float)W && fy >= 0.0f && fy < (float)H) {          // (false on NaN)
+                const size_t Q = (size_t)((int)fy * W + (int)fx);
+                const float4 qn = oA[Q], qp = oB[Q];
+                const float qr = oC[3 * Q + 0], qg = oC[3 * Q + 1], qb = oC[3 * Q + 2], qlen = oN[Q];
+                const float lim = ptol * n.w;
+                if (__float_as_int(qp.w) == mat && dist2(qp.x, qp.y, qp.z, p.x, p.y, p.z) <= lim * lim &&
+                    dist2(qn.x, qn.y, qn.z, n.x, n.y, n.z) <= ntol2) {
+                    hr = qr; hg = qg; hb = qb;
+                    hn = fminf(qlen, cap);
+                }
+            }
+        }
+    }
+    Hc[3 * P + 0] = hr; Hc[3 * P + 1] = hg; Hc[3 * P + 2] = hb;
+    Hn[P] = hn;
+}
+
+// The blend: c0 = (sum + Hc * Hn) / (div + Hn) per channel, N = div + Hn (div = (float)iter) -- with Hn = 0 the mean
+// pt_denoise filters.  Streaming: a lane takes four consecutive pixels, 48 bytes of each packed-float3 plane as three
+// 16-byte accesses and the lengths as one (VEC: every plane is 16-byte aligned, which the library's own allocations are;
+// a caller's accumulation buffer may not be); the pixels after the last whole group of four go one per lane.
+// `rgba` (levels = 0, optional): tonemap_pixel of c0 with divisor 1.
+__device__ __forceinline__ float blend1(float s, float hc, float hn, float den) { return (s + hc * hn) / den; }
+template <bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_temporal_blend(const float *__restrict__ sum, const float *__restrict__ Hc,
+                                                          const float *__restrict__ Hn, float *__restrict__ Cout,
+                                                          float *__restrict__ Nout, uint8_t *__restrict__ rgba, uint32_t npix,
+                                                          float div) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t groups = VEC ? npix / 4 : 0;
+    if (VEC && i < groups) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(sum) + 3 * (size_t)i;
+        const float4 *h4 = reinterpret_cast<const float4 *>(Hc) + 3 * (size_t)i;
+        const float4 s0 = s4[0], s1 = s4[1], s2 = s4[2], h0 = h4[0], h1 = h4[1], h2 = h4[2];
+        const float4 l = reinterpret_cast<const float4 *>(Hn)[i];
+        const float4 d = make_float4(div + l.x, div + l.y, div + l.z, div + l.w);
+        // floats 0..11 of the group: pixel 0 = 0 1 2, pixel 1 = 3 4 5, pixel 2 = 6 7 8, pixel 3 = 9 10 11
+        const float4 c0 = make_float4(blend1(s0.x, h0.x, l.x, d.x), blend1(s0.y, h0.y, l.x, d.x), blend1(s0.z, h0.z, l.x, d.x),
+                                      blend1(s0.w, h0.w, l.y, d.y));
+        const float4 c1 = make_float4(blend1(s1.x, h1.x, l.y, d.y), blend1(s1.y, h1.y, l.y, d.y), blend1(s1.z, h1.z, l.z, d.z),
+                                      blend1(s1.w, h1.w, l.z, d.z));
+        const float4 c2 = make_float4(blend1(s2.x, h2.x, l.z, d.z), blend1(s2.y, h2.y, l.w, d.w), blend1(s2.z, h2.z, l.w, d.w),
+                                      blend1(s2.w, h2.w, l.w, d.w));
+        float4 *o4 = reinterpret_cast<float4 *>(Cout) + 3 * (size_t)i;
+        o4[0] = c0; o4[1] = c1; o4[2] = c2;
+        reinterpret_cast<float4 *>(Nout)[i] = d;
+        if (rgba) {
+            uchar4 *px = reinterpret_cast<uchar4 *>(rgba) + 4 * (size_t)i;
+            px[0] = tonemap_pixel(c0.x, c0.y, c0.z, 1); px[1] = tonemap_pixel(c0.w, c1.x, c1.y, 1);
+            px[2] = tonemap_pixel(c1.z, c1.w, c2.x, 1); px[3] = tonemap_pixel(c2.y, c2.z, c2.w, 1);
+        }
+        return;
+    }
+    // one pixel per lane: everything (not VEC), or the npix % 4 pixels after the groups (the lanes right behind them)
+    const uint32_t P = VEC ? groups * 4 + (i - groups) : i;
+    if (P >= npix) return;
+    const float l = Hn[P], d = div + l;
+    const float r = blend1(sum[3 * (size_t)P + 0], Hc[3 * (size_t)P + 0], l, d), g = blend1(sum[3 * (size_t)P + 1], Hc[3 * (size_t)P + 1], l, d),
+                b = blend1(sum[3 * (size_t)P + 2], Hc[3 * (size_t)P + 2], l, d);
+    Cout[3 * (size_t)P + 0] = r; Cout[3 * (size_t)P + 1] = g; Cout[3 * (size_t)P + 2] = b;
+    Nout[P] = d;
+    if (rgba) reinterpret_cast<uchar4 *>(rgba)[P] = tonemap_pixel(r, g, b, 1);
+}
+
 }  // namespace

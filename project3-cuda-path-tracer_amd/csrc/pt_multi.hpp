@@ -902,6 +902,18 @@ int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8
     return one::pt_denoise(params, iter, host_rgb, host_rgba);
 }
 float *pt_denoised_device_image(void) { return G.live ? nullptr : one::pt_denoised_device_image(); }
+int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_params *temporal, int iter, float *host_rgb, uint8_t *host_rgba) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_denoise_temporal: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_denoise_temporal(params, temporal, iter, host_rgb, host_rgba);
+}
+int pt_history(float *rgb, float *length) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_history: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
+    return one::pt_history(rgb, length);
+}
+int pt_history_reset(void) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_history_reset: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
+    return one::pt_history_reset();
+}
 
 int pt_tonemap(uint8_t *host_rgba, int iter) {
     if (!G.live) return one::pt_tonemap(host_rgba, iter);

@@ -134,6 +134,20 @@ extern "C" int ptdbg_denoise_times(const pt_denoise_params *params, int iter, in
     return one::denoise_times(params, iter, reps, ms);
 }
 
+// diagnostics (not in include/ptmi355.h): launches of k_reproject / k_temporal_blend since pt_init (single-device sessions)
+extern "C" int ptdbg_temporal(unsigned long long out[2]) {
+    if (!g_single.live) return -1;
+    for (int k = 0; k < 2; ++k) out[k] = g_single.tp_launches[k];
+    return 0;
+}
+
+// diagnostics (not in include/ptmi355.h): device times of the temporal call's launches beside a level of the filter and copies of
+// the bytes they move (pt_h_denoise.hpp: temporal_times; profiles/denoise/measure_temporal.py).  Single-device sessions.
+extern "C" int ptdbg_temporal_times(const pt_denoise_params *params, const pt_temporal_params *temporal, int iter, int reps, float *ms) {
+    if (G.live) return fail(PT_ERR_INVALID, "ptdbg_temporal_times: single-device sessions");
+    return one::temporal_times(params, temporal, iter, reps, ms);
+}
+
 #ifdef PT_WAVE_TIMES
 // diagnostic build only (not in include/ptmi355.h): per-wave start / end ticks and hardware ids of k_bounce's last launches
 extern "C" int ptdbg_wave_times(unsigned long long *times /* [8][8192][2] */, uint32_t *hw /* [8][8192] */) {

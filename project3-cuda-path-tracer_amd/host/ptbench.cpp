@@ -5,11 +5,17 @@
 //   ptbench SCENEFILE.txt [--iters N] [--batch B] [--out BASENAME] [--sort] [--no-compact]
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
-//           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP]
+//           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
 //
 // --denoise LEVELS,SC,SN,SP: after the last iteration, the edge-avoiding A-trous filter (pt_denoise: LEVELS levels, sigmas
 // of colour / normal / position) of the accumulated image; BASE.<N>samp.denoised.png is written beside the image through the
 // same saveImage pipeline (clamp, x255, truncate -- on the denoised mean), and one line reports the filter's time.
+//
+// --move DX,DY,DZ,ITERS (needs --denoise): what an interactive host does when the camera moves.  After the render and its
+// denoised picture: one pt_denoise_temporal on the finished view (it becomes the history), position and lookAt translated by
+// (DX, DY, DZ), pt_set_camera, pt_clear_image, ITERS iterations, and three pictures of the moved view: BASE.moved.<ITERS>samp.png
+// (the mean), ....denoised.png (pt_denoise) and ....temporal.png (pt_denoise_temporal: the history blended in, the same filter);
+// one line reports the times.  --temporal CAP,TOL_P,TOL_N: max_history and the position / normal tolerances (default 64,0.1,0.1).
 //
 // --batch B: iterations per launch sequence (default: up to 64 and ~40 M paths, as the shim sizes its windows; 1 = one
 // pathtrace() per iteration); every batch but the last is enqueued without waiting, so consecutive batches overlap on the
@@ -51,7 +57,8 @@ int main(int argc, char **argv) {
         printf("Usage: %s SCENEFILE.txt [--iters N] [--batch B] [--out BASE] [--sort] [--no-compact] [--cache-first] "
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
-               "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP]\n", argv[0]);
+               "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
+               "[--temporal CAP,TOL_P,TOL_N]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -60,6 +67,10 @@ int main(int argc, char **argv) {
     int warmup = 64;
     bool denoise = false;
     pt_denoise_params dn = {0, 0.0f, 0.0f, 0.0f};
+    bool move = false;
+    float move_by[3] = {0.0f, 0.0f, 0.0f};
+    int move_iters = 0;
+    pt_temporal_params tp = {64, 0.1f, 0.1f};
     std::string resume;
     int start = -1;
     float lens_radius = 0.0f, focal_distance = 0.0f;
@@ -98,6 +109,21 @@ int main(int argc, char **argv) {
             }
             dn.levels = lv; denoise = true;
         }
+        else if (a == "--move" && i + 1 < argc) {
+            if (sscanf(argv[++i], "%f,%f,%f,%d", &move_by[0], &move_by[1], &move_by[2], &move_iters) != 4 || move_iters < 1) {
+                fprintf(stderr, "--move wants DX,DY,DZ,ITERS with ITERS >= 1\n");
+                return 1;
+            }
+            move = true;
+        }
+        else if (a == "--temporal" && i + 1 < argc) {
+            int cap = 0;
+            if (sscanf(argv[++i], "%d,%f,%f", &cap, &tp.position_tolerance, &tp.normal_tolerance) != 3) {
+                fprintf(stderr, "--temporal wants MAX_HISTORY,POSITION_TOLERANCE,NORMAL_TOLERANCE\n");
+                return 1;
+            }
+            tp.max_history = cap;
+        }
         else if (a == "--strip-rows" && i + 1 < argc) strip_rows = atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) { devices.clear(); for (int k = 0, n = atoi(argv[++i]); k < n; ++k) devices.push_back(k); }
         else if (a == "--devices" && i + 1 < argc) {
@@ -109,6 +135,7 @@ int main(int argc, char **argv) {
     pth_scene *sc = pth_load_scene(argv[1]);
     if (!sc) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     if (iters < 0) iters = sc->iterations;
+    if (move && !denoise) { fprintf(stderr, "--move needs --denoise (the filter its pictures go through)\n"); return 1; }
     if (per_call) {
         flags |= PT_PIN_IMAGE | PT_HOST_SPARSE | (lookahead ? PT_LOOKAHEAD : 0u);
         if (!resume.empty()) { fprintf(stderr, "--per-call does not combine with --resume\n"); return 1; }
@@ -227,6 +254,51 @@ int main(int argc, char **argv) {
         snprintf(name, sizeof name, "%s.%dsamp.sum.pfm", out.c_str(), iteration);
         if (pth_write_pfm(name, image.data(), W, H, 1.0f) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
         printf("Saved %s.\n", name);
+    }
+    if (move) {
+        std::vector<float> mean((size_t)W * H * 3);
+        const auto m0 = std::chrono::steady_clock::now();
+        if (pt_denoise_temporal(&dn, &tp, iteration, NULL, NULL) != PT_OK) { fprintf(stderr, "pt_denoise_temporal: %s\n", pt_last_error()); return 1; }
+        const auto m1 = std::chrono::steady_clock::now();
+        pt_camera cam = sc->camera;
+        cam.position.x += move_by[0]; cam.position.y += move_by[1]; cam.position.z += move_by[2];
+        cam.lookAt.x += move_by[0]; cam.lookAt.y += move_by[1]; cam.lookAt.z += move_by[2];
+        if (pt_set_camera(&cam, sc->trace_depth) != PT_OK) { fprintf(stderr, "pt_set_camera: %s\n", pt_last_error()); return 1; }
+        if (pt_clear_image() != PT_OK) { fprintf(stderr, "pt_clear_image: %s\n", pt_last_error()); return 1; }
+        const auto m2 = std::chrono::steady_clock::now();
+        for (int it = 0; it < move_iters;) {
+            const int n = (move_iters - it < batch) ? move_iters - it : batch;
+            const int rc = (n == 1) ? pt_trace(NULL, 0, it + 1, NULL) : pt_trace_batch(it + 1, n, NULL);
+            if (rc != PT_OK) { fprintf(stderr, "pathtrace: %s\n", pt_last_error()); return 1; }
+            it += n;
+        }
+        if (pt_get_image(image.data()) != PT_OK) { fprintf(stderr, "pt_get_image: %s\n", pt_last_error()); return 1; }
+        const auto m3 = std::chrono::steady_clock::now();
+        snprintf(name, sizeof name, "%s.moved.%dsamp.png", out.c_str(), move_iters);
+        pth_image_to_rgb8(image.data(), W, H, (float)move_iters, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+        const auto m4 = std::chrono::steady_clock::now();
+        if (pt_denoise(&dn, move_iters, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise: %s\n", pt_last_error()); return 1; }
+        const auto m5 = std::chrono::steady_clock::now();
+        snprintf(name, sizeof name, "%s.moved.%dsamp.denoised.png", out.c_str(), move_iters);
+        pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+        const auto m6 = std::chrono::steady_clock::now();
+        if (pt_denoise_temporal(&dn, &tp, move_iters, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise_temporal: %s\n", pt_last_error()); return 1; }
+        const auto m7 = std::chrono::steady_clock::now();
+        snprintf(name, sizeof name, "%s.moved.%dsamp.temporal.png", out.c_str(), move_iters);
+        pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+            return std::chrono::duration<double, std::milli>(b - a).count();
+        };
+        printf("move (%g, %g, %g), %d iterations, max_history %d, tolerances %g / %g: %.3f ms the temporal call on the finished view, "
+               "%.3f ms the %d iterations of the moved view, %.3f ms pt_denoise with its G-buffer, %.3f ms pt_denoise_temporal with the reprojection "
+               "(both with the copy of the result)\n", move_by[0], move_by[1], move_by[2], move_iters, tp.max_history, tp.position_tolerance,
+               tp.normal_tolerance, ms(m0, m1), ms(m2, m3), move_iters, ms(m4, m5), ms(m6, m7));
     }
     pt_free();
     pth_free_scene(sc);
