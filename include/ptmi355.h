@@ -442,6 +442,20 @@ int pt_probe_rng(const uint32_t *seeds, int n, int draws, uint32_t *state, float
 int pt_probe_sincos(const float *x, uint32_t first_bits, uint32_t n, float *s, float *c, uint64_t sum[2]);
 int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, float *dirs);
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]);
+/* pt_probe_shade_scatter: one pass of the loop body's shader (pathtrace.cu:224-266 with scatterRay completed)
+ * on n caller-supplied (path, intersection) pairs, through the kernels' own shade_scatter (csrc/pt_device.hpp): mirror, Fresnel
+ * dielectric, total internal reflection, diffuse, emitter, miss and the last bounce, one lane per pair.  paths (in / out), isects,
+ * outside (n bytes: the winning test's `outside`; NULL = 1 for every path) and materials are host arrays.  Per path: remainingBounces
+ * <= 0 -> untouched; t > 0 on an emitter -> color *= material.color * emittance, remainingBounces = 0; t > 0 otherwise -> scattered
+ * with the engine keyed by (iter, pixelIndex, depth), remainingBounces -= 1, and color = 0 when that reaches 0; t <= 0 -> color = 0,
+ * remainingBounces = 0.  A path that ends keeps the ray it came with (the oracle's pto_shade_scatter scatters before it zeroes a
+ * last-bounce path: compare `ray` where remainingBounces > 0 afterwards, everything else for every path).  deferred = 0: the call
+ * of the kernels that sample a diffuse direction at once; 1: the deferring kernels' call, followed by what the next bounce's load
+ * does with a pending direction (csrc/pt_k_bounce.hpp: tile_load) -- the same bytes.  Refused on the host, before anything is
+ * launched (PT_ERR_INVALID): n < 0 or above 2^26, a null array with n > 0, num_materials < 1, deferred outside {0, 1}, a record
+ * with t > 0 whose materialId is outside [0, num_materials).  n == 0 launches nothing. */
+int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                           const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred);
 /* pt_probe_tri_form: the every-triangle loop's first stage on the device, through the kernel's own code (csrc/pt_k_trisweep.hpp:
  * tri_ray_operands, tri_group_form), for ONE mesh of `count` triangles (records and frame as pt_tri_records makes them) and n rays
  * (origins, directions: n x 3 floats each; rays with |origin|_1 > origin_bound are `wild` as in the kernels).  Per ray (each output

@@ -162,6 +162,7 @@ def library():
             L.pt_probe_sincos.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_probe_hemisphere.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
             L.pt_probe_sqrt.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+            L.pt_probe_shade_scatter.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
             L.pt_probe_clock.argtypes = [C.c_int, C.POINTER(C.c_double)]
             L.pt_probe_tri_form.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_probe_own_surface_plan.argtypes = [C.c_uint64, C.c_int, C.c_int]
@@ -565,3 +566,17 @@ def probe_hemisphere(normals, seeds):
     out = np.zeros((len(sd), 3), dtype=np.float32)
     _chk(library().pt_probe_hemisphere(_p(nr), _p(sd), len(sd), _p(out)))
     return out
+
+
+def probe_shade_scatter(iter, depth, materials, paths, isects, outside=None, deferred=False):
+    """One pass of the loop body's shader on the device (include/ptmi355.h: pt_probe_shade_scatter) for (path, intersection)
+    pairs: the paths afterwards (PATH_DT; the arguments are not written).  outside: one byte per pair, None = 1 for all;
+    deferred: the deferring kernels' call, resolved as the next bounce's load resolves it (the same bytes)."""
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT)
+    p = np.array(paths, dtype=PATH_DT, copy=True, order="C").reshape(-1)
+    x = np.ascontiguousarray(isects, dtype=ISECT_DT).reshape(-1)
+    o = None if outside is None else np.ascontiguousarray(outside, dtype=np.uint8).reshape(-1)
+    if len(x) != len(p) or (o is not None and len(o) != len(p)):
+        raise PtError("probe_shade_scatter: %d paths, %d intersections, %s outside flags" % (len(p), len(x), "no" if o is None else len(o)))
+    _chk(library().pt_probe_shade_scatter(int(iter), int(depth), _p(m), len(m), _p(p), _p(x), _p(o), len(p), 1 if deferred else 0))
+    return p

@@ -82,8 +82,20 @@ void pt_free(void) {
 }
 
 
+// materials -> the kernels' MAT_WORDS records (pt_device.hpp), `rec` zeroed by the caller: pt_init's scene upload and
+// pt_probe_shade_scatter's table
+static void pack_materials(const pt_material *materials, int count, float *rec) {
+    for (int i = 0; i < count; ++i) {
+        const pt_material &m = materials[i];
+        float *r = rec + (size_t)i * ptd::MAT_WORDS;
+        r[0] = m.color.x; r[1] = m.color.y; r[2] = m.color.z;
+        r[3] = m.specular.color.x; r[4] = m.specular.color.y; r[5] = m.specular.color.z;
+        r[6] = m.hasReflective; r[7] = m.hasRefractive; r[8] = m.indexOfRefraction; r[9] = m.emittance;
+    }
+}
+
 static int init_impl(const pt_scene_desc *d);
-int la_discard(int how);            // PT_LOOKAHEAD: forget the windows traced ahead (below, with pt_trace)
+int la_discard(int how);           // PT_LOOKAHEAD: forget the windows traced ahead (below, with pt_trace)
 enum { LA_STREAM = 0, LA_HOST = 1, LA_LATER = 2 };
 
 }  // namespace one
@@ -243,13 +255,7 @@ static int init_impl(const pt_scene_desc *d) {
         if (g.type == PT_TRIANGLE_MESH) memcpy(&r[ptd::G_INV + 6], &boff, 4);     // a mesh's matrices are never read
     }
     std::vector<float> mrec((size_t)d->num_materials * ptd::MAT_WORDS, 0.0f);
-    for (int i = 0; i < d->num_materials; ++i) {
-        const pt_material &m = d->materials[i];
-        float *r = mrec.data() + (size_t)i * ptd::MAT_WORDS;
-        r[0] = m.color.x; r[1] = m.color.y; r[2] = m.color.z;
-        r[3] = m.specular.color.x; r[4] = m.specular.color.y; r[5] = m.specular.color.z;
-        r[6] = m.hasReflective; r[7] = m.hasRefractive; r[8] = m.indexOfRefraction; r[9] = m.emittance;
-    }
+    pack_materials(d->materials, d->num_materials, mrec.data());
     std::vector<float> trec((size_t)std::max(1, d->num_triangles) * TRI_WORDS, 0.0f);
     for (int i = 0; i < d->num_triangles; ++i) {
         const pt_triangle &t = d->triangles[i];

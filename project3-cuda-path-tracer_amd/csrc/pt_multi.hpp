@@ -1028,6 +1028,10 @@ int pt_probe_sincos(const float *x, uint32_t first_bits, uint32_t n, float *s, f
     return one::pt_probe_sincos(x, first_bits, n, s, c, sum);
 }
 int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, float *dirs) { return one::pt_probe_hemisphere(normals, seeds, n, dirs); }
+int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                           const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
+    return one::pt_probe_shade_scatter(iter, depth, materials, num_materials, paths, isects, outside, n, deferred);
+}
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
 int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }
 int pt_probe_own_surface_plan(uint64_t paths, int ngeoms, int plain_fused) { return one::pt_probe_own_surface_plan(paths, ngeoms, plain_fused); }

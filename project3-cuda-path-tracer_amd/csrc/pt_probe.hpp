@@ -1,8 +1,9 @@
 // pt_probe.hpp -- known-answer probes of libptmi355.so (included by ptmi355.hip only): the device functions of
 // pt_device.hpp that restate third-party arithmetic the reference merely calls -- thrust's minstd_rand + u01
 // (pathtrace.cu:41-45, interactions.h:12-13), the sin / cos binding of interactions.h:40-41 and
-// calculateRandomDirectionInHemisphere (interactions.h:10-42) -- run on caller data, so that a test can hold them
-// against published constants and against the oracle one function at a time instead of through whole images.
+// calculateRandomDirectionInHemisphere (interactions.h:10-42) -- and this project's own completion of the empty scatterRay
+// (interactions.h:69-79: ptd::shade_scatter) run on caller data, so that a test can hold them against published constants,
+// the reference's glm vectors and the oracle one function at a time instead of through whole images.
 // No session needed: the probes run on the calling thread's current HIP device.
 #pragma once
 
@@ -55,6 +56,41 @@ __global__ void k_probe_hemisphere(const float *normals, const uint32_t *seeds, 
     uint32_t st = ptd::lcg_seed(seeds[i]);
     const f3 d = ptd::hemisphere(ptd::mk(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), st);
     dirs[3 * i] = d.x; dirs[3 * i + 1] = d.y; dirs[3 * i + 2] = d.z;
+}
+
+// one pass of the loop body's shader (pathtrace.cu:224-266 with scatterRay completed) through the kernels'
+// own ptd::shade_scatter: one lane per (path, intersection) pair, host structs as they are.  A path that ends keeps the ray it
+// came with.  defer != 0: the deferring kernels' call -- a diffuse survivor comes back with the hit normal for a direction and
+// draws it afterwards, as the next bounce's load does
+__global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
+                                                             const pt_shadeable_intersection *__restrict__ isects,
+                                                             const uint8_t *__restrict__ outside, int n, int defer) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    pt_path_segment p = paths[i];
+    if (p.remainingBounces <= 0) return;                            // (the oracle's compaction-off mode: untouched)
+    const pt_shadeable_intersection x = isects[i];
+    ptd::PathState ps;
+    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
+    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
+    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    bool deferred = false;
+    const bool alive = ptd::shade_scatter(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
+                                          outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                          defer != 0, &deferred);
+    if (deferred) {
+        // what the next bounce's load does with a pending direction (pt_k_bounce.hpp: tile_load<RESOLVE>, whose `depth - 1`
+        // is this bounce's depth): the same engine, the same sampler, on the normal the scatter left in the direction
+        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
+        ps.d = ptd::hemisphere(ps.d, rng);
+    }
+    pt_path_segment *q = paths + i;
+    if (alive) {
+        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
+        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
+    }
+    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
+    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
 }
 
 // the shader clock while whatever else is running runs: one wave counts its cycle counter (s_memtime) against the constant
@@ -217,6 +253,34 @@ int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, floa
     hipLaunchKernelGGL(k_probe_hemisphere, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_n, d_seeds, n, d_d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(dirs, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                           const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
+    // everything is refused here, before anything is launched: the kernel never indexes past the material table
+    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)))
+        return fail(PT_ERR_INVALID, "pt_probe_shade_scatter: bad argument");
+    for (int i = 0; i < n; ++i)
+        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
+            return fail(PT_ERR_INVALID, "pt_probe_shade_scatter: record %d hits material %d of %d", i, isects[i].materialId, num_materials);
+    if (n == 0) return PT_OK;
+    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
+    pack_materials(materials, num_materials, mrec.data());          // pt_init's own records
+    ProbeBufs b;
+    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
+    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
+    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
+    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
+    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside)) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_shade_scatter: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_shade_scatter, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
+                       d_outside, n, deferred);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
