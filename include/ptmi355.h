@@ -256,6 +256,33 @@ void pt_free(void);
 int pt_set_camera(const pt_camera *camera, int trace_depth);
 int pt_set_lens(float lens_radius, float focal_distance);   /* see pt_scene_desc */
 
+/* ---- environment lighting: a ray that leaves the scene reads a cube map ------------------------------------------------
+ * Without a map a path whose ray hits nothing ends with colour 0 (pathtrace.cu:262-264): only emitters give light.  With
+ * one it ends with colour = throughput * E(d) per component, d = the direction of the ray that missed exactly as it was
+ * traced.  E(d) is the NEAREST texel of a cube map of n x n texels per face (DESIGN.md section 6.16 has the complete
+ * specification; binary32, one rounding per operation, no FMA; tests/environment_model.py is its numpy form, and the
+ * device's result equals it bit for bit):
+ *   axis  = 0 if |d.x| >= |d.y| and |d.x| >= |d.z|, else 1 if |d.y| >= |d.z|, else 2;  m = |d[axis]|;  !(m > 0): E = 0
+ *   face  = 2 * axis + (d[axis] < 0);  (a, b) = the other two components in x, y, z order (no mirroring per face)
+ *   i     = min((int)((a / m * 0.5f + 0.5f) * (float)n), n - 1), j likewise from b;  texel (face * n + j) * n + i
+ * The "remainingBounces reaches 0 -> colour 0" rule is unchanged, and so are the G-buffer and the filters (a miss keeps
+ * t = -1; its pixel now carries colour in the running sum).
+ * pt_set_environment: texels = host array of 6 * n * n RGB float32 triples, index ((face * n + j) * n + i) * 3, copied to
+ * the device(s); texels == NULL or n == 0: no environment (the state after pt_init).  Session state: it survives
+ * pt_set_camera and pt_clear_image and ends with pt_free.  The call synchronises the session and discards the
+ * PT_LOOKAHEAD windows, as a camera change does; it does not touch the accumulation buffer (the host decides whether to
+ * pt_clear_image).  Non-finite texels propagate as in any multiplication.  Honoured by every pipeline -- batches,
+ * asynchronous batches, windows, the stepping interface, tiled sessions, sessions over several devices -- except
+ * PT_FAKE_SHADER (the reference as shipped), which ignores it.
+ * pt_get_environment: *n = the size set (0: none; nothing else is written then); the texels as they were given, when
+ * capacity_texels >= 6 * n * n (PT_ERR_INVALID otherwise, with *n set).
+ * PT_ERR_INVALID: before pt_init; n outside [0, 1024]; texels == NULL with n > 0. */
+int pt_set_environment(const float *texels, int n);
+int pt_get_environment(float *texels, int capacity_texels, int *n);
+/* host-only (no GPU): the texel index the specification assigns to each of `count` directions (dirs: count x 3 floats) in
+ * a map of n x n texels per face (n in [1, 1024]), -1 where it assigns none */
+int pt_environment_texel(const float *dirs, int count, int n, int32_t *index);
+
 /* pathtrace (pathtrace.cu:284-393): one iteration `iter` (1-based; RNG key and
  * tonemap divisor).  pbo_rgba: optional DEVICE pointer to W*H RGBA8 (the mapped
  * GL PBO in the reference), may be NULL.  host_image_sum: optional HOST buffer
@@ -456,6 +483,11 @@ int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]);
  * with t > 0 whose materialId is outside [0, num_materials).  n == 0 launches nothing. */
 int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
                            const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred);
+/* pt_probe_environment: the miss exit's lookup and multiply (pt_set_environment above) through the kernels' own device function, one
+ * lane per (direction, throughput) pair: colour[i] = throughput[i] * E(dirs[i]) per component (all count x 3 floats), +0 when n == 0.
+ * texels as for pt_set_environment.  PT_ERR_INVALID: count < 0, a null array with count > 0, n outside [0, 1024], texels == NULL
+ * with n > 0.  count == 0 launches nothing. */
+int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour);
 /* pt_probe_tri_form: the every-triangle loop's first stage on the device, through the kernel's own code (csrc/pt_k_trisweep.hpp:
  * tri_ray_operands, tri_group_form), for ONE mesh of `count` triangles (records and frame as pt_tri_records makes them) and n rays
  * (origins, directions: n x 3 floats each; rays with |origin|_1 > origin_bound are `wild` as in the kernels).  Per ray (each output

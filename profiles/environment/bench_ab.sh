@@ -1,0 +1,14 @@
+#!/bin/bash
+# DESIGN.md section 6.16, "cost to sessions without an environment": `python bench.py` (C2) of the parent commit and of this
+# one, alternating, three runs each on one box; then profiles/environment/bench_ab.py folds the six lines into bench_ab.json.
+#   profiles/environment/bench_ab.sh PARENT_TREE [OUT_DIR]      PARENT_TREE: a built checkout of the parent commit
+set -o pipefail
+PARENT=${1:?a built checkout of the parent commit}
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+OUT=${2:-$ROOT/profiles/environment}
+mkdir -p "$OUT"
+for i in 1 2 3; do
+  (cd "$PARENT" && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 | tail -1 > "$OUT/bench_parent_$i.json") || exit 1
+  (cd "$ROOT" && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 | tail -1 > "$OUT/bench_new_$i.json") || exit 1
+done
+python "$ROOT/profiles/environment/bench_ab.py" "$OUT"

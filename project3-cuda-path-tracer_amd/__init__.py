@@ -12,6 +12,7 @@ from .binding import (  # noqa: F401
     set_image, probe_rng, probe_sincos, probe_sincos_sums, probe_hemisphere, probe_shade_scatter, probe_sqrt, probe_clock, probe_tri_form, probe_own_surface_plan,
     gbuffer, denoise, denoised_device_ptr, DenoiseParams,
     denoise_temporal, history, history_reset, TemporalParams,
+    set_environment, get_environment, gradient_cubemap, environment_texel, probe_environment,
 )
 from .build import build  # noqa: F401
 from . import sharding  # noqa: F401,E402

@@ -171,6 +171,10 @@ def library():
             L.pt_denoised_device_image.restype = C.c_void_p
             L.pt_denoise_temporal.argtypes = [C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_int, C.c_void_p, C.c_void_p]
             L.pt_history.argtypes = [C.c_void_p, C.c_void_p]
+            L.pt_set_environment.argtypes = [C.c_void_p, C.c_int]
+            L.pt_get_environment.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+            L.pt_environment_texel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            L.pt_probe_environment.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -263,6 +267,84 @@ def set_lens(lens_radius, focal_distance):
 def set_camera(camera, trace_depth):
     cam = np.ascontiguousarray(camera, dtype=CAMERA_DT).reshape(1)
     _chk(library().pt_set_camera(_p(cam), trace_depth))
+
+
+def _cube_texels(texels):
+    """(texels as [6 * n * n, 3] float32, n) of a cube map given as [6, n, n, 3] or [6 * n * n, 3]."""
+    t = np.ascontiguousarray(texels, dtype=np.float32)
+    count = t.size // 3
+    n = int(round((count / 6.0) ** 0.5))
+    if t.size == 0 or t.size % 3 or 6 * n * n != count:
+        raise PtError("environment: %s is not 6 * n * n RGB texels" % (t.shape,))
+    return t.reshape(count, 3), n
+
+
+def set_environment(texels):
+    """The cube map a ray that leaves the scene reads (include/ptmi355.h: pt_set_environment): [6, n, n, 3] float32, indexed
+    [face, j, i]; None: no environment, a miss ends with colour 0 again.  The running sum is not touched."""
+    if texels is None:
+        _chk(library().pt_set_environment(None, 0))
+        return
+    t, n = _cube_texels(texels)
+    _chk(library().pt_set_environment(_p(t), n))
+
+
+def get_environment():
+    """The session's cube map as it was set, [6, n, n, 3] float32, or None."""
+    n = C.c_int(0)
+    L = library()
+    rc = L.pt_get_environment(None, 0, C.byref(n))              # the size: PT_OK with n = 0 when none is set
+    if n.value == 0:
+        _chk(rc)
+        return None
+    out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
+    _chk(L.pt_get_environment(_p(out), 6 * n.value * n.value, C.byref(n)))
+    return out
+
+
+def gradient_cubemap(n, zenith, horizon, ground):
+    """A sky for set_environment, [6, n, n, 3] float32: horizon + (zenith - horizon) * max(y, 0) + (ground - horizon) * max(-y, 0)
+    at the texel centres, y = the unit direction's second component.  Host arithmetic in float64, rounded to float32 once: the
+    texels are input to the lookup's specification, not part of it."""
+    n = int(n)
+    if n < 1 or n > 1024:
+        raise PtError("gradient_cubemap: n = %d outside [1, 1024]" % n)
+    z, h, g = (np.asarray(c, dtype=np.float64).reshape(3) for c in (zenith, horizon, ground))
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n * 2.0 - 1.0        # texel centres in [-1, 1]
+    b, a = np.meshgrid(c, c, indexing="ij")                           # [j, i]: b from j, a from i
+    out = np.zeros((6, n, n, 3), dtype=np.float32)
+    for face in range(6):
+        axis, major = face >> 1, (-1.0 if face & 1 else 1.0)
+        comp = [None, None, None]
+        comp[axis] = np.full_like(a, major)
+        rest = [k for k in range(3) if k != axis]
+        comp[rest[0]], comp[rest[1]] = a, b
+        y = comp[1] / np.sqrt(comp[0] * comp[0] + comp[1] * comp[1] + comp[2] * comp[2])
+        up, down = np.maximum(y, 0.0)[..., None], np.maximum(-y, 0.0)[..., None]
+        out[face] = (h + (z - h) * up + (g - h) * down).astype(np.float32)
+    return out
+
+
+def environment_texel(dirs, n):
+    """Host-only: the texel index [count] int32 the specification assigns to each direction of a map of n x n texels per face
+    (include/ptmi355.h: pt_environment_texel), -1 where it assigns none."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(d), dtype=np.int32)
+    _chk(library().pt_environment_texel(_p(d), len(d), int(n), _p(out)))
+    return out
+
+
+def probe_environment(texels, dirs, throughput):
+    """The miss exit's lookup and multiply on the device (include/ptmi355.h: pt_probe_environment): throughput * E(dirs) per
+    component, [count, 3] float32.  texels: a cube map as for set_environment, or None (no map: +0)."""
+    t, n = (None, 0) if texels is None else _cube_texels(texels)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(throughput, dtype=np.float32).reshape(-1, 3)
+    if len(d) != len(c):
+        raise PtError("probe_environment: %d directions, %d throughputs" % (len(d), len(c)))
+    out = np.zeros((len(d), 3), dtype=np.float32)
+    _chk(library().pt_probe_environment(_p(t), n, _p(d), _p(c), len(d), _p(out)))
+    return out
 
 
 def trace_batch(iter0, count, host_image=None):

@@ -500,11 +500,46 @@ struct PathState {
     f3 o, d, c;
 };
 
+// Environment lighting: the texel of an n x n-per-face cube map that direction d reads, nearest
+// texel, no mirroring per face; -1 for a direction without one (zero, or NaN on its major axis).  Host and device: the
+// divides are correctly rounded, nothing contracts.  u, v lie in [-1, 1], so the products are >= 0; the fmax only turns
+// the NaN of a direction with two infinite (or a NaN minor) component into texel coordinate 0 instead of an index
+// outside the map.
+__host__ __device__ __forceinline__ int env_texel(float dx, float dy, float dz, int n) {
+    const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
+    int axis;
+    float m, major, a, b;
+    if (ax >= ay && ax >= az) { axis = 0; m = ax; major = dx; a = dy; b = dz; }
+    else if (ay >= az)        { axis = 1; m = ay; major = dy; a = dx; b = dz; }
+    else                      { axis = 2; m = az; major = dz; a = dx; b = dy; }
+    if (!(m > 0.0f)) return -1;
+    const int face = 2 * axis + (major < 0.0f ? 1 : 0);
+    const float u = a / m, v = b / m;
+    const float fn = (float)n;
+    const int i = (int)__builtin_fmaxf((u * 0.5f + 0.5f) * fn, 0.0f), j = (int)__builtin_fmaxf((v * 0.5f + 0.5f) * fn, 0.0f);
+    return (face * n + (j < n - 1 ? j : n - 1)) * n + (i < n - 1 ? i : n - 1);
+}
+// E(d): the device keeps a texel as 16 B {r, g, b, 0} -- one load
+PTD f3 env_radiance(const float4 *texels, int n, f3 d) {
+    const int k = env_texel(d.x, d.y, d.z, n);
+    if (k < 0) return mk(0.0f, 0.0f, 0.0f);
+    const float4 e = texels[k];
+    return mk(e.x, e.y, e.z);
+}
+// the colour a path that missed ends with: throughput * E(d), or +0 in a session without a map (n == 0)
+PTD f3 miss_colour(f3 throughput, f3 d, const float4 *texels, int n) {
+    if (n == 0) return mk(0.0f, 0.0f, 0.0f);
+    return mul(throughput, env_radiance(texels, n, d));
+}
+
 // returns true when the path stays alive; on false `ps.c` is the final colour.  `defer_diffuse`: a diffuse survivor
 // keeps the hit normal in `ps.d` and sets `*deferred` -- hemisphere(n, seeded_engine(iter, pixel, depth)) is left to
-// whoever reads the path next (the next bounce's load, or the export); everything else is as without it
+// whoever reads the path next (the next bounce's load, or the export); everything else is as without it.
+// `missed` (the pipelines that honour the environment): a path that misses sets it and keeps its throughput in `ps.c` and
+// its direction in `ps.d` -- the caller ends it with miss_colour, where and when the gather suits it
 PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, const float *mats,
-                       int iter, int pixel, int depth, bool last_bounce, bool defer_diffuse = false, bool *deferred = nullptr) {
+                       int iter, int pixel, int depth, bool last_bounce, bool defer_diffuse = false, bool *deferred = nullptr,
+                       bool *missed = nullptr) {
     if (t > 0.0f) {
         const float *m = mats + matId * MAT_WORDS;
         f3 mcol = mk(m[0], m[1], m[2]);
@@ -566,7 +601,8 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
         }
         return true;
     }
-    ps.c = mk(0.0f, 0.0f, 0.0f);                           // pathtrace.cu:262-264
+    if (missed) *missed = true;                            // ends with throughput * E(d), DESIGN.md section 6.16
+    else ps.c = mk(0.0f, 0.0f, 0.0f);                      // pathtrace.cu:262-264
     return false;
 }
 

@@ -40,6 +40,7 @@ void pt_free(void) {
     if (R.d_grec) (void)hipFree(R.d_grec);
     if (R.d_tri_bound) (void)hipFree(R.d_tri_bound);
     if (R.d_ginfo) (void)hipFree(R.d_ginfo);
+    if (R.d_env) (void)hipFree(R.d_env);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -579,6 +580,56 @@ int pt_set_lens(float lens_radius, float focal_distance) {
     if (lens_radius > 0.0f && (R.flags & PT_CACHE_FIRST))
         return fail(PT_ERR_INVALID, "pt_set_lens: PT_CACHE_FIRST cannot be combined with a lens");
     R.lens.radius = lens_radius; R.lens.focal = focal_distance;
+    return PT_OK;
+}
+
+// Environment lighting (include/ptmi355.h).  The map is scene state the launches in flight read:
+// the host waits for everything the session has enqueued -- windows traced ahead are void, as after a camera change --
+// before the old texels are released.  The accumulation buffer stays as it is.
+int pt_set_environment(const float *texels, int n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_environment: not initialised");
+    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_environment: n = %d outside [0, 1024]", n);
+    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_environment: null texels with n = %d", n);
+    if (!texels) n = 0;
+    const int rc = la_discard(LA_HOST);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(R.stream));
+    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
+        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
+        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
+    }
+    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    R.ov_active = false;
+    R.env_n = 0;
+    if (R.d_env) { (void)hipFree(R.d_env); R.d_env = nullptr; }
+    R.env_keep.clear();
+    if (n == 0) return PT_OK;
+    const size_t count = (size_t)6 * (size_t)n * (size_t)n;
+    std::vector<float> quad(count * 4);
+    for (size_t k = 0; k < count; ++k) {
+        quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; quad[4 * k + 3] = 0.0f;
+    }
+    if (hipMalloc((void **)&R.d_env, count * 16) != hipSuccess) {
+        (void)hipGetLastError(); R.d_env = nullptr;
+        return fail(PT_ERR_NOMEM, "pt_set_environment: %zu bytes of device memory for a %d x %d x 6 map", count * 16, n, n);
+    }
+    HIPCHK(hipMemcpy(R.d_env, quad.data(), count * 16, hipMemcpyHostToDevice));
+    R.env_keep.assign(texels, texels + count * 3);
+    R.env_n = n;
+    return PT_OK;
+}
+
+int pt_get_environment(float *texels, int capacity_texels, int *n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_environment: not initialised");
+    if (!n) return fail(PT_ERR_INVALID, "pt_get_environment: null n");
+    const int en = R.env_n;
+    *n = en;
+    if (en == 0) return PT_OK;
+    const size_t count = (size_t)6 * (size_t)en * (size_t)en;
+    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
+        return fail(PT_ERR_INVALID, "pt_get_environment: room for %d texels, the map has %zu", texels ? capacity_texels : 0, count);
+    memcpy(texels, R.env_keep.data(), count * 12);
     return PT_OK;
 }
 

@@ -32,6 +32,7 @@ BounceArgs bounce_args(int depth) {
     a.cull0_tiles = R.cull0_tiles;
     a.iter_counts = R.iter_counts;
     a.persist = R.persist;
+    a.env = R.d_env; a.env_n = R.env_n;
     return a;
 }
 
@@ -139,24 +140,31 @@ const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false) {
     if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false>;
     return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false>;
 }
+// ... each in two forms: sessions with an environment map launch the ENV instantiation (a miss reads the map), the others
+// the one without
+template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN, bool SORT = false, bool OWN = false>
+void launch_k_bounce(const BounceArgs &a) {
+    if (a.env_n) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+    else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+}
 template <int MODE, bool COMPACT, int MESH, bool GEN>
 void launch_bounce_at(const BounceArgs &a) {
     if constexpr (MODE == MODE_FUSED && COMPACT && MESH != MESH_PRE) {
         if (R.sort_keys > 0) {                                // PT_SORT_MATERIAL, fused: survivors placed by material
-            if (R.scene_lds) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, true, GEN, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
-            else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, false, GEN, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+            if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN, true>(a);
+            else launch_k_bounce<MODE, COMPACT, MESH, false, GEN, true>(a);
             return;
         }
     }
     if constexpr (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE) {
         if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce)
-            if (R.scene_lds) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
-            else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+            if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>(a);
+            else launch_k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>(a);
             return;
         }
     }
-    if (R.scene_lds) hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, true, GEN>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
-    else hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, false, GEN>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+    if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN>(a);
+    else launch_k_bounce<MODE, COMPACT, MESH, false, GEN>(a);
 }
 template <int MODE, bool COMPACT>
 void launch_bounce(const BounceArgs &a) {
@@ -203,18 +211,26 @@ int enqueue_bounce(int depth) {
         if (a.nbins <= SORTW_MAX_BINS && R.sort_wave) {
             // up to 64 keys: wave-private sorting, one barrier per 512-path chunk (pt_kernels.hpp: k_shade_sorted_w)
             const size_t lds = shade_sorted_w_lds_words(R.scene.nmats) * 4;
+            // (with an environment map: the ENV instantiations, as for k_bounce)
+#define PT_SORTED_W(COMPACT, GEN)                                                                                                   \
+    do {                                                                                                                            \
+        if (a.env_n) hipLaunchKernelGGL((k_shade_sorted_w<COMPACT, GEN, true>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);  \
+        else hipLaunchKernelGGL((k_shade_sorted_w<COMPACT, GEN>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);                \
+    } while (0)
             if (a.gen_rays) {
-                if (compact) hipLaunchKernelGGL((k_shade_sorted_w<true, true>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
-                else hipLaunchKernelGGL((k_shade_sorted_w<false, true>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
+                if (compact) PT_SORTED_W(true, true); else PT_SORTED_W(false, true);
             } else {
-                if (compact) hipLaunchKernelGGL((k_shade_sorted_w<true, false>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
-                else hipLaunchKernelGGL((k_shade_sorted_w<false, false>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
+                if (compact) PT_SORTED_W(true, false); else PT_SORTED_W(false, false);
             }
+#undef PT_SORTED_W
         } else {
             const size_t nb = (size_t)((a.nbins + 3) & ~3);
             const size_t lds = ((size_t)LDS_CTL_WORDS + (3 + WAVES) * nb + 2 * SORT_CHUNK +
                                 (a.nbins <= 64 ? (size_t)R.scene.nmats * ptd::MAT_WORDS : 0)) * 4;
-            if (compact) hipLaunchKernelGGL(k_shade_sorted<true>, dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
+            if (a.env_n) {
+                if (compact) hipLaunchKernelGGL((k_shade_sorted<true, true>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
+                else hipLaunchKernelGGL((k_shade_sorted<false, true>), dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
+            } else if (compact) hipLaunchKernelGGL(k_shade_sorted<true>, dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
             else hipLaunchKernelGGL(k_shade_sorted<false>, dim3(R.grid_sort), dim3(BLOCK), lds, R.stream, a);
         }
         HIPCHK(hipGetLastError());
@@ -603,7 +619,10 @@ int enqueue_batch_serial(int iter0, int count) {
         // launch's last workgroup (own finalGather) or k_gather's first
         if (R.want_host_stats && R.d_stats) { a.host_stats = R.d_stats; R.host_stats_serial = R.fin_serial; }
         R.grid_iter_cur = iter_grid_for((uint64_t)R.map.tile_pixels * (uint64_t)count, R.lane_cur != nullptr);
-        if (R.scene_lds) hipLaunchKernelGGL(k_iteration<true>, dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
+        if (a.env_n) {                                          // with an environment map: the ENV instantiation, as for k_bounce
+            if (R.scene_lds) hipLaunchKernelGGL((k_iteration<true, true>), dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
+            else hipLaunchKernelGGL((k_iteration<false, true>), dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
+        } else if (R.scene_lds) hipLaunchKernelGGL(k_iteration<true>, dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
         else hipLaunchKernelGGL(k_iteration<false>, dim3(R.grid_iter_cur), dim3(BLOCK), R.lds_bytes, R.stream, a);
         HIPCHK(hipGetLastError());
         R.step_depth = R.trace_depth;

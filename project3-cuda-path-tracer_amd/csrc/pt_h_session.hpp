@@ -68,6 +68,9 @@ struct Renderer {
     std::vector<float> grec_keep;      // the geom records as uploaded (PT_MESH_BVH rewrites the meshes' words when the trees are rebuilt)
     bool scene_lds = true;        // gather records + materials staged in LDS (else read through the vector cache)
     SceneDev scene{};
+    float4 *d_env = nullptr;               // pt_set_environment: the cube map on the device (BounceArgs::env), {r, g, b, 0} per texel
+    int env_n = 0;                         // ... its texels per face edge; 0: none (the kernels without ENV are launched)
+    std::vector<float> env_keep;           // ... and as the caller gave it (pt_get_environment)
     size_t lds_bytes = 0;
     Control *ctl = nullptr;
     Persist *persist = nullptr;

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(BLOCK) void k_sort_hist(BounceArgs a) {
     }
 }
 
-template <bool COMPACT>
+template <bool COMPACT, bool ENV = false>          // ENV: the session has an environment map (a miss ends with throughput * E(d))
 __global__ __launch_bounds__(BLOCK) void k_shade_sorted(BounceArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
     uint32_t *sctl = reinterpret_cast<uint32_t *>(lds_raw);
@@ -299,8 +299,10 @@ __global__ __launch_bounds__(BLOCK) void k_shade_sorted(BounceArgs a) {
                 const int m = at(a.isect.mat(), i);
                 const uint32_t smp = sample_of(a.map, pid);
                 const int pixel = local_to_pixel(a.map, (int)(pid - smp * (uint32_t)a.map.tile_pixels));
+                bool missed = false;
                 alive = ptd::shade_scatter(ps, t, nrm, m & 0x7fffffff, (m < 0) ? 0 : 1, mat_src, iter0 + (int)smp, pixel,
-                                           a.depth, last_bounce);
+                                           a.depth, last_bounce, false, nullptr, ENV ? &missed : nullptr);
+                if (ENV && missed) ps.c = ptd::miss_colour(ps.c, ps.d, a.env, a.env_n);
                 if (!alive) {
                     put_final(a.fin, pid, ps.c, stamp);
                 }
@@ -359,7 +361,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
     return v;
 }
 
-template <bool COMPACT, bool GEN = false>
+template <bool COMPACT, bool GEN = false, bool ENV = false>
 __global__ __launch_bounds__(BLOCK, GEN ? 6 : 8) void k_shade_sorted_w(BounceArgs a) {
     static_assert(SORT_TPW == 2, "a wave handles two tiles per chunk");
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
@@ -451,8 +453,10 @@ __global__ __launch_bounds__(BLOCK, GEN ? 6 : 8) void k_shade_sorted_w(BounceArg
             if (active) {
                 const uint32_t smp = sample_of(a.map, pid[s]);
                 const int pixel = local_to_pixel(a.map, (int)(pid[s] - smp * (uint32_t)a.map.tile_pixels));
+                bool missed = false;
                 alive = ptd::shade_scatter(ps, th[s], nrm[s], mh[s] & 0x7fffffff, (mh[s] < 0) ? 0 : 1, mats, iter0 + (int)smp, pixel,
-                                           a.depth, last_bounce);
+                                           a.depth, last_bounce, false, nullptr, ENV ? &missed : nullptr);
+                if (ENV && missed) ps.c = ptd::miss_colour(ps.c, ps.d, a.env, a.env_n);
                 if (!alive) {
                     put_final(a.fin, pid[s], ps.c, stamp);
                 }

@@ -750,6 +750,19 @@ int pt_set_lens(float lens_radius, float focal_distance) {
     return on_all([&](Worker &) -> int { return one::pt_set_lens(lens_radius, focal_distance); });
 }
 
+// every context traces with the same map: each keeps its own device copy
+int pt_set_environment(const float *texels, int n) {
+    if (!G.live) return one::pt_set_environment(texels, n);
+    const int rc = multi_sync();
+    if (rc) return rc;
+    return on_all([&](Worker &) -> int { return one::pt_set_environment(texels, n); });
+}
+
+int pt_get_environment(float *texels, int capacity_texels, int *n) {
+    if (!G.live) return one::pt_get_environment(texels, capacity_texels, n);
+    return on_one(0, [&](Worker &) -> int { return one::pt_get_environment(texels, capacity_texels, n); });
+}
+
 int pt_synchronize(void) {
     if (!G.live) return one::pt_synchronize();
     return multi_sync();
@@ -1031,6 +1044,10 @@ int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, floa
 int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
                            const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
     return one::pt_probe_shade_scatter(iter, depth, materials, num_materials, paths, isects, outside, n, deferred);
+}
+int pt_environment_texel(const float *dirs, int count, int n, int32_t *index) { return one::pt_environment_texel(dirs, count, n, index); }
+int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour) {
+    return one::pt_probe_environment(texels, n, dirs, throughput, count, colour);
 }
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
 int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }

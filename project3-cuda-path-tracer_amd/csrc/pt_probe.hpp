@@ -93,6 +93,16 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth,
     q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
 }
 
+// the miss exit's colour through the kernels' own ptd::miss_colour: one lane per (direction, throughput) pair
+__global__ __launch_bounds__(64) void k_probe_environment(const float4 *__restrict__ texels, int n, const float *__restrict__ dirs,
+                                                           const float *__restrict__ throughput, int count, float *__restrict__ colour) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const f3 c = ptd::miss_colour(ptd::mk(throughput[3 * i], throughput[3 * i + 1], throughput[3 * i + 2]),
+                                  ptd::mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]), texels, n);
+    colour[3 * i] = c.x; colour[3 * i + 1] = c.y; colour[3 * i + 2] = c.z;
+}
+
 // the shader clock while whatever else is running runs: one wave counts its cycle counter (s_memtime) against the constant
 // 100-MHz counter (s_memrealtime) for `ticks` of the latter.  Sixteen scalar registers: it has to fit beside a persistent
 // grid that leaves 32 of a SIMD's 800 free (pt_k_image.hpp: k_gather_one).  Ends by itself: the real-time counter advances.
@@ -281,6 +291,36 @@ int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, in
                        d_outside, n, deferred);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_environment_texel(const float *dirs, int count, int n, int32_t *index) {
+    if (count < 0 || n < 1 || n > 1024 || (count > 0 && (!dirs || !index)))
+        return fail(PT_ERR_INVALID, "pt_environment_texel: bad argument (count %d, n %d)", count, n);
+    for (int i = 0; i < count; ++i) index[i] = ptd::env_texel(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], n);
+    return PT_OK;
+}
+
+int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour) {
+    if (count < 0 || n < 0 || n > 1024 || (n > 0 && !texels) || (count > 0 && (!dirs || !throughput || !colour)))
+        return fail(PT_ERR_INVALID, "pt_probe_environment: bad argument (count %d, n %d)", count, n);
+    if (count == 0) return PT_OK;
+    const size_t nt = (size_t)6 * (size_t)n * (size_t)n;
+    std::vector<float> quad(std::max<size_t>(nt, 1) * 4, 0.0f);          // the session's device layout: {r, g, b, 0}
+    for (size_t k = 0; k < nt; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    ProbeBufs b;
+    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
+    const float *d_dirs = (const float *)b.get((size_t)count * 12, dirs);
+    const float *d_thr = (const float *)b.get((size_t)count * 12, throughput);
+    float *d_col = (float *)b.get((size_t)count * 12, nullptr);
+    if (!d_tex || !d_dirs || !d_thr || !d_col) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_environment: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_environment, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_tex, n, d_dirs, d_thr, count, d_col);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(colour, d_col, (size_t)count * 12, hipMemcpyDeviceToHost));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }

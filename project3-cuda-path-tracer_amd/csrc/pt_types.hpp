@@ -351,6 +351,11 @@ struct BounceArgs {
     // diffuse survivors leave their direction to the next bounce, which draws it when it loads them (PENDING_DIR): set by
     // the launch plan only when that bounce is a k_bounce that resolves (tile_load<RESOLVE>)
     int defer_dir;
+    // LAST members (every field above keeps the offset it had before they existed): pt_set_environment's cube map, 6 * env_n *
+    // env_n texels {r, g, b, 0}, face-major; env_n == 0: none.  Read by the ENV instantiations of the
+    // shading kernels, where a path misses; sessions without a map launch the others.
+    const float4 *env;
+    int env_n;
 };
 
 // what k_intersect needs to generate bounce 0's camera rays itself (sorted batches: no k_raygen, no pool to read)

@@ -6,6 +6,12 @@
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
+//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB]
+//
+// --sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB: environment lighting (pt_set_environment) from a gradient baked here into a cube map of
+// N x N texels per face: horizon + (zenith - horizon) * max(y, 0) + (ground - horizon) * max(-y, 0) at the texel centres, y = the
+// unit direction's second component -- float64 rounded to float32 once, operation for operation what binding.gradient_cubemap
+// bakes (the same texels bit for bit).  Set after pathtraceInit, before the first iteration; rays that leave the scene read it.
 //
 // --denoise LEVELS,SC,SN,SP: after the last iteration, the edge-avoiding A-trous filter (pt_denoise: LEVELS levels, sigmas
 // of colour / normal / position) of the accumulated image; BASE.<N>samp.denoised.png is written beside the image through the
@@ -44,6 +50,7 @@
 // Links libptmi355.so (the HIP library) and host/pthost.cpp.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,7 +65,7 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -71,6 +78,8 @@ int main(int argc, char **argv) {
     float move_by[3] = {0.0f, 0.0f, 0.0f};
     int move_iters = 0;
     pt_temporal_params tp = {64, 0.1f, 0.1f};
+    int sky_n = 0;
+    double sky[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};          // zenith, horizon, ground
     std::string resume;
     int start = -1;
     float lens_radius = 0.0f, focal_distance = 0.0f;
@@ -124,6 +133,13 @@ int main(int argc, char **argv) {
             }
             tp.max_history = cap;
         }
+        else if (a == "--sky" && i + 1 < argc) {
+            if (sscanf(argv[++i], "%d,%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf", &sky_n, &sky[0], &sky[1], &sky[2], &sky[3], &sky[4], &sky[5],
+                       &sky[6], &sky[7], &sky[8]) != 10 || sky_n < 1 || sky_n > 1024) {
+                fprintf(stderr, "--sky wants N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB with 1 <= N <= 1024\n");
+                return 1;
+            }
+        }
         else if (a == "--strip-rows" && i + 1 < argc) strip_rows = atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) { devices.clear(); for (int k = 0, n = atoi(argv[++i]); k < n; ++k) devices.push_back(k); }
         else if (a == "--devices" && i + 1 < argc) {
@@ -161,6 +177,32 @@ int main(int argc, char **argv) {
     if (!devices.empty()) { d.devices = devices.data(); d.num_devices = (int32_t)devices.size(); }
     pt_free();                                            // main.cpp:126
     if (pt_init(&d) != PT_OK) { fprintf(stderr, "pathtraceInit: %s\n", pt_last_error()); return 1; }
+
+    if (sky_n > 0) {
+        // texel (face, j, i): the direction through its centre has 1 (or -1) on the face's axis and the centres' coordinates
+        // on the other two, in x, y, z order (include/ptmi355.h: pt_set_environment)
+        const int n = sky_n;
+        std::vector<float> tex((size_t)6 * n * n * 3);
+        for (int face = 0; face < 6; ++face)
+            for (int j = 0; j < n; ++j)
+                for (int i = 0; i < n; ++i) {
+                    const double ca = ((double)i + 0.5) / (double)n * 2.0 - 1.0, cb = ((double)j + 0.5) / (double)n * 2.0 - 1.0;
+                    const int axis = face >> 1;
+                    double v[3];
+                    v[axis] = (face & 1) ? -1.0 : 1.0;
+                    v[axis == 0 ? 1 : 0] = ca;
+                    v[axis == 2 ? 1 : 2] = cb;
+                    const double y = v[1] / std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+                    const double up = y > 0.0 ? y : 0.0, down = -y > 0.0 ? -y : 0.0;
+                    float *t = &tex[(((size_t)face * n + j) * n + i) * 3];
+                    for (int k = 0; k < 3; ++k) {
+                        const double z = sky[k], h = sky[3 + k], g = sky[6 + k];
+                        t[k] = (float)(h + (z - h) * up + (g - h) * down);
+                    }
+                }
+        if (pt_set_environment(tex.data(), n) != PT_OK) { fprintf(stderr, "pt_set_environment: %s\n", pt_last_error()); return 1; }
+        printf("sky: %d x %d x 6 texels\n", n, n);
+    }
 
     std::vector<float> image((size_t)W * H * 3, 0.0f);    // scene->state.image
     int iteration = 0;
