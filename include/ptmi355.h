@@ -196,6 +196,23 @@ enum pt_flags {
                                     negative, NaN or infinite: no lobe, today's path with today's draws.  Diffuse surfaces,
                                     emitters, the miss exit and the last-bounce rule are untouched; PT_FAKE_SHADER ignores
                                     the flag.  Honoured by every pipeline that shades. */
+    PT_DIRECT_LIGHT  = 1u << 13, /* opt-in: direct lighting.  The last bounce of a path that hits a diffuse surface, which
+                                    ends with colour 0 without the flag, aims a FINAL RAY at a random point of an emissive
+                                    cube or sphere instead: with traceDepth D a path has D + 1 bounces, and the final ray
+                                    scores only if its nearest hit is the primitive it was aimed at ("direct lighting"
+                                    below).  Its expectation is that of a plain session of depth
+                                    D + 1 in a scene without specular surfaces.  Bounces 0 .. D - 2, emitters, misses,
+                                    mirrors and dielectrics are untouched; mesh emitters and the environment map are not
+                                    sampled; a scene without an emissive cube or sphere renders as without the flag, bit for
+                                    bit.  pt_stats reports D + 1 bounces (live[D] = the final rays), pt_trace_bounce accepts
+                                    depth D.  Honoured by the fused pipelines (with and without PT_COMPACT, the fused form of
+                                    PT_SORT_MATERIAL, meshes with and without PT_MESH_BVH), which run such a session a kernel
+                                    per bounce, whatever PTMI355_WHOLE_MAX says: the one-launch kernel has no direct form.
+                                    Refused by pt_init (PT_ERR_INVALID) with PT_UNFUSED, with PT_CACHE_FIRST, with a
+                                    PT_SORT_MATERIAL session that would take the two-kernel form (their intersection planes
+                                    do not carry the winning primitive; extending them is a later change), with
+                                    trace_depth > 63 (pt_stats::live has 64 entries; pt_set_camera refuses that depth
+                                    likewise) and with more than 1024 light elements.  PT_FAKE_SHADER ignores the flag. */
     PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after
@@ -311,6 +328,48 @@ int pt_environment_texel(const float *dirs, int count, int n, int32_t *index);
  * pt_glossy_alpha2: host only (no GPU); alpha2[i] for each of `count` exponents.  PT_ERR_INVALID: count < 0, a null array with
  * count > 0. */
 int pt_glossy_alpha2(const float *exponents, int count, float *alpha2);
+
+/* ---- direct lighting (PT_DIRECT_LIGHT): the last bounce aims at a sampled light ----------------------------------------------
+ * With the flag and traceDepth D: bounces 0 .. D - 2 are today's; bounce D - 1 is today's last bounce except that a hit on a
+ * diffuse surface survives with a ray aimed at a sampled point of a light and its colour multiplied by the sample's weight;
+ * bounce D traces that final ray like any other and ends every path (DESIGN.md section 6.18 has the complete specification;
+ * binary32, one rounding per operation in the order written, no FMA; tests/direct_model.py is its numpy form, and the device's
+ * result equals it bit for bit).
+ * Light elements, on the host at pt_init (binary64 on the binary32 entries of pt_geom::transform M, every stored value rounded
+ * once), primitives in index order, only PT_SPHERE / PT_CUBE whose material has emittance > 0:
+ *   cube:   six parallelograms, face f = 2 * axis + (negative side ? 1 : 0): c0 = M * (corner, 1), the corner with the face's
+ *           coordinate (+-0.5) on `axis` and -0.5 on the other two; ea, eb = the columns of M of the other two axes in x, y, z
+ *           order; normal = (ea x eb) / |ea x eb| signed away from the cube's centre; area = |ea x eb|.
+ *   sphere: one element (c0, ea, eb, normal = 0); area = pi * |det M3|^(2/3), exact for a uniform scale, a selection mass otherwise.
+ *   an element whose area is not a finite number > 0 is left out; cdf[e] = (running sum of the areas) / total, the last forced
+ *   to 1.0f; inv_p[e] = total / area[e].  E = 0: the flag has no effect.  E > 1024: pt_init fails.
+ * Sampling at a diffuse hit of bounce D - 1 (P = getPointOnRay's point, n = the reported normal, c = colour * material.color):
+ *   rng = makeSeededRandomEngine(iter, pixel, D - 1); u0, u1, u2 = its first three draws; e = the smallest index with
+ *   u0 < cdf[e] (E - 1 if none).
+ *   parallelogram: y = (c0 + ea * u1) + eb * u2;  nl = normal;  A = area.
+ *   sphere: z = 1 - 2 * u1;  r = sqrt(max(1 - z * z, 0));  (sin, cos) of u2 * TWO_PI by the shared sin / cos;
+ *           s = 0.5 * (r * cos, r * sin, z);  y = multiplyMV(transform, (s, 1));  q = multiplyMV(invTranspose, (s, 0));
+ *           len = sqrt(dot(q, q));  nl = q * (1 / len);  A = (float)(pi * |det M3|) * (len * 2) -- the exact area measure of
+ *           the uniform object-space draw on any ellipsoid.
+ *   v = y - P;  d2 = dot(v, v);  dir = v * (1 / sqrt(d2));  cs = dot(n, dir);  cl = -dot(nl, dir);  with o =
+ *   multiplyMV(inverseTransform, (P, 1)): P is inside the element's primitive when every |o_k| < 0.5 (cube) / dot(o, o) < 0.25
+ *   (sphere), and then cl = -cl (a scene enclosed in its light).
+ *   any of d2 > 0, cs > 0, cl > 0 false (NaN is false): the path ends with colour 0, no ray is traced.  Otherwise
+ *   w = ((cs * cl) * (A * inv_p[e])) / (d2 * (float)pi), colour = c * w, origin P, direction dir: one more bounce.
+ * Final ray (bounce D): its target is the primitive of element e, recomputed from the same engine's first draw.  It scores
+ *   colour *= material.color * emittance when t > 0 and the winning primitive (strict less, lowest index on ties) is the
+ *   target; everything else -- another primitive in front, another emitter, a miss, with or without an environment map -- ends
+ *   with colour 0.  Nothing draws at bounce D; the camera's engine slot stays D.
+ * pt_light_elements: host only (no GPU), pt_init's own function.  Returns E, or the required count when `capacity` is too
+ * small, in which case nothing is written; out may be NULL with capacity 0.  PT_ERR_INVALID: a negative count, a null array
+ * with a positive count, an emitting candidate's materialid outside the table. */
+typedef struct pt_light_element {
+    int32_t geom, kind;            /* the primitive's index; PT_SPHERE or PT_CUBE (one face of it) */
+    pt_vec3 c0, ea, eb, normal;    /* the parallelogram c0 + ea * u + eb * v and its outward unit normal; 0 for a sphere */
+    float area, cdf, inv_p;
+} pt_light_element;
+int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials,
+                      pt_light_element *out, int capacity);
 
 /* pathtrace (pathtrace.cu:284-393): one iteration `iter` (1-based; RNG key and
  * tonemap divisor).  pbo_rgba: optional DEVICE pointer to W*H RGBA8 (the mapped
@@ -525,6 +584,23 @@ int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materi
  * texels as for pt_set_environment.  PT_ERR_INVALID: count < 0, a null array with count > 0, n outside [0, 1024], texels == NULL
  * with n > 0.  count == 0 launches nothing. */
 int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour);
+/* pt_probe_direct_sample: PT_DIRECT_LIGHT's sampler (above; csrc/pt_device.hpp: direct_sample) on the device through the function
+ * the kernels call, one lane per record: for each of `count` (P, n, engine seed) triples (P, n: count x 3 floats; seeded like
+ * pt_probe_hemisphere) the direction (count x 3), the weight and the element picked, on the light table of the scene given as for
+ * pt_light_elements.  weight = 0 and dir = 0 where the path would end (step 6).  A scene without elements: weight 0, dir 0,
+ * element -1, nothing launched.  Refusals as pt_probe_shade_scatter's: count < 0 or above 2^26, a null array with count > 0,
+ * num_materials < 1, what pt_light_elements refuses, more than 1024 elements.  count == 0 launches nothing.
+ * pt_probe_shade_scatter_direct: pt_probe_shade_scatter's contract through the direct form of shade_scatter, as the kernels of a
+ * PT_DIRECT_LIGHT session of traceDepth `trace_depth` call it at bounce `depth` in [0, trace_depth].  The bounce, not
+ * remainingBounces, says where a path is: remainingBounces <= 0 -> untouched; a survivor leaves with remainingBounces =
+ * trace_depth - depth (what pt_export_paths shows), a path that ends with 0.  depth < trace_depth - 1: the plain scatter;
+ * depth == trace_depth - 1: the sampling bounce; depth == trace_depth: the final ray -- hit_geom[i] (n int32, the winning
+ * primitive's index, -1 for a miss; read at this depth only, may be NULL otherwise) decides whether it scores. */
+int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, const float *P,
+                           const float *n, const uint32_t *seeds, int count, float *dir, float *weight, int32_t *element);
+int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                  const uint8_t *outside, const int32_t *hit_geom, int n);
 /* pt_probe_tri_form: the every-triangle loop's first stage on the device, through the kernel's own code (csrc/pt_k_trisweep.hpp:
  * tri_ray_operands, tri_group_form), for ONE mesh of `count` triangles (records and frame as pt_tri_records makes them) and n rays
  * (origins, directions: n x 3 floats each; rays with |origin|_1 > origin_bound are `wild` as in the kernels).  Per ray (each output

@@ -31,12 +31,16 @@ PATH_DT = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("color", "<f
 ISECT_DT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("materialId", "<i4")])
 TRI_DT = np.dtype([("v0", "<f4", 3), ("v1", "<f4", 3), ("v2", "<f4", 3)])
 MESH_DT = np.dtype([("geom_index", "<i4"), ("first_triangle", "<i4"), ("triangle_count", "<i4")])
+# pt_light_element (include/ptmi355.h), 68 bytes
+LIGHT_DT = np.dtype([("geom", "<i4"), ("kind", "<i4"), ("c0", "<f4", 3), ("ea", "<f4", 3), ("eb", "<f4", 3), ("normal", "<f4", 3),
+                     ("area", "<f4"), ("cdf", "<f4"), ("inv_p", "<f4")])
 
 PT_COMPACT, PT_SORT_MATERIAL, PT_FAKE_SHADER, PT_CACHE_FIRST, PT_UNFUSED, PT_MESH_BVH, PT_AA_JITTER, PT_ASYNC_IMAGE, PT_PIN_IMAGE = 1, 2, 4, 8, 16, 32, 64, 128, 256
 PT_HOST_SPARSE = 1024
 PT_SHARED_IMAGE = 512
 PT_LOOKAHEAD = 2048         # pt_trace traces ahead of its caller (include/ptmi355.h)
 PT_GLOSSY = 4096            # SPECEX gives mirrors and dielectrics a GGX lobe (include/ptmi355.h)
+PT_DIRECT_LIGHT = 8192      # the last bounce aims a final ray at a sampled light (include/ptmi355.h)
 BVH_NODE_WORDS = 16
 
 
@@ -179,6 +183,11 @@ def library():
             L.pt_glossy_alpha2.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
             L.pt_probe_glossy_lobe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
             L.pt_probe_shade_scatter_glossy.argtypes = L.pt_probe_shade_scatter.argtypes
+            L.pt_light_elements.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            L.pt_probe_direct_sample.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_probe_shade_scatter_direct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -674,6 +683,54 @@ def probe_glossy_lobe(normals, seeds, alpha2):
     out = np.zeros((len(sd), 3), dtype=np.float32)
     _chk(library().pt_probe_glossy_lobe(_p(nr), _p(sd), _p(a2), len(sd), _p(out)))
     return out
+
+
+def light_elements(geoms, materials):
+    """Host-only: the light element table a PT_DIRECT_LIGHT session builds at pathtraceInit (include/ptmi355.h:
+    pt_light_elements), a LIGHT_DT array; empty when no cube or sphere emits."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    L = library()
+    need = _chk(L.pt_light_elements(_p(g), len(g), _p(m), len(m), None, 0))
+    out = np.zeros(need, dtype=LIGHT_DT)
+    if need:
+        assert _chk(L.pt_light_elements(_p(g), len(g), _p(m), len(m), _p(out), need)) == need
+    return out
+
+
+def probe_direct_sample(geoms, materials, P, normals, seeds):
+    """PT_DIRECT_LIGHT's sampler on the device for (P, normal, engine seed) triples on the light table of (geoms, materials)
+    (include/ptmi355.h: pt_probe_direct_sample): (dir [n, 3] float32, weight [n] float32, element [n] int32); weight 0 and
+    dir 0 where the path would end."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    p = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    if len(p) != len(sd) or len(nr) != len(sd):
+        raise PtError("probe_direct_sample: %d points, %d normals, %d seeds" % (len(p), len(nr), len(sd)))
+    d = np.zeros((len(sd), 3), dtype=np.float32)
+    w = np.zeros(len(sd), dtype=np.float32)
+    e = np.zeros(len(sd), dtype=np.int32)
+    _chk(library().pt_probe_direct_sample(_p(g), len(g), _p(m), len(m), _p(p), _p(nr), _p(sd), len(sd), _p(d), _p(w), _p(e)))
+    return d, w, e
+
+
+def probe_shade_scatter_direct(iter, depth, trace_depth, geoms, materials, paths, isects, outside=None, hit_geom=None):
+    """probe_shade_scatter through the direct form of the shader, as a PT_DIRECT_LIGHT session of traceDepth `trace_depth` calls
+    it at bounce `depth` in [0, trace_depth] (include/ptmi355.h: pt_probe_shade_scatter_direct).  hit_geom: the winning primitive
+    per pair (-1: miss), read at depth == trace_depth."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    p = np.array(paths, dtype=PATH_DT, copy=True, order="C").reshape(-1)
+    x = np.ascontiguousarray(isects, dtype=ISECT_DT).reshape(-1)
+    o = None if outside is None else np.ascontiguousarray(outside, dtype=np.uint8).reshape(-1)
+    h = None if hit_geom is None else np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    if len(x) != len(p) or (o is not None and len(o) != len(p)) or (h is not None and len(h) != len(p)):
+        raise PtError("probe_shade_scatter_direct: %d paths, %d intersections" % (len(p), len(x)))
+    _chk(library().pt_probe_shade_scatter_direct(int(iter), int(depth), int(trace_depth), _p(g), len(g), _p(m), len(m), _p(p), _p(x),
+                                                 _p(o), _p(h), len(p)))
+    return p
 
 
 def probe_shade_scatter_glossy(iter, depth, materials, paths, isects, outside=None, deferred=False):

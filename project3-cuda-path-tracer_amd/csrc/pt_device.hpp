@@ -548,6 +548,88 @@ PTD f3 miss_colour(f3 throughput, f3 d, const float4 *texels, int n) {
     return mul(throughput, env_radiance(texels, n, d));
 }
 
+// ---------------------------------------------------------------------------
+// direct lighting (PT_DIRECT_LIGHT): the last bounce of a diffuse hit aims at a sampled light
+// ---------------------------------------------------------------------------
+// light element record: 56 dwords, made on the host at pt_init (pt_lights.hpp: ptlight::records) from pt_light_elements'
+// table.  [0] kind (0 sphere, 1 parallelogram: a cube face) [1] geom [2] area [3] cdf [4] inv_p [5] sphere: (float)(pi |det M3|)
+// [6..17] c0 ea eb normal   [18..29] inverseTransform   [30..41] transform   [42..53] invTranspose of the primitive
+// (4 columns x 3 rows each, as in the geom record).  Lanes index the table divergently: vector loads.
+constexpr int LIGHT_WORDS = 56;
+constexpr int L_KIND = 0, L_GEOM = 1, L_AREA = 2, L_CDF = 3, L_INVP = 4, L_DETPI = 5, L_C0 = 6, L_EA = 9, L_EB = 12, L_NRM = 15,
+              L_INV = 18, L_FWD = 30, L_INVT = 42;
+
+// the smallest e with u0 < cdf[e]; count - 1 if none (cdf is non-decreasing and ends with 1.0f, u0 < 1)
+PTD int light_pick(const float *lights, int count, float u0) {
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u0 < lights[(size_t)mid * LIGHT_WORDS + L_CDF]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// steps 1 (the draws) to 7 of section 6.18 at the point P with normal n: the engine's first three draws pick the element and
+// the point y on it.  true: `dir` = the unit direction to y and `w` = the sample's weight cos cos A inv_p / (pi r^2); false
+// (y is not in front of P, or P not in front of the element): dir = 0, w = 0.  elem = the element picked either way.
+PTD bool direct_sample(const float *lights, int count, f3 P, f3 n, uint32_t &rng, f3 &dir, float &w, int &elem) {
+    const float TWO_PI = 6.2831853071795864769252867665590057683943f;
+    const float PI = 3.14159265358979323846264338327950288f;
+    const float u0 = u01(rng);
+    const float u1 = u01(rng);
+    const float u2 = u01(rng);
+    const int e = light_pick(lights, count, u0);
+    elem = e;
+    const float *L = lights + (size_t)e * LIGHT_WORDS;
+    const bool sphere = __float_as_int(L[L_KIND]) == 0;
+    f3 y, nl;
+    float A;
+    if (sphere) {
+        const float z = 1.0f - 2.0f * u1;
+        const float r = __builtin_sqrtf(__builtin_fmaxf(1.0f - z * z, 0.0f));
+        float sa, ca;
+        sincos_shared(u2 * TWO_PI, sa, ca);
+        const f3 s = scale(mk(r * ca, r * sa, z), 0.5f);
+        y = mv_point(L + L_FWD, s);
+        const f3 q = mv_dir(L + L_INVT, s);
+        const float len = __builtin_sqrtf(dot(q, q));
+        nl = scale(q, 1.0f / len);
+        A = L[L_DETPI] * (len * 2.0f);
+    } else {
+        const f3 c0 = mk(L[L_C0], L[L_C0 + 1], L[L_C0 + 2]);
+        const f3 ea = mk(L[L_EA], L[L_EA + 1], L[L_EA + 2]);
+        const f3 eb = mk(L[L_EB], L[L_EB + 1], L[L_EB + 2]);
+        y = add(add(c0, scale(ea, u1)), scale(eb, u2));
+        nl = mk(L[L_NRM], L[L_NRM + 1], L[L_NRM + 2]);
+        A = L[L_AREA];
+    }
+    const f3 v = sub(y, P);
+    const float d2 = dot(v, v);
+    const f3 d = scale(v, 1.0f / __builtin_sqrtf(d2));
+    const float cs = dot(n, d);
+    float cl = -dot(nl, d);
+    // P inside the element's primitive (a scene enclosed in its light): the element is seen from its other side
+    const f3 o = mv_point(L + L_INV, P);
+    const bool inside = sphere ? dot(o, o) < 0.25f
+                               : (__builtin_fabsf(o.x) < 0.5f && __builtin_fabsf(o.y) < 0.5f && __builtin_fabsf(o.z) < 0.5f);
+    if (inside) cl = -cl;
+    if (!(d2 > 0.0f && cs > 0.0f && cl > 0.0f)) {                      // NaN: false
+        dir = mk(0.0f, 0.0f, 0.0f);
+        w = 0.0f;
+        return false;
+    }
+    dir = d;
+    w = ((cs * cl) * (A * L[L_INVP])) / (d2 * PI);
+    return true;
+}
+
+// the primitive the final ray of (iter, pixel) was aimed at: the first draw of the engine of the bounce that aimed it
+PTD int direct_target(const float *lights, int count, int iter, int pixel, int depth) {
+    uint32_t rng = seeded_engine(iter, pixel, depth);
+    const int e = light_pick(lights, count, u01(rng));
+    return __float_as_int(lights[(size_t)e * LIGHT_WORDS + L_GEOM]);
+}
+
 // returns true when the path stays alive; on false `ps.c` is the final colour.  `defer_diffuse`: a diffuse survivor
 // keeps the hit normal in `ps.d` and sets `*deferred` -- hemisphere(n, seeded_engine(iter, pixel, depth)) is left to
 // whoever reads the path next (the next bounce's load, or the export); everything else is as without it.
@@ -557,10 +639,14 @@ PTD f3 miss_colour(f3 throughput, f3 d, const float4 *texels, int n) {
 // word 10 scatters about a sampled microfacet normal h instead of n -- the engine's first two draws; the Fresnel choice
 // is then its third.  h that does not face the ray is replaced by the face-forward normal ng, and a reflection that
 // would enter the surface it left by the reflection about ng.  Without GLOSSY the word is never read.
-template <bool GLOSSY = false>
+// DIRECT (the kernels a PT_DIRECT_LIGHT session launches for its last two bounces): at the last
+// bounce a hit on a diffuse surface survives with a ray aimed at a sampled point of a light (direct_sample on the table
+// `lights` of `nlights` elements) and its colour multiplied by the sample's weight; a mirror or dielectric ends with colour 0
+// as without it.  Without DIRECT the two arguments are never read.
+template <bool GLOSSY = false, bool DIRECT = false>
 PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, const float *mats,
                        int iter, int pixel, int depth, bool last_bounce, bool defer_diffuse = false, bool *deferred = nullptr,
-                       bool *missed = nullptr) {
+                       bool *missed = nullptr, const float *lights = nullptr, int nlights = 0) {
     if (t > 0.0f) {
         const float *m = mats + matId * MAT_WORDS;
         f3 mcol = mk(m[0], m[1], m[2]);
@@ -572,6 +658,19 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
         // the last bounce: whatever the scatter would produce, the path ends with colour 0 (remainingBounces reaches 0,
         // completion spec 8.0) -- no engine, no direction (wave-uniform: the whole launch takes this exit)
         if (last_bounce) {
+            if (DIRECT && nlights > 0 && !(m[6] > 0.0f) && !(m[7] > 0.0f)) {
+                uint32_t rng = seeded_engine(iter, pixel, depth);
+                const f3 P = point_on_ray(ps.o, ps.d, t);
+                f3 dir;
+                float w;
+                int e;
+                if (direct_sample(lights, nlights, P, n, rng, dir, w, e)) {
+                    ps.c = scale(mul(ps.c, mcol), w);
+                    ps.o = P;
+                    ps.d = dir;
+                    return true;
+                }
+            }
             ps.c = mk(0.0f, 0.0f, 0.0f);
             return false;
         }

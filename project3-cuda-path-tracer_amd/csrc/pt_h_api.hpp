@@ -41,6 +41,7 @@ void pt_free(void) {
     if (R.d_tri_bound) (void)hipFree(R.d_tri_bound);
     if (R.d_ginfo) (void)hipFree(R.d_ginfo);
     if (R.d_env) (void)hipFree(R.d_env);
+    if (R.d_lights) (void)hipFree(R.d_lights);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -158,6 +159,21 @@ static int init_impl(const pt_scene_desc *d) {
                                     "combined with PT_AA_JITTER or a lens (INSTRUCTION.md:113)");
     if (d->lens_radius > 0.0f && !(d->focal_distance > 0.0f))
         return fail(PT_ERR_INVALID, "pt_init: a lens needs focal_distance > 0");
+    // PT_DIRECT_LIGHT: the pipelines that keep intersection planes do not carry the winning primitive
+    // (the two-kernel sort is refused further down, once the form of the sort is known); PT_FAKE_SHADER ignores the flag
+    std::vector<pt_light_element> light_el;
+    if ((d->flags & PT_DIRECT_LIGHT) && !(d->flags & PT_FAKE_SHADER)) {
+        if (d->flags & PT_UNFUSED)
+            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_UNFUSED (its intersection planes do not carry the winning primitive)");
+        if (d->flags & PT_CACHE_FIRST)
+            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_CACHE_FIRST (the first-bounce cache keeps no primitive number)");
+        if (d->trace_depth > MAX_DEPTH - 1)
+            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT runs trace_depth + 1 bounces: trace_depth %d outside [1,%d]", d->trace_depth, MAX_DEPTH - 1);
+        const int ne = ptlight::elements(d->geoms, d->num_geoms, d->materials, d->num_materials, light_el);
+        if (ne < 0) return fail(PT_ERR_INTERNAL, "pt_init: light elements");       // (material indices were checked above)
+        if (ne > ptlight::MAX_ELEMENTS)
+            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT: %d light elements (at most %d)", ne, ptlight::MAX_ELEMENTS);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(PT_ERR_DEVICE, "pt_init: no HIP device (this library has no CPU fallback)");
@@ -370,6 +386,17 @@ static int init_impl(const pt_scene_desc *d) {
         const double tiles_k = (double)d->num_materials * ((double)((R.cap + 63) / 64) + 8192.0 * R.sort_runs);
         if (on && tiles_k * 2560.0 * 2.0 <= budget_gb * 1e9 && tiles_k * 64.0 < 2147483648.0) R.sort_keys = d->num_materials;
     }
+    if ((R.flags & PT_DIRECT_LIGHT) && !(R.flags & PT_FAKE_SHADER) && (R.flags & PT_SORT_MATERIAL) && !R.sort_keys)
+        return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with the two-kernel form of PT_SORT_MATERIAL, which this "
+                                    "session would take (its intersection planes do not carry the winning primitive)");
+    if (!light_el.empty()) {
+        std::vector<float> lrec;
+        ptlight::records(d->geoms, light_el, lrec);
+        static_assert(ptlight::RECORD_WORDS == ptd::LIGHT_WORDS, "one record layout");
+        HIPCHK(hipMalloc((void **)&R.d_lights, lrec.size() * 4));
+        HIPCHK(hipMemcpy(R.d_lights, lrec.data(), lrec.size() * 4, hipMemcpyHostToDevice));
+        R.nlights = (int)light_el.size();
+    }
     // pools, intersections, final colours, image, control
     const size_t capz = R.cap;
     const size_t pool_mult = (size_t)std::max(1, R.sort_keys);
@@ -405,7 +432,7 @@ static int init_impl(const pt_scene_desc *d) {
     R.max_tiles = (R.cap + TILE - 1) / TILE;
     // only the election buckets of the bounces this scene can run are cleared per batch
     R.ctl_bytes = offsetof(Control, bucket) - offsetof(Control, stamp) +
-                  (size_t)R.trace_depth * sizeof(((Control *)nullptr)->bucket[0]);
+                  (size_t)session_bounces() * sizeof(((Control *)nullptr)->bucket[0]);
     HIPCHK(hipMalloc((void **)&R.ctl, sizeof(Control)));
     HIPCHK(hipMemsetAsync(R.ctl, 0, sizeof(Control), R.stream));      // incl. Control::ticket, which no batch clears
     HIPCHK(hipMalloc((void **)&R.persist, sizeof(Persist)));
@@ -421,18 +448,27 @@ static int init_impl(const pt_scene_desc *d) {
     int per_cu = 8;
     {
         const bool sorted = R.sort_keys > 0;
-        const void *fns[2];
-        if (R.mesh_mode == MESH_BVH) { fns[0] = bounce_fn<MESH_PRE>(R.scene_lds, false, false); fns[1] = bounce_fn<MESH_PRE>(R.scene_lds, true, false); }
-        else if (R.mesh_mode == MESH_TILES) { fns[0] = bounce_fn<MESH_TILES>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_TILES>(R.scene_lds, true, sorted); }
-        else { fns[0] = bounce_fn<MESH_NONE>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE>(R.scene_lds, true, sorted); }
         // (a session may launch the own-surface form of the plain kernel, batch by batch: enqueue_bounce)
         const bool own = R.mesh_mode == MESH_NONE && !sorted;
-        const void *fns_own[2] = {own ? bounce_fn<MESH_NONE>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE>(R.scene_lds, true, false, true) : fns[1]};
-        for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1]}) {
-            int n = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
-            per_cu = std::min(per_cu, n);
-        }
+        // sh: the shading variant (std::integral_constant) -- 0, and SH_DIRECT for the forms a PT_DIRECT_LIGHT session launches
+        // for its last two bounces
+        auto size_for = [&](auto sh) -> int {
+            constexpr int SH = decltype(sh)::value;
+            const void *fns[2];
+            if (R.mesh_mode == MESH_BVH) { fns[0] = bounce_fn<MESH_PRE, SH>(R.scene_lds, false, false); fns[1] = bounce_fn<MESH_PRE, SH>(R.scene_lds, true, false); }
+            else if (R.mesh_mode == MESH_TILES) { fns[0] = bounce_fn<MESH_TILES, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_TILES, SH>(R.scene_lds, true, sorted); }
+            else { fns[0] = bounce_fn<MESH_NONE, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE, SH>(R.scene_lds, true, sorted); }
+            const void *fns_own[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true) : fns[1]};
+            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1]}) {
+                int n = 0;
+                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
+                per_cu = std::min(per_cu, n);
+            }
+            return PT_OK;
+        };
+        int rc = size_for(std::integral_constant<int, 0>{});
+        if (rc == PT_OK && R.nlights > 0) rc = size_for(std::integral_constant<int, SH_DIRECT>{});
+        if (rc != PT_OK) return rc;
     }
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
@@ -535,6 +571,8 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
                     R.map.W, R.map.H, camera->resolution[0], camera->resolution[1]);
     if (trace_depth < 1 || trace_depth > MAX_DEPTH)
         return fail(PT_ERR_INVALID, "pt_set_camera: trace_depth %d outside [1, %d]", trace_depth, MAX_DEPTH);
+    if ((R.flags & PT_DIRECT_LIGHT) && !(R.flags & PT_FAKE_SHADER) && trace_depth > MAX_DEPTH - 1)
+        return fail(PT_ERR_INVALID, "pt_set_camera: PT_DIRECT_LIGHT runs trace_depth + 1 bounces: trace_depth %d outside [1, %d]", trace_depth, MAX_DEPTH - 1);
     if (memcmp(&R.cam, camera, sizeof R.cam) != 0) {
         R.cache_valid = false;                                  // refill the bounce-0 cache
         // windows traced ahead for the old camera are void, and what follows rewrites masks and boxes their launches read
@@ -554,7 +592,7 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
     if (trace_depth != R.trace_depth) {
         // the per-batch clear covers the election buckets of the bounces that can run
         R.ctl_bytes = offsetof(Control, bucket) - offsetof(Control, stamp) +
-                      (size_t)trace_depth * sizeof(((Control *)nullptr)->bucket[0]);
+                      (size_t)(trace_depth + (R.nlights > 0 ? 1 : 0)) * sizeof(((Control *)nullptr)->bucket[0]);
     }
     const bool moved = memcmp(&R.cam, camera, sizeof R.cam) != 0;
     R.cam = *camera;
@@ -679,7 +717,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.epi_enabled &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 
@@ -967,8 +1005,8 @@ int pt_trace_begin(int iter0, int count) {
 
 int pt_trace_bounce(int depth, int *n_live_after) {
     if (!R.live || !R.in_step) return fail(PT_ERR_INVALID, "pt_trace_bounce: call pt_trace_begin first");
-    if (depth != R.step_depth || depth >= R.trace_depth)
-        return fail(PT_ERR_INVALID, "pt_trace_bounce: depth %d, expected %d (< %d)", depth, R.step_depth, R.trace_depth);
+    if (depth != R.step_depth || depth >= session_bounces())
+        return fail(PT_ERR_INVALID, "pt_trace_bounce: depth %d, expected %d (< %d)", depth, R.step_depth, session_bounces());
     int rc = (R.flags & PT_FAKE_SHADER) ? enqueue_fake() : enqueue_bounce(depth);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(R.stream));
@@ -1009,7 +1047,7 @@ int pt_export_paths(pt_path_segment *host_paths, int capacity, int *n_live) {
             HIPCHK(hipMemcpy(&span, tile_dir(R.cur_dir).mem + 3 * nrp + 8, 4, hipMemcpyDeviceToHost));
         }
         hipLaunchKernelGGL(k_export_paths, dim3((n + 255) / 256), dim3(256), 0, R.stream, R.pool[R.cur], R.map, n,
-                           live, R.trace_depth - R.step_depth, (pt_path_segment *)R.scratch,
+                           live, session_bounces() - R.step_depth, (pt_path_segment *)R.scratch,
                            tile_dir(packed ? R.cur_dir : -1), span, R.step_iter0, R.step_depth - 1, R.pool_own ? OWN_MASK : 0u);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(host_paths, R.scratch, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost, R.stream));
@@ -1222,6 +1260,17 @@ int pt_get_profile(pt_profile *out) {
     if (rc) return rc;
     *out = R.prof;
     return PT_OK;
+}
+
+// PT_DIRECT_LIGHT's light element table (include/ptmi355.h; pt_lights.hpp): what pt_init builds, host only
+int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, pt_light_element *out, int capacity) {
+    if (num_geoms < 0 || num_materials < 0 || capacity < 0 || (num_geoms > 0 && !geoms) || (num_materials > 0 && !materials) || (capacity > 0 && !out))
+        return fail(PT_ERR_INVALID, "pt_light_elements: bad argument (%d geoms, %d materials, capacity %d)", num_geoms, num_materials, capacity);
+    std::vector<pt_light_element> el;
+    const int ne = ptlight::elements(geoms, num_geoms, materials, num_materials, el);
+    if (ne < 0) return fail(PT_ERR_INVALID, "pt_light_elements: a cube or sphere names a material outside [0, %d)", num_materials);
+    if (ne <= capacity && ne > 0) memcpy(out, el.data(), (size_t)ne * sizeof(pt_light_element));
+    return ne;
 }
 
 int pt_get_stats(pt_stats *stats) {

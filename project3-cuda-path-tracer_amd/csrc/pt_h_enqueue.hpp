@@ -33,6 +33,7 @@ BounceArgs bounce_args(int depth) {
     a.iter_counts = R.iter_counts;
     a.persist = R.persist;
     a.env = R.d_env; a.env_n = R.env_n;
+    a.lights = R.d_lights; a.nlights = R.nlights;
     return a;
 }
 
@@ -123,37 +124,50 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // serves them all, no ray generation); the fused kernel reads the results of the mesh pre-pass under PT_MESH_BVH
 // (the hierarchy is never walked inline by k_bounce) and generates bounce 0's rays itself in batches (GEN).
 // the fused compacting kernel that launch_bounce_at picks for (scene in LDS, ray generation, material keys)
-template <int MESH>
+// SH: the shading variant the grid is sized for -- 0, or SH_DIRECT for the last two bounces of a PT_DIRECT_LIGHT session
+template <int MESH, int SH = 0>
 const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false) {
     if constexpr (MESH == MESH_NONE) {
         if (own && !sorted) {
-            if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, false, true>;
-            return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, false, true>;
+            if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, false, true, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, false, true, SH>;
+            return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, false, true, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, false, true, SH>;
         }
     }
     if constexpr (MESH != MESH_PRE) {
         if (sorted) {
-            if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, true>;
-            return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, true>;
+            if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, true, false, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, true, false, SH>;
+            return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, true, false, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, true, false, SH>;
         }
     }
-    if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false>;
-    return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false>;
+    if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, false, false, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, false, false, SH>;
+    return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, false, false, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, false, false, SH>;
 }
 // ... each in four forms (pt_types.hpp: SH_ENV | SH_GLOSSY): sessions with an environment map launch the ENV instantiations
 // (a miss reads the map), sessions with PT_GLOSSY the GLOSSY ones (mirrors and dielectrics scatter about a microfacet
 // normal), every other session the ones with neither.  Every shading kernel is picked through this switch.
-#define PT_SHADE_DISPATCH(CALL)                                                                     \
-    do {                                                                                            \
-        switch ((a.env_n ? SH_ENV : 0) | ((R.flags & PT_GLOSSY) ? SH_GLOSSY : 0)) {                 \
-        case SH_ENV | SH_GLOSSY: { constexpr int SH = SH_ENV | SH_GLOSSY; CALL; } break;            \
-        case SH_GLOSSY: { constexpr int SH = SH_GLOSSY; CALL; } break;                              \
-        case SH_ENV: { constexpr int SH = SH_ENV; CALL; } break;                                    \
-        default: { constexpr int SH = 0; CALL; } break;                                             \
-        }                                                                                           \
+// (variadic: the launch macro inside CALL expands to text with commas of its own)
+// EXTRA: a further bit every case carries -- SH_DIRECT for the last two bounces of a PT_DIRECT_LIGHT session (launch_k_bounce), else 0
+#define PT_SHADE_DISPATCH_WITH(EXTRA, ...)                                                                  \
+    do {                                                                                                    \
+        switch ((a.env_n ? SH_ENV : 0) | ((R.flags & PT_GLOSSY) ? SH_GLOSSY : 0)) {                         \
+        case SH_ENV | SH_GLOSSY: { constexpr int SH = SH_ENV | SH_GLOSSY | (EXTRA); __VA_ARGS__; } break;   \
+        case SH_GLOSSY: { constexpr int SH = SH_GLOSSY | (EXTRA); __VA_ARGS__; } break;                     \
+        case SH_ENV: { constexpr int SH = SH_ENV | (EXTRA); __VA_ARGS__; } break;                           \
+        default: { constexpr int SH = (EXTRA); __VA_ARGS__; } break;                                        \
+        }                                                                                                   \
     } while (0)
+#define PT_SHADE_DISPATCH(...) PT_SHADE_DISPATCH_WITH(0, __VA_ARGS__)
+// PT_DIRECT_LIGHT: bounces D - 1 (the sampling bounce) and D (the final ray) of a session that has
+// lights to sample launch the DIRECT forms of the fused kernel; bounces 0 .. D - 2 the kernels of a session without the flag,
+// with the same arguments (last_bounce is false there and the camera's engine slot is D either way).
 template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN, bool SORT = false, bool OWN = false>
 void launch_k_bounce(const BounceArgs &a) {
+    if constexpr (MODE == MODE_FUSED) {
+        if (a.nlights > 0 && a.depth >= a.trace_depth - 1) {
+            PT_SHADE_DISPATCH_WITH(SH_DIRECT, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
+            return;
+        }
+    }
     PT_SHADE_DISPATCH(hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
 }
 template <int MODE, bool COMPACT, int MESH, bool GEN>
@@ -315,7 +329,7 @@ int enqueue_end(void) {
         // a window traced ahead of the caller (PT_LOOKAHEAD): its final colours stay where they are until the calls that
         // consume them (k_gather_one, one sample each); only its counters are folded, on the lane's own stream
         hipLaunchKernelGGL(k_gather, dim3(1), dim3(BLOCK), 0, R.stream, R.image, R.final_mem, R.cap, R.map, R.step_count, R.ctl,
-                           R.persist, R.trace_depth, 0u, R.whole ? 1 : 0, 1, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
+                           R.persist, session_bounces(), 0u, R.whole ? 1 : 0, 1, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
                            (HostStats *)nullptr);
         R.whole = false;
         HIPCHK(hipGetLastError());
@@ -332,7 +346,7 @@ int enqueue_end(void) {
     }
     hipLaunchKernelGGL(k_gather, dim3((R.map.tile_pixels + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, gs, R.image,
                        R.final_mem, R.cap, R.map,
-                       R.step_count, R.ctl, R.persist, (R.flags & PT_FAKE_SHADER) ? 0 : R.trace_depth,
+                       R.step_count, R.ctl, R.persist, (R.flags & PT_FAKE_SHADER) ? 0 : session_bounces(),
                        (R.flags & PT_FAKE_SHADER) ? (uint32_t)R.map.tile_pixels * (uint32_t)R.step_count : 0u,
                        R.whole ? 1 : 0, R.epi_done ? 1 : 0, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
                        (R.whole && R.host_stats_serial) ? R.d_stats : (HostStats *)nullptr);
@@ -592,8 +606,9 @@ int enqueue_batch_serial(int iter0, int count) {
     // (one iteration straight into a page-locked host image: the launch hides the PCIe transfer under its tracing, which
     // a kernel per bounce + a copy cannot: worth it for larger frames too -- 3840x2160: 2.49 -> see profiles/r04/ab_percall_4k.log)
     const uint64_t whole_limit = (count == 1 && R.epi_host) ? std::max(R.whole_max_paths, R.whole_max_host_paths) : R.whole_max_paths;
+    // (a PT_DIRECT_LIGHT session with lights to sample runs a kernel per bounce: k_iteration has no DIRECT form)
     const bool whole = !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && count >= 1 &&
+                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && count >= 1 &&
                        (uint64_t)R.map.tile_pixels * (uint64_t)count <= whole_limit;
     int rc = enqueue_begin(iter0, count, false, !whole);
     if (rc) return rc;
@@ -629,7 +644,7 @@ int enqueue_batch_serial(int iter0, int count) {
         R.step_depth = R.trace_depth;
         R.whole = true;
     } else {
-        for (int d = 0; d < R.trace_depth; ++d) {
+        for (int d = 0; d < session_bounces(); ++d) {
             rc = enqueue_bounce(d);
             if (rc) return rc;
         }

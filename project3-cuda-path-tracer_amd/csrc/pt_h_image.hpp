@@ -128,7 +128,7 @@ int collect_stats(void) {
     if (R.flags & PT_FAKE_SHADER) {
         R.stats.live[0] = R.map.tile_pixels * R.step_count; R.stats.rays = R.stats.live[0]; R.stats.bounces = 1;
     } else {
-        for (int d = 0; d < R.trace_depth && d < 64; ++d) {
+        for (int d = 0; d < session_bounces() && d < 64; ++d) {
             R.stats.live[d] = (int32_t)c.alive[d];
             R.stats.rays += c.alive[d];
             if (c.alive[d]) R.stats.bounces = d + 1;

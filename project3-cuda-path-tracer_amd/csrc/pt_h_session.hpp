@@ -71,6 +71,11 @@ struct Renderer {
     float4 *d_env = nullptr;               // pt_set_environment: the cube map on the device (BounceArgs::env), {r, g, b, 0} per texel
     int env_n = 0;                         // ... its texels per face edge; 0: none (the kernels without ENV are launched)
     std::vector<float> env_keep;           // ... and as the caller gave it (pt_get_environment)
+    // PT_DIRECT_LIGHT: the light element table on the device (BounceArgs::lights, ptd::LIGHT_WORDS
+    // dwords per element) and its size.  nlights > 0 only in a session that has the flag, is not PT_FAKE_SHADER and whose
+    // scene has a cube or sphere that emits: such a session runs trace_depth + 1 bounces (session_bounces), a kernel each.
+    float *d_lights = nullptr;
+    int nlights = 0;
     size_t lds_bytes = 0;
     Control *ctl = nullptr;
     Persist *persist = nullptr;
@@ -319,6 +324,9 @@ int ensure_scratch(size_t bytes) {
     R.scratch_bytes = bytes;
     return PT_OK;
 }
+
+// bounces a batch of this session runs: traceDepth, and the final ray of PT_DIRECT_LIGHT behind them
+int session_bounces(void) { return R.trace_depth + (R.nlights > 0 ? 1 : 0); }
 
 RangeDir tile_dir(int depth) {
     const uint32_t W = (uint32_t)R.grid * WAVES * (uint32_t)(R.sort_keys > 0 ? R.sort_runs : 1);     // runs of tiles

@@ -156,12 +156,16 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 // SH: the shading variant, SH_ENV | SH_GLOSSY (pt_types.hpp).  GLOSSY: the session has PT_GLOSSY --
 // mirrors and dielectrics with alpha^2 > 0 scatter about a microfacet normal (ptd::shade_scatter<true>); sessions without
 // the flag launch the instantiations without it, as with ENV.
+// DIRECT: bounces D - 1 and D of a PT_DIRECT_LIGHT session with traceDepth D (k_bounce only).  At
+// D - 1 the last-bounce exit of a diffuse hit aims a final ray at a sampled light (ptd::shade_scatter<.., true>); at D every
+// path ends: with the emitter's colour when its nearest hit is the primitive `geom` it was aimed at, with 0 otherwise -- a
+// miss included, whatever the environment.  The table's pointer and size are read where they are used, like the map's.
 template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = false, int SH = 0>
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
                                            uint32_t n, uint32_t dst_base, uint32_t &packed, uint32_t &traced,
-                                           uint32_t key_stride = 0, uint32_t own_bits = 0) {
-    constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0;
+                                           uint32_t key_stride = 0, uint32_t own_bits = 0, int geom = -1) {
+    constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0, DIRECT = (SH & SH_DIRECT) != 0;
     const int lane = c.lane;
     bool alive = false, deferred = false, missed = false;
     ptd::PathState ps;
@@ -194,8 +198,25 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
     };
     if (tr.active) {
         const bool defer = DEFER && (c.kargs ? karg_field<int>(offsetof(BounceArgs, defer_dir)) : a.defer_dir) != 0;
-        alive = ptd::shade_scatter<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
+        if constexpr (DIRECT) {
+            const float *lights = c.kargs ? karg_field<const float *>(offsetof(BounceArgs, lights)) : a.lights;
+            const int nlights = c.kargs ? karg_field<int>(offsetof(BounceArgs, nlights)) : a.nlights;
+            if (depth == a.trace_depth) {                      // the final ray (wave-uniform: the whole launch)
+                const int target = ptd::direct_target(lights, nlights, c.iter0 + (int)tr.smp, tr.pixel, depth - 1);
+                if (t > 0.0f && geom == target) {
+                    const float *m = c.acc.mats + mat * ptd::MAT_WORDS;
+                    ps.c = ptd::mul(ps.c, ptd::scale(ptd::mk(m[0], m[1], m[2]), m[9]));
+                } else {
+                    ps.c = ptd::mk(0.0f, 0.0f, 0.0f);
+                }
+            } else {
+                alive = ptd::shade_scatter<GLOSSY, true>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
+                                                         depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr, lights, nlights);
+            }
+        } else {
+            alive = ptd::shade_scatter<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
                                    depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr);
+        }
         if (!ENV && !alive) end_path();
     }
     // ---- survivors append to the wave's packed run (wave64 ballot + popcount rank) ----
@@ -252,7 +273,7 @@ __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &
     if (tr.active) tile_result(q, par, c.acc, a.scene.tris, tr.mb, t, nrm, mat, outside, geom);
     // OWN: the launch plan admits scenes of up to OWN_MAX_GEOMS primitives, so geom + 1 fits the pid's four bits
     tile_shade<COMPACT, MESH, SORT, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
-                                           OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u);
+                                           OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom);
 }
 
 // The tiles [first, first + count) of one wave's run at one bounce, two in flight (see the intersection stages

@@ -1050,6 +1050,19 @@ int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materi
     return one::pt_probe_shade_scatter_glossy(iter, depth, materials, num_materials, paths, isects, outside, n, deferred);
 }
 int pt_glossy_alpha2(const float *exponents, int count, float *alpha2) { return one::pt_glossy_alpha2(exponents, count, alpha2); }
+int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, pt_light_element *out, int capacity) {
+    return one::pt_light_elements(geoms, num_geoms, materials, num_materials, out, capacity);
+}
+int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, const float *P,
+                           const float *n, const uint32_t *seeds, int count, float *dir, float *weight, int32_t *element) {
+    return one::pt_probe_direct_sample(geoms, num_geoms, materials, num_materials, P, n, seeds, count, dir, weight, element);
+}
+int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                  const uint8_t *outside, const int32_t *hit_geom, int n) {
+    return one::pt_probe_shade_scatter_direct(iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
+                                              hit_geom, n);
+}
 int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const float *alpha2, int n, float *dirs) {
     return one::pt_probe_glossy_lobe(normals, seeds, alpha2, n, dirs);
 }

@@ -103,6 +103,61 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth,
     q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
 }
 
+// PT_DIRECT_LIGHT's sampler through the kernels' own ptd::direct_sample, seeded like k_probe_hemisphere
+__global__ __launch_bounds__(64) void k_probe_direct_sample(const float *__restrict__ lights, int nlights, const float *__restrict__ P,
+                                                             const float *__restrict__ nrm, const uint32_t *__restrict__ seeds, int count,
+                                                             float *__restrict__ dir, float *__restrict__ weight, int32_t *__restrict__ element) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t st = ptd::lcg_seed(seeds[i]);
+    f3 d;
+    float w;
+    int e;
+    (void)ptd::direct_sample(lights, nlights, ptd::mk(P[3 * i], P[3 * i + 1], P[3 * i + 2]), ptd::mk(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), st, d, w, e);
+    dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+    weight[i] = w;
+    element[i] = e;
+}
+
+// k_probe_shade_scatter through the direct form of the shader, as tile_shade<.., SH_DIRECT> calls it at bounce `depth` of a session of
+// traceDepth `trace_depth`: the scatter with last_bounce = (depth == trace_depth - 1), or -- depth == trace_depth -- the final ray's
+// scoring rule on the winning primitive hit_geom[i]
+__global__ __launch_bounds__(64) void k_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const float *__restrict__ mats,
+                                                                    const float *__restrict__ lights, int nlights, pt_path_segment *paths,
+                                                                    const pt_shadeable_intersection *__restrict__ isects,
+                                                                    const uint8_t *__restrict__ outside, const int32_t *__restrict__ hit_geom, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    pt_path_segment p = paths[i];
+    if (p.remainingBounces <= 0) return;
+    const pt_shadeable_intersection x = isects[i];
+    ptd::PathState ps;
+    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
+    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
+    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    bool alive = false;
+    if (depth == trace_depth) {
+        const int target = nlights > 0 ? ptd::direct_target(lights, nlights, iter, p.pixelIndex, depth - 1) : -2;
+        if (x.t > 0.0f && hit_geom[i] == target) {
+            const float *m = mats + x.materialId * ptd::MAT_WORDS;
+            ps.c = ptd::mul(ps.c, ptd::scale(ptd::mk(m[0], m[1], m[2]), m[9]));
+        } else {
+            ps.c = ptd::mk(0.0f, 0.0f, 0.0f);
+        }
+    } else {
+        alive = ptd::shade_scatter<false, true>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
+                                                outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, depth == trace_depth - 1,
+                                                false, nullptr, nullptr, lights, nlights);
+    }
+    pt_path_segment *q = paths + i;
+    if (alive) {
+        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
+        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
+    }
+    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
+    q->remainingBounces = alive ? trace_depth - depth : 0;
+}
+
 // the miss exit's colour through the kernels' own ptd::miss_colour: one lane per (direction, throughput) pair
 __global__ __launch_bounds__(64) void k_probe_environment(const float4 *__restrict__ texels, int n, const float *__restrict__ dirs,
                                                            const float *__restrict__ throughput, int count, float *__restrict__ colour) {
@@ -317,6 +372,86 @@ int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materi
                                   const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
     return probe_shade_scatter("pt_probe_shade_scatter_glossy", true, iter, depth, materials, num_materials, paths, isects, outside, n,
                                deferred);
+}
+
+// the light table of a probe call: pt_init's own functions; -1 with the message set
+static int probe_light_records(const char *who, const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials,
+                               std::vector<float> &rec) {
+    if (num_geoms < 0 || num_materials < 1 || !materials || (num_geoms > 0 && !geoms)) return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    std::vector<pt_light_element> el;
+    const int ne = ptlight::elements(geoms, num_geoms, materials, num_materials, el);
+    if (ne < 0) return fail(PT_ERR_INVALID, "%s: a cube or sphere names a material outside [0, %d)", who, num_materials);
+    if (ne > ptlight::MAX_ELEMENTS) return fail(PT_ERR_INVALID, "%s: %d light elements (at most %d)", who, ne, ptlight::MAX_ELEMENTS);
+    ptlight::records(geoms, el, rec);
+    return ne;
+}
+
+int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, const float *P,
+                           const float *n, const uint32_t *seeds, int count, float *dir, float *weight, int32_t *element) {
+    if (count < 0 || count > (1 << 26) || (count > 0 && (!P || !n || !seeds || !dir || !weight || !element)))
+        return fail(PT_ERR_INVALID, "pt_probe_direct_sample: bad argument");
+    std::vector<float> rec;
+    const int ne = probe_light_records("pt_probe_direct_sample", geoms, num_geoms, materials, num_materials, rec);
+    if (ne < 0) return ne;
+    if (count == 0) return PT_OK;
+    if (ne == 0) {
+        for (int i = 0; i < count; ++i) { dir[3 * i] = dir[3 * i + 1] = dir[3 * i + 2] = 0.0f; weight[i] = 0.0f; element[i] = -1; }
+        return PT_OK;
+    }
+    ProbeBufs b;
+    const float *d_l = (const float *)b.get(rec.size() * 4, rec.data());
+    const float *d_p = (const float *)b.get((size_t)count * 12, P);
+    const float *d_n = (const float *)b.get((size_t)count * 12, n);
+    const uint32_t *d_s = (const uint32_t *)b.get((size_t)count * 4, seeds);
+    float *d_d = (float *)b.get((size_t)count * 12, nullptr);
+    float *d_w = (float *)b.get((size_t)count * 4, nullptr);
+    int32_t *d_e = (int32_t *)b.get((size_t)count * 4, nullptr);
+    if (!d_l || !d_p || !d_n || !d_s || !d_d || !d_w || !d_e) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_direct_sample: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_direct_sample, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_l, ne, d_p, d_n, d_s, count, d_d, d_w, d_e);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(dir, d_d, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(weight, d_w, (size_t)count * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(element, d_e, (size_t)count * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                  const uint8_t *outside, const int32_t *hit_geom, int n) {
+    const char *who = "pt_probe_shade_scatter_direct";
+    if (n < 0 || n > (1 << 26) || num_materials < 1 || trace_depth < 1 || trace_depth > MAX_DEPTH - 1 || depth < 0 || depth > trace_depth ||
+        (n > 0 && (!paths || !isects || !materials)) || (n > 0 && depth == trace_depth && !hit_geom))
+        return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    for (int i = 0; i < n; ++i)
+        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
+            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
+    std::vector<float> rec;
+    const int ne = probe_light_records(who, geoms, num_geoms, materials, num_materials, rec);
+    if (ne < 0) return ne;
+    if (n == 0) return PT_OK;
+    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
+    pack_materials(materials, num_materials, mrec.data(), false);
+    ProbeBufs b;
+    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
+    const float *d_l = ne > 0 ? (const float *)b.get(rec.size() * 4, rec.data()) : nullptr;
+    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
+    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
+    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
+    const int32_t *d_hit = hit_geom ? (const int32_t *)b.get((size_t)n * 4, hit_geom) : nullptr;
+    if (!d_mats || (ne > 0 && !d_l) || !d_paths || !d_isects || (outside && !d_outside) || (hit_geom && !d_hit)) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
+    }
+    hipLaunchKernelGGL(k_probe_shade_scatter_direct, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, trace_depth, d_mats, d_l, ne,
+                       d_paths, d_isects, d_outside, d_hit, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
 }
 
 int pt_glossy_alpha2(const float *exponents, int count, float *alpha2) {

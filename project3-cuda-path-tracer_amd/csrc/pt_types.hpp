@@ -356,13 +356,19 @@ struct BounceArgs {
     // shading kernels, where a path misses; sessions without a map launch the others.
     const float4 *env;
     int env_n;
+    // ... and behind them PT_DIRECT_LIGHT's light element table, ptd::LIGHT_WORDS dwords per element;
+    // nlights == 0: the session has no flag or no light to sample.  Read by the DIRECT instantiations of k_bounce, which such
+    // a session launches for its last two bounces only.
+    const float *lights;
+    int nlights;
 };
 
 // the shading kernels' variant switch (template parameter SH of k_bounce, k_iteration, k_shade_sorted, k_shade_sorted_w): the
 // launch plan picks the instantiation, so a session that uses neither runs the code it ran before they existed
 enum : int {
     SH_ENV = 1,        // the session has an environment map
-    SH_GLOSSY = 2      // the session has PT_GLOSSY
+    SH_GLOSSY = 2,     // the session has PT_GLOSSY
+    SH_DIRECT = 4      // bounces D - 1 and D of a PT_DIRECT_LIGHT session (k_bounce only)
 };
 
 // what k_intersect needs to generate bounce 0's camera rays itself (sorted batches: no k_raygen, no pool to read)

@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ptmi355.h"
@@ -65,6 +66,7 @@ static inline const char *pt_experiment(const char *name) {
 #include "pt_types.hpp"
 #include "pt_bvh.hpp"
 #include "pt_cull.hpp"
+#include "pt_lights.hpp"
 #include "pt_kernels.hpp"
 
 #include "pt_h_session.hpp"

@@ -6,7 +6,10 @@
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
-//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy]
+//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct]
+//
+// --direct: PT_DIRECT_LIGHT -- the last bounce of a path that hits a diffuse surface aims a final ray at a sampled point of an
+// emissive cube or sphere (DEPTH + 1 bounces; include/ptmi355.h).  scenes/cornell_two_lamps.txt.
 //
 // --glossy: PT_GLOSSY -- a mirror or dielectric whose material has SPECEX > 0 scatters about a sampled microfacet normal (a GGX
 // lobe of alpha^2 = 2 / (SPECEX + 2); include/ptmi355.h).  Without it SPECEX is ignored (scenes/cornell_glossy.txt then renders
@@ -69,7 +72,7 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -101,6 +104,7 @@ int main(int argc, char **argv) {
         else if (a == "--bvh") flags |= PT_MESH_BVH;
         else if (a == "--aa") flags |= PT_AA_JITTER;
         else if (a == "--glossy") flags |= PT_GLOSSY;
+        else if (a == "--direct") flags |= PT_DIRECT_LIGHT;
         else if (a == "--lens" && i + 2 < argc) { lens_radius = (float)atof(argv[++i]); focal_distance = (float)atof(argv[++i]); }
         else if (a == "--pfm") pfm = true;
         else if (a == "--save-sum") save_sum = true;
