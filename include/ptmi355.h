@@ -213,6 +213,19 @@ enum pt_flags {
                                     do not carry the winning primitive; extending them is a later change), with
                                     trace_depth > 63 (pt_stats::live has 64 entries; pt_set_camera refuses that depth
                                     likewise) and with more than 1024 light elements.  PT_FAKE_SHADER ignores the flag. */
+    PT_TEXTURES      = 1u << 14, /* opt-in: texture mapping.  A material may carry a CUBE TEXTURE (pt_set_texture): at a hit on
+                                    a sphere or cube the texel that the object-space hit point reads multiplies material.color
+                                    -- at the emitter exit and in the diffuse multiply ("texture mapping" below; DESIGN.md
+                                    section 6.19).  specular.color, every draw, origins and directions are untouched; hits on
+                                    meshes, on materials without a texture and misses are as without the flag; a flagged
+                                    session with no texture set is the plain session bit for bit and launches its kernels.
+                                    While a texture is set the session runs a kernel per bounce, whatever PTMI355_WHOLE_MAX
+                                    says: the one-launch kernel has no textured form.  Honoured by the fused pipelines (with
+                                    and without PT_COMPACT, the fused form of PT_SORT_MATERIAL, meshes with and without
+                                    PT_MESH_BVH).  Refused by pt_init (PT_ERR_INVALID) with PT_UNFUSED, with PT_CACHE_FIRST,
+                                    with a PT_SORT_MATERIAL session that would take the two-kernel form (their intersection
+                                    planes do not carry the winning primitive) and with PT_DIRECT_LIGHT (the textured form of
+                                    the direct kernels is a later change).  PT_FAKE_SHADER ignores the flag. */
     PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after
@@ -306,6 +319,34 @@ int pt_get_environment(float *texels, int capacity_texels, int *n);
 /* host-only (no GPU): the texel index the specification assigns to each of `count` directions (dirs: count x 3 floats) in
  * a map of n x n texels per face (n in [1, 1024]), -1 where it assigns none */
 int pt_environment_texel(const float *dirs, int count, int n, int32_t *index);
+
+/* ---- texture mapping (PT_TEXTURES): one cube texture per material, on spheres and cubes -------------------------------------
+ * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/texture_model.py is the numpy form,
+ * and the device's result equals it bit for bit).  A cube texture is 6 * n * n RGB float32 texels,
+ * index ((face * n + j) * n + i) * 3, n in [1, 1024]: the layout of pt_set_environment.  At a hit with t > 0 on primitive g
+ * of type PT_SPHERE or PT_CUBE whose material m has a texture T of size n:
+ *   P = getPointOnRay's point, as the shader computes it;  q = multiplyMV(g.inverseTransform, (P, 1));
+ *   k = the texel pt_environment_texel assigns to q (major-axis ties to the earlier axis, face = 2 * axis + (negative ? 1 : 0),
+ *       the other two components in x, y, z order without mirroring, nearest texel, clamped; -1 for a zero or NaN point);
+ *   mcol = k >= 0 ? (color.x * T[k].r, color.y * T[k].g, color.z * T[k].b) : color
+ * and mcol stands exactly where material.color stands: the emitter exit (colour *= mcol * emittance) and the diffuse multiply.
+ * For a cube this is planar mapping of the face that was hit, for a sphere the cube-sphere mapping.  Mirrors and dielectrics
+ * look as before (specular.color has no texture).  Meshes have no parametrisation: their hits read material.color as it is.
+ * pt_gbuffer, pt_denoise and pt_denoise_temporal are unchanged: they filter the textured running sum (demodulating by albedo
+ * is out of scope).  PT_TEXTURES together with PT_DIRECT_LIGHT is a later change.
+ * pt_set_texture: copies the texels to the device(s) -- every context of a session over several devices keeps its own copy;
+ * texels == NULL or n == 0 removes that material's texture.  Session state: it survives pt_set_camera and pt_clear_image and
+ * ends with pt_free.  The call synchronises the session and discards the PT_LOOKAHEAD windows, as pt_set_environment does, and
+ * leaves the accumulation buffer alone.
+ * pt_get_texture: the contract of pt_get_environment, per material.
+ * PT_ERR_INVALID (both): before pt_init; a session without PT_TEXTURES; material outside [0, num_materials); n outside
+ * [0, 1024]; texels == NULL with n > 0. */
+int pt_set_texture(int material, const float *texels, int n);
+int pt_get_texture(int material, float *texels, int capacity_texels, int *n);
+/* host-only (no GPU): the texel index k of the steps above for each of `count` (primitive hit_geom[i], world point points[3 i ..])
+ * pairs in a texture of n x n texels per face; -1 where the specification assigns none, and for mesh primitives.
+ * PT_ERR_INVALID: a negative count, a null array with count > 0, a hit_geom entry outside [0, num_geoms), n outside [1, 1024]. */
+int pt_texture_texel(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n, int32_t *index);
 
 /* ---- glossy reflection and frosted glass (PT_GLOSSY): SPECEX gives the specular surfaces a GGX lobe ------------------------
  * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/glossy_model.py is the numpy form,
@@ -584,6 +625,19 @@ int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materi
  * texels as for pt_set_environment.  PT_ERR_INVALID: count < 0, a null array with count > 0, n outside [0, 1024], texels == NULL
  * with n > 0.  count == 0 launches nothing. */
 int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour);
+/* pt_probe_texture: PT_TEXTURES' lookup and multiply (above) through the function the kernels call, one lane per record:
+ * colour_out = colour_in * T[k], or colour_in where k < 0 or the primitive is a mesh.  No session is needed; count == 0 launches
+ * nothing.  PT_ERR_INVALID: the refusals of pt_texture_texel, texels == NULL, count above 2^26.
+ * pt_probe_shade_scatter_textured: pt_probe_shade_scatter's signature, contract and refusals through the textured form of
+ * shade_scatter as the kernels of a PT_TEXTURES session call it, with the primitives (geoms, hit_geom: n int32, -1 for records with
+ * t <= 0) and a texture table as parallel arrays: tex_texels (all textures back to back), tex_n[num_materials] (0 = none),
+ * tex_offset[num_materials] (in texels).  A record with t > 0 must name a primitive inside the table. */
+int pt_probe_texture(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, const float *texels, int n,
+                     const float *colour_in, float *colour_out);
+int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                    const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                    const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                    const int32_t *tex_n, const int32_t *tex_offset);
 /* pt_probe_direct_sample: PT_DIRECT_LIGHT's sampler (above; csrc/pt_device.hpp: direct_sample) on the device through the function
  * the kernels call, one lane per record: for each of `count` (P, n, engine seed) triples (P, n: count x 3 floats; seeded like
  * pt_probe_hemisphere) the direction (count x 3), the weight and the element picked, on the light table of the scene given as for

@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     set_environment, get_environment, gradient_cubemap, environment_texel, probe_environment,
     glossy_alpha2, probe_glossy_lobe, probe_shade_scatter_glossy,
     PT_DIRECT_LIGHT, LIGHT_DT, light_elements, probe_direct_sample, probe_shade_scatter_direct,
+    PT_TEXTURES, set_texture, get_texture, checker_cubemap, texture_texel, probe_texture, probe_shade_scatter_textured,
 )
 from .build import build  # noqa: F401
 from . import sharding  # noqa: F401,E402

@@ -41,6 +41,7 @@ PT_SHARED_IMAGE = 512
 PT_LOOKAHEAD = 2048         # pt_trace traces ahead of its caller (include/ptmi355.h)
 PT_GLOSSY = 4096            # SPECEX gives mirrors and dielectrics a GGX lobe (include/ptmi355.h)
 PT_DIRECT_LIGHT = 8192      # the last bounce aims a final ray at a sampled light (include/ptmi355.h)
+PT_TEXTURES = 16384         # a cube texture per material tints spheres and cubes (include/ptmi355.h)
 BVH_NODE_WORDS = 16
 
 
@@ -188,6 +189,12 @@ def library():
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_probe_shade_scatter_direct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.pt_set_texture.argtypes = [C.c_int, C.c_void_p, C.c_int]
+            L.pt_get_texture.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+            L.pt_texture_texel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            L.pt_probe_texture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_probe_shade_scatter_textured.argtypes = L.pt_probe_shade_scatter.argtypes + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                                                              C.c_void_p, C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -358,6 +365,95 @@ def probe_environment(texels, dirs, throughput):
     out = np.zeros((len(d), 3), dtype=np.float32)
     _chk(library().pt_probe_environment(_p(t), n, _p(d), _p(c), len(d), _p(out)))
     return out
+
+
+def set_texture(material, texels):
+    """The cube texture of one material (include/ptmi355.h: pt_set_texture): [6, n, n, 3] float32, indexed [face, j, i]; None
+    removes it.  Sessions initialised with PT_TEXTURES.  The running sum is not touched."""
+    if texels is None:
+        _chk(library().pt_set_texture(int(material), None, 0))
+        return
+    t, n = _cube_texels(texels)
+    _chk(library().pt_set_texture(int(material), _p(t), n))
+
+
+def get_texture(material):
+    """That material's cube texture as it was set, [6, n, n, 3] float32, or None."""
+    n = C.c_int(0)
+    L = library()
+    rc = L.pt_get_texture(int(material), None, 0, C.byref(n))     # the size: PT_OK with n = 0 when none is set
+    if n.value == 0:
+        _chk(rc)
+        return None
+    out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
+    _chk(L.pt_get_texture(int(material), _p(out), 6 * n.value * n.value, C.byref(n)))
+    return out
+
+
+def checker_cubemap(n, cells, colour0, colour1):
+    """A checkerboard for set_texture, [6, n, n, 3] float32: texel [face, j, i] takes colour0 or colour1 by the parity of
+    i * cells // n + j * cells // n + face -- the integer rule of the scene format's `CHECKER` line (host/pthost.h)."""
+    n, cells = int(n), int(cells)
+    if n < 1 or n > 1024 or cells < 1 or cells > 1024:
+        raise PtError("checker_cubemap: n = %d, cells = %d outside [1, 1024]" % (n, cells))
+    col = np.stack([np.asarray(colour0, dtype=np.float32).reshape(3), np.asarray(colour1, dtype=np.float32).reshape(3)])
+    k = np.arange(n, dtype=np.int64) * cells // n
+    odd = (k[None, None, :] + k[None, :, None] + np.arange(6, dtype=np.int64)[:, None, None]) & 1      # [face, j, i]
+    return np.ascontiguousarray(col[odd])
+
+
+def texture_texel(geoms, hit_geom, points, n):
+    """Host-only: the texel index [count] int32 the specification assigns to each (primitive, world point) pair in a texture of
+    n x n texels per face (include/ptmi355.h: pt_texture_texel); -1 where it assigns none, and for mesh primitives."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    h = np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    if len(h) != len(pts):
+        raise PtError("texture_texel: %d primitives, %d points" % (len(h), len(pts)))
+    out = np.zeros(len(h), dtype=np.int32)
+    _chk(library().pt_texture_texel(_p(g), len(g), _p(h), _p(pts), len(h), int(n), _p(out)))
+    return out
+
+
+def probe_texture(geoms, hit_geom, points, texels, colour_in):
+    """The texture lookup and multiply on the device through the function the kernels call (include/ptmi355.h: pt_probe_texture):
+    colour_in * T[k] per component, or colour_in where there is no texel; [count, 3] float32."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    h = np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(colour_in, dtype=np.float32).reshape(-1, 3)
+    if len(h) != len(pts) or len(c) != len(pts):
+        raise PtError("probe_texture: %d primitives, %d points, %d colours" % (len(h), len(pts), len(c)))
+    t, n = _cube_texels(texels)
+    out = np.zeros((len(h), 3), dtype=np.float32)
+    _chk(library().pt_probe_texture(_p(g), len(g), _p(h), _p(pts), len(h), _p(t), n, _p(c), _p(out)))
+    return out
+
+
+def probe_shade_scatter_textured(iter, depth, materials, paths, isects, geoms, hit_geom, textures, outside=None, deferred=False):
+    """probe_shade_scatter through the textured form of the shader, as the kernels of a PT_TEXTURES session call it
+    (include/ptmi355.h: pt_probe_shade_scatter_textured).  hit_geom: the winning primitive per pair (-1 for t <= 0);
+    textures: {material: [6, n, n, 3] float32}."""
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    p = np.array(paths, dtype=PATH_DT, copy=True, order="C").reshape(-1)
+    x = np.ascontiguousarray(isects, dtype=ISECT_DT).reshape(-1)
+    o = None if outside is None else np.ascontiguousarray(outside, dtype=np.uint8).reshape(-1)
+    h = np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    if len(x) != len(p) or len(h) != len(p) or (o is not None and len(o) != len(p)):
+        raise PtError("probe_shade_scatter_textured: %d paths, %d intersections, %d primitives" % (len(p), len(x), len(h)))
+    tn = np.zeros(len(m), dtype=np.int32)
+    toff = np.zeros(len(m), dtype=np.int32)
+    parts, total = [], 0
+    for mat in sorted(textures or {}):
+        t, n = _cube_texels(textures[mat])
+        tn[mat], toff[mat] = n, total
+        parts.append(t)
+        total += len(t)
+    tex = np.ascontiguousarray(np.concatenate(parts)) if parts else None
+    _chk(library().pt_probe_shade_scatter_textured(int(iter), int(depth), _p(m), len(m), _p(p), _p(x), _p(o), len(p), 1 if deferred else 0,
+                                                   _p(g), len(g), _p(h), _p(tex), _p(tn), _p(toff)))
+    return p
 
 
 def trace_batch(iter0, count, host_image=None):

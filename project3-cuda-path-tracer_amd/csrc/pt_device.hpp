@@ -549,6 +549,40 @@ PTD f3 miss_colour(f3 throughput, f3 d, const float4 *texels, int n) {
 }
 
 // ---------------------------------------------------------------------------
+// texture mapping (PT_TEXTURES): a cube texture per material tints material.color at a hit
+// ---------------------------------------------------------------------------
+// steps 2-3: the texel of an n x n-per-face cube texture that the world point P reads on the primitive whose
+// inverseTransform is `inv` (4 columns x 3 rows, as in the geom record): q = multiplyMV(inverseTransform, (P, 1)) as
+// mv_point computes it, then env_texel(q) unchanged.  Host and device.
+template <typename P> __host__ __device__ __forceinline__ int texture_texel(P inv, float px, float py, float pz, int n) {
+    const float qx = (inv[0] * px + inv[3] * py) + (inv[6] * pz + inv[9]);
+    const float qy = (inv[1] * px + inv[4] * py) + (inv[7] * pz + inv[10]);
+    const float qz = (inv[2] * px + inv[5] * py) + (inv[8] * pz + inv[11]);
+    return env_texel(qx, qy, qz, n);
+}
+// steps 2-4 for a hit at P on a sphere or cube: colour * T[k] per component, or the colour as it is where the
+// specification assigns no texel.  T: 16 B {r, g, b, 0} per texel, one load.
+template <typename P> PTD f3 texture_tint(f3 colour, P inv, f3 Pw, const float4 *T, int n) {
+    const int k = texture_texel(inv, Pw.x, Pw.y, Pw.z, n);
+    if (k < 0) return colour;
+    const float4 e = T[k];
+    return mk(colour.x * e.x, colour.y * e.y, colour.z * e.z);
+}
+// mcol of a hit (t > 0) of the ray (o, d) on primitive type `type` with inverseTransform `inv` and material `matId`: the
+// material's colour, tinted when the material has a texture (tab[matId] = {offset in texels, n}; n == 0: none) and the
+// primitive a parametrisation (spheres and cubes).  The gather is divergent: it runs on those lanes only.  What the
+// TEX instantiations of k_bounce and the probes call.
+template <typename P> PTD f3 texture_mcol(const float *mats, int matId, uint32_t type, P inv, f3 o, f3 d, float t,
+                                          const int2 *tab, const float4 *texels) {
+    const float *m = mats + matId * MAT_WORDS;
+    f3 mcol = mk(m[0], m[1], m[2]);
+    const int2 e = tab[matId];
+    if (e.y > 0 && (type == (uint32_t)PT_SPHERE || type == (uint32_t)PT_CUBE))
+        mcol = texture_tint(mcol, inv, point_on_ray(o, d, t), texels + e.x, e.y);
+    return mcol;
+}
+
+// ---------------------------------------------------------------------------
 // direct lighting (PT_DIRECT_LIGHT): the last bounce of a diffuse hit aims at a sampled light
 // ---------------------------------------------------------------------------
 // light element record: 56 dwords, made on the host at pt_init (pt_lights.hpp: ptlight::records) from pt_light_elements'
@@ -643,13 +677,16 @@ PTD int direct_target(const float *lights, int count, int iter, int pixel, int d
 // bounce a hit on a diffuse surface survives with a ray aimed at a sampled point of a light (direct_sample on the table
 // `lights` of `nlights` elements) and its colour multiplied by the sample's weight; a mirror or dielectric ends with colour 0
 // as without it.  Without DIRECT the two arguments are never read.
-template <bool GLOSSY = false, bool DIRECT = false>
+// TEX (the kernels a PT_TEXTURES session launches while a texture is set): `*tex_mcol` stands where
+// material.color stands -- the emitter exit and the diffuse multiply; the caller has computed it (texture_mcol).  Without TEX
+// the argument is never read.
+template <bool GLOSSY = false, bool DIRECT = false, bool TEX = false>
 PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, const float *mats,
                        int iter, int pixel, int depth, bool last_bounce, bool defer_diffuse = false, bool *deferred = nullptr,
-                       bool *missed = nullptr, const float *lights = nullptr, int nlights = 0) {
+                       bool *missed = nullptr, const float *lights = nullptr, int nlights = 0, const f3 *tex_mcol = nullptr) {
     if (t > 0.0f) {
         const float *m = mats + matId * MAT_WORDS;
-        f3 mcol = mk(m[0], m[1], m[2]);
+        f3 mcol = TEX ? *tex_mcol : mk(m[0], m[1], m[2]);
         float emittance = m[9];
         if (emittance > 0.0f) {
             ps.c = mul(ps.c, scale(mcol, emittance));      // pathtrace.cu:247-249

@@ -42,6 +42,8 @@ void pt_free(void) {
     if (R.d_ginfo) (void)hipFree(R.d_ginfo);
     if (R.d_env) (void)hipFree(R.d_env);
     if (R.d_lights) (void)hipFree(R.d_lights);
+    if (R.d_tex) (void)hipFree(R.d_tex);
+    if (R.d_tex_tab) (void)hipFree(R.d_tex_tab);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -173,6 +175,16 @@ static int init_impl(const pt_scene_desc *d) {
         if (ne < 0) return fail(PT_ERR_INTERNAL, "pt_init: light elements");       // (material indices were checked above)
         if (ne > ptlight::MAX_ELEMENTS)
             return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT: %d light elements (at most %d)", ne, ptlight::MAX_ELEMENTS);
+    }
+    // PT_TEXTURES: the lookup needs the winning primitive, as direct lighting does (the two-kernel sort is
+    // refused further down); the textured form of the DIRECT kernels is a later change; PT_FAKE_SHADER ignores the flag
+    if ((d->flags & PT_TEXTURES) && !(d->flags & PT_FAKE_SHADER)) {
+        if (d->flags & PT_UNFUSED)
+            return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_UNFUSED (its intersection planes do not carry the winning primitive)");
+        if (d->flags & PT_CACHE_FIRST)
+            return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_CACHE_FIRST (the first-bounce cache keeps no primitive number)");
+        if (d->flags & PT_DIRECT_LIGHT)
+            return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_DIRECT_LIGHT (the direct kernels have no textured form yet)");
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -389,6 +401,9 @@ static int init_impl(const pt_scene_desc *d) {
     if ((R.flags & PT_DIRECT_LIGHT) && !(R.flags & PT_FAKE_SHADER) && (R.flags & PT_SORT_MATERIAL) && !R.sort_keys)
         return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with the two-kernel form of PT_SORT_MATERIAL, which this "
                                     "session would take (its intersection planes do not carry the winning primitive)");
+    if ((R.flags & PT_TEXTURES) && !(R.flags & PT_FAKE_SHADER) && (R.flags & PT_SORT_MATERIAL) && !R.sort_keys)
+        return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with the two-kernel form of PT_SORT_MATERIAL, which this "
+                                    "session would take (its intersection planes do not carry the winning primitive)");
     if (!light_el.empty()) {
         std::vector<float> lrec;
         ptlight::records(d->geoms, light_el, lrec);
@@ -468,6 +483,8 @@ static int init_impl(const pt_scene_desc *d) {
         };
         int rc = size_for(std::integral_constant<int, 0>{});
         if (rc == PT_OK && R.nlights > 0) rc = size_for(std::integral_constant<int, SH_DIRECT>{});
+        // (a PT_TEXTURES session launches the TEX forms whenever a texture is set: pt_set_texture comes after this)
+        if (rc == PT_OK && (R.flags & PT_TEXTURES) && !(R.flags & PT_FAKE_SHADER)) rc = size_for(std::integral_constant<int, SH_TEX>{});
         if (rc != PT_OK) return rc;
     }
     if (per_cu < 1) per_cu = 1;
@@ -679,6 +696,81 @@ int pt_get_environment(float *texels, int capacity_texels, int *n) {
     return PT_OK;
 }
 
+// Texture mapping (include/ptmi355.h).  Textures are scene state the launches in flight read, like the
+// environment map: the host waits for everything the session has enqueued and the windows traced ahead are void before the
+// device copy is replaced.  The accumulation buffer stays as it is.  Every texture's texels sit back to back in ONE device
+// array, rebuilt per call (a host keeps a handful of textures and sets them once).
+int pt_set_texture(int material, const float *texels, int n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_texture: not initialised");
+    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_set_texture: the session was not initialised with PT_TEXTURES");
+    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_set_texture: material %d outside [0, %d)", material, R.scene.nmats);
+    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_texture: n = %d outside [0, 1024]", n);
+    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_texture: null texels with n = %d", n);
+    if (!texels) n = 0;
+    const int rc = la_discard(LA_HOST);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(R.stream));
+    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
+        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
+        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
+    }
+    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    R.ov_active = false;
+    if (R.tex_n.empty()) { R.tex_n.assign((size_t)R.scene.nmats, 0); R.tex_keep.resize((size_t)R.scene.nmats); }
+    // the new table on the host first: the session keeps its old textures when the device has no room for the new set
+    std::vector<int> tn = R.tex_n;
+    tn[(size_t)material] = n;
+    std::vector<int2> tab((size_t)R.scene.nmats);
+    size_t total = 0;
+    int ntex = 0;
+    for (int m = 0; m < R.scene.nmats; ++m) {
+        tab[(size_t)m] = make_int2((int)total, tn[(size_t)m]);
+        total += (size_t)6 * (size_t)tn[(size_t)m] * (size_t)tn[(size_t)m];
+        if (tn[(size_t)m] > 0) ++ntex;
+    }
+    if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "pt_set_texture: %zu texels in all (at most 2^31 - 1)", total);
+    float4 *d_new = nullptr;
+    if (ntex > 0) {
+        std::vector<float> quad(total * 4);
+        for (int m = 0; m < R.scene.nmats; ++m) {
+            const size_t cnt = (size_t)6 * (size_t)tn[(size_t)m] * (size_t)tn[(size_t)m];
+            const float *src = m == material ? texels : R.tex_keep[(size_t)m].data();
+            float *dst = quad.data() + (size_t)tab[(size_t)m].x * 4;
+            for (size_t k = 0; k < cnt; ++k) { dst[4 * k] = src[3 * k]; dst[4 * k + 1] = src[3 * k + 1]; dst[4 * k + 2] = src[3 * k + 2]; dst[4 * k + 3] = 0.0f; }
+        }
+        if (hipMalloc((void **)&d_new, total * 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PT_ERR_NOMEM, "pt_set_texture: %zu bytes of device memory for the session's textures", total * 16);
+        }
+        HIPCHK(hipMemcpy(d_new, quad.data(), total * 16, hipMemcpyHostToDevice));
+        if (!R.d_tex_tab) HIPCHK(hipMalloc((void **)&R.d_tex_tab, tab.size() * sizeof(int2)));
+        HIPCHK(hipMemcpy(R.d_tex_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
+    }
+    if (R.d_tex) (void)hipFree(R.d_tex);
+    R.d_tex = d_new;
+    R.tex_n = tn;
+    if (n > 0) R.tex_keep[(size_t)material].assign(texels, texels + (size_t)6 * (size_t)n * (size_t)n * 3);
+    else std::vector<float>().swap(R.tex_keep[(size_t)material]);
+    R.ntex = ntex;
+    return PT_OK;
+}
+
+int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_texture: not initialised");
+    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_get_texture: the session was not initialised with PT_TEXTURES");
+    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_get_texture: material %d outside [0, %d)", material, R.scene.nmats);
+    if (!n) return fail(PT_ERR_INVALID, "pt_get_texture: null n");
+    const int tn = R.tex_n.empty() ? 0 : R.tex_n[(size_t)material];
+    *n = tn;
+    if (tn == 0) return PT_OK;
+    const size_t count = (size_t)6 * (size_t)tn * (size_t)tn;
+    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
+        return fail(PT_ERR_INVALID, "pt_get_texture: room for %d texels, the texture has %zu", texels ? capacity_texels : 0, count);
+    memcpy(texels, R.tex_keep[(size_t)material].data(), count * 12);
+    return PT_OK;
+}
+
 int pt_synchronize(void) {
     if (!R.live) return fail(PT_ERR_INVALID, "pt_synchronize: not initialised");
     HIPCHK(hipStreamSynchronize(R.stream));
@@ -717,7 +809,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.epi_enabled &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 

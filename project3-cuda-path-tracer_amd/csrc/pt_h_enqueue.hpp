@@ -34,6 +34,7 @@ BounceArgs bounce_args(int depth) {
     a.persist = R.persist;
     a.env = R.d_env; a.env_n = R.env_n;
     a.lights = R.d_lights; a.nlights = R.nlights;
+    if (R.ntex > 0) { a.tex = R.d_tex; a.tex_tab = R.d_tex_tab; }
     return a;
 }
 
@@ -124,7 +125,8 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // serves them all, no ray generation); the fused kernel reads the results of the mesh pre-pass under PT_MESH_BVH
 // (the hierarchy is never walked inline by k_bounce) and generates bounce 0's rays itself in batches (GEN).
 // the fused compacting kernel that launch_bounce_at picks for (scene in LDS, ray generation, material keys)
-// SH: the shading variant the grid is sized for -- 0, or SH_DIRECT for the last two bounces of a PT_DIRECT_LIGHT session
+// SH: the shading variant the grid is sized for -- 0, SH_DIRECT for the last two bounces of a PT_DIRECT_LIGHT session, or SH_TEX
+// for a PT_TEXTURES session
 template <int MESH, int SH = 0>
 const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false) {
     if constexpr (MESH == MESH_NONE) {
@@ -165,6 +167,12 @@ void launch_k_bounce(const BounceArgs &a) {
     if constexpr (MODE == MODE_FUSED) {
         if (a.nlights > 0 && a.depth >= a.trace_depth - 1) {
             PT_SHADE_DISPATCH_WITH(SH_DIRECT, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
+            return;
+        }
+        // PT_TEXTURES: while the session has a texture set, every bounce launches the TEX forms;
+        // a flagged session without one launches what a session without the flag does (bounce_args leaves tex_tab null)
+        if (a.tex_tab != nullptr) {
+            PT_SHADE_DISPATCH_WITH(SH_TEX, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
             return;
         }
     }
@@ -606,9 +614,10 @@ int enqueue_batch_serial(int iter0, int count) {
     // (one iteration straight into a page-locked host image: the launch hides the PCIe transfer under its tracing, which
     // a kernel per bounce + a copy cannot: worth it for larger frames too -- 3840x2160: 2.49 -> see profiles/r04/ab_percall_4k.log)
     const uint64_t whole_limit = (count == 1 && R.epi_host) ? std::max(R.whole_max_paths, R.whole_max_host_paths) : R.whole_max_paths;
-    // (a PT_DIRECT_LIGHT session with lights to sample runs a kernel per bounce: k_iteration has no DIRECT form)
+    // (a PT_DIRECT_LIGHT session with lights to sample runs a kernel per bounce: k_iteration has no DIRECT form; nor has it a TEX
+    // form -- a PT_TEXTURES session does while a texture is set, decided launch by launch)
     const bool whole = !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && count >= 1 &&
+                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex == 0 && count >= 1 &&
                        (uint64_t)R.map.tile_pixels * (uint64_t)count <= whole_limit;
     int rc = enqueue_begin(iter0, count, false, !whole);
     if (rc) return rc;

@@ -76,6 +76,15 @@ struct Renderer {
     // scene has a cube or sphere that emits: such a session runs trace_depth + 1 bounces (session_bounces), a kernel each.
     float *d_lights = nullptr;
     int nlights = 0;
+    // PT_TEXTURES: at most one cube texture per material.  tex_keep[m] / tex_n[m]: as the caller gave
+    // them (pt_get_texture); d_tex: every texture's texels {r, g, b, 0} back to back, d_tex_tab: per material {offset in texels,
+    // n}, both rebuilt by pt_set_texture.  ntex = textures set; > 0: the session launches the TEX forms of k_bounce, a kernel
+    // per bounce.
+    std::vector<std::vector<float>> tex_keep;
+    std::vector<int> tex_n;
+    float4 *d_tex = nullptr;
+    int2 *d_tex_tab = nullptr;
+    int ntex = 0;
     size_t lds_bytes = 0;
     Control *ctl = nullptr;
     Persist *persist = nullptr;

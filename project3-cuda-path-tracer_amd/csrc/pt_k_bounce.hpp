@@ -160,12 +160,16 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 // D - 1 the last-bounce exit of a diffuse hit aims a final ray at a sampled light (ptd::shade_scatter<.., true>); at D every
 // path ends: with the emitter's colour when its nearest hit is the primitive `geom` it was aimed at, with 0 otherwise -- a
 // miss included, whatever the environment.  The table's pointer and size are read where they are used, like the map's.
+// TEX: a PT_TEXTURES session while a texture is set (k_bounce only) -- a hit on a sphere or cube whose
+// material has a cube texture shades with material.color * texel (ptd::texture_mcol, shade_scatter<.., TEX>).  The gather runs on
+// those lanes only; the two pointers are read from the argument block where a lane hit, like the map's.
 template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = false, int SH = 0>
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
                                            uint32_t n, uint32_t dst_base, uint32_t &packed, uint32_t &traced,
                                            uint32_t key_stride = 0, uint32_t own_bits = 0, int geom = -1) {
-    constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0, DIRECT = (SH & SH_DIRECT) != 0;
+    constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0, DIRECT = (SH & SH_DIRECT) != 0, TEX = (SH & SH_TEX) != 0;
+    static_assert(!(DIRECT && TEX), "pt_init refuses PT_TEXTURES with PT_DIRECT_LIGHT");
     const int lane = c.lane;
     bool alive = false, deferred = false, missed = false;
     ptd::PathState ps;
@@ -213,6 +217,15 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
                 alive = ptd::shade_scatter<GLOSSY, true>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
                                                          depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr, lights, nlights);
             }
+        } else if constexpr (TEX) {
+            f3 mcol = ptd::mk(0.0f, 0.0f, 0.0f);
+            if (t > 0.0f)                                      // (the fused pipelines name the primitive hit; without one, no tint)
+                mcol = ptd::texture_mcol(c.acc.mats, mat, geom >= 0 ? c.acc.ginfo[geom] >> 28 : (uint32_t)PT_TRIANGLE_MESH,
+                                         c.acc.grec + (size_t)(geom >= 0 ? geom : 0) * GREC_WORDS, ro, rd, t,
+                                         c.kargs ? karg_field<const int2 *>(offsetof(BounceArgs, tex_tab)) : a.tex_tab,
+                                         c.kargs ? karg_field<const float4 *>(offsetof(BounceArgs, tex)) : a.tex);
+            alive = ptd::shade_scatter<GLOSSY, false, true>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
+                                   depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr, nullptr, 0, &mcol);
         } else {
             alive = ptd::shade_scatter<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
                                    depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr);

@@ -763,6 +763,19 @@ int pt_get_environment(float *texels, int capacity_texels, int *n) {
     return on_one(0, [&](Worker &) -> int { return one::pt_get_environment(texels, capacity_texels, n); });
 }
 
+// every context shades with the same textures: each keeps its own device copy
+int pt_set_texture(int material, const float *texels, int n) {
+    if (!G.live) return one::pt_set_texture(material, texels, n);
+    const int rc = multi_sync();
+    if (rc) return rc;
+    return on_all([&](Worker &) -> int { return one::pt_set_texture(material, texels, n); });
+}
+
+int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
+    if (!G.live) return one::pt_get_texture(material, texels, capacity_texels, n);
+    return on_one(0, [&](Worker &) -> int { return one::pt_get_texture(material, texels, capacity_texels, n); });
+}
+
 int pt_synchronize(void) {
     if (!G.live) return one::pt_synchronize();
     return multi_sync();
@@ -831,7 +844,9 @@ static int multi_trace(uint8_t *pbo_rgba, int iter0, int count, float *host_imag
     }
     // pathtrace() with the host image and no PBO, one iteration: no exchange at all -- every context's launch writes its
     // own tile's pixels (those whose sum changed) into the caller's image while it traces (pt_trace_mapped)
-    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange &&
+    // (G.direct_ok was asked at pt_init; a PT_TEXTURES session runs a kernel per bounce while a texture is set -- the contexts'
+    // threads are idle between calls, and every context has the same textures)
+    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange && G.w[0]->ctx.ntex == 0 &&
         (G.w[0]->ctx.flags & PT_PIN_IMAGE) && multi_pin(host_image_sum, (size_t)G.npix * 12)) {
         int rc = exchange_settled();
         if (rc) return rc;
@@ -1069,6 +1084,20 @@ int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const floa
 int pt_environment_texel(const float *dirs, int count, int n, int32_t *index) { return one::pt_environment_texel(dirs, count, n, index); }
 int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour) {
     return one::pt_probe_environment(texels, n, dirs, throughput, count, colour);
+}
+int pt_texture_texel(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n, int32_t *index) {
+    return one::pt_texture_texel(geoms, num_geoms, hit_geom, points, count, n, index);
+}
+int pt_probe_texture(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, const float *texels, int n,
+                     const float *colour_in, float *colour_out) {
+    return one::pt_probe_texture(geoms, num_geoms, hit_geom, points, count, texels, n, colour_in, colour_out);
+}
+int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                    const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                    const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                    const int32_t *tex_n, const int32_t *tex_offset) {
+    return one::pt_probe_shade_scatter_textured(iter, depth, materials, num_materials, paths, isects, outside, n, deferred, geoms, num_geoms,
+                                                hit_geom, tex_texels, tex_n, tex_offset);
 }
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
 int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }

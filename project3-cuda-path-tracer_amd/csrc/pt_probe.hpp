@@ -103,6 +103,59 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth,
     q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
 }
 
+// PT_TEXTURES' lookup and multiply through the kernels' own ptd::texture_tint: one lane per (primitive,
+// world point, colour) record; inv: 12 words per primitive (inverseTransform, 4 columns x 3 rows), type: PT_SPHERE / PT_CUBE / mesh
+__global__ __launch_bounds__(64) void k_probe_texture(const float *__restrict__ inv, const int32_t *__restrict__ type, const int32_t *__restrict__ hit_geom,
+                                                       const float *__restrict__ points, int count, const float4 *__restrict__ texels, int n,
+                                                       const float *__restrict__ colour_in, float *__restrict__ colour_out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const int g = hit_geom[i];
+    f3 c = ptd::mk(colour_in[3 * i], colour_in[3 * i + 1], colour_in[3 * i + 2]);
+    if (type[g] == PT_SPHERE || type[g] == PT_CUBE)
+        c = ptd::texture_tint(c, inv + (size_t)g * 12, ptd::mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]), texels, n);
+    colour_out[3 * i] = c.x; colour_out[3 * i + 1] = c.y; colour_out[3 * i + 2] = c.z;
+}
+
+// k_probe_shade_scatter through the textured form of the shader, as tile_shade<.., SH_TEX> calls it: mcol from ptd::texture_mcol on
+// the record's primitive (hit_geom) and the texture table, then shade_scatter<false, false, true>
+__global__ __launch_bounds__(64) void k_probe_shade_scatter_textured(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
+                                                                      const pt_shadeable_intersection *__restrict__ isects,
+                                                                      const uint8_t *__restrict__ outside, int n, int defer,
+                                                                      const float *__restrict__ inv, const int32_t *__restrict__ type,
+                                                                      const int32_t *__restrict__ hit_geom, const float4 *__restrict__ texels,
+                                                                      const int2 *__restrict__ tab) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    pt_path_segment p = paths[i];
+    if (p.remainingBounces <= 0) return;
+    const pt_shadeable_intersection x = isects[i];
+    ptd::PathState ps;
+    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
+    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
+    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    bool deferred = false;
+    f3 mcol = ptd::mk(0.0f, 0.0f, 0.0f);
+    if (x.t > 0.0f) {
+        const int g = hit_geom[i];
+        mcol = ptd::texture_mcol(mats, x.materialId, (uint32_t)type[g], inv + (size_t)g * 12, ps.o, ps.d, x.t, tab, texels);
+    }
+    const bool alive = ptd::shade_scatter<false, false, true>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
+                                                              outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                                              defer != 0, &deferred, nullptr, nullptr, 0, &mcol);
+    if (deferred) {
+        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
+        ps.d = ptd::hemisphere(ps.d, rng);
+    }
+    pt_path_segment *q = paths + i;
+    if (alive) {
+        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
+        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
+    }
+    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
+    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
+}
+
 // PT_DIRECT_LIGHT's sampler through the kernels' own ptd::direct_sample, seeded like k_probe_hemisphere
 __global__ __launch_bounds__(64) void k_probe_direct_sample(const float *__restrict__ lights, int nlights, const float *__restrict__ P,
                                                              const float *__restrict__ nrm, const uint32_t *__restrict__ seeds, int count,
@@ -448,6 +501,128 @@ int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt
     }
     hipLaunchKernelGGL(k_probe_shade_scatter_direct, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, trace_depth, d_mats, d_l, ne,
                        d_paths, d_isects, d_outside, d_hit, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+// ---- texture mapping (PT_TEXTURES) ----
+// the primitives of a probe call as the lookups read them: inverseTransform as 12 words (4 columns x 3 rows) and the type
+static void texture_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &inv, std::vector<int32_t> &type) {
+    inv.assign((size_t)std::max(1, num_geoms) * 12, 0.0f);
+    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
+    for (int g = 0; g < num_geoms; ++g) {
+        for (int c = 0; c < 4; ++c)
+            for (int r = 0; r < 3; ++r) inv[(size_t)g * 12 + c * 3 + r] = geoms[g].inverseTransform.m[c][r];
+        type[(size_t)g] = (int32_t)geoms[g].type;
+    }
+}
+// the refusals pt_texture_texel and pt_probe_texture share; 0 when the arguments are sound
+static int texture_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n) {
+    if (count < 0 || num_geoms < 0 || n < 1 || n > 1024 || (num_geoms > 0 && !geoms) || (count > 0 && (!hit_geom || !points)))
+        return fail(PT_ERR_INVALID, "%s: bad argument (count %d, %d geoms, n %d)", who, count, num_geoms, n);
+    for (int i = 0; i < count; ++i)
+        if (hit_geom[i] < 0 || hit_geom[i] >= num_geoms)
+            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
+    return PT_OK;
+}
+
+int pt_texture_texel(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n, int32_t *index) {
+    const int rc = texture_args("pt_texture_texel", geoms, num_geoms, hit_geom, points, count, n);
+    if (rc) return rc;
+    if (count > 0 && !index) return fail(PT_ERR_INVALID, "pt_texture_texel: null index");
+    std::vector<float> inv;
+    std::vector<int32_t> type;
+    texture_geoms(geoms, num_geoms, inv, type);
+    for (int i = 0; i < count; ++i) {
+        const int g = hit_geom[i];
+        index[i] = (type[(size_t)g] == PT_SPHERE || type[(size_t)g] == PT_CUBE)
+                       ? ptd::texture_texel(inv.data() + (size_t)g * 12, points[3 * i], points[3 * i + 1], points[3 * i + 2], n) : -1;
+    }
+    return PT_OK;
+}
+
+int pt_probe_texture(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, const float *texels, int n,
+                     const float *colour_in, float *colour_out) {
+    const int rc = texture_args("pt_probe_texture", geoms, num_geoms, hit_geom, points, count, n);
+    if (rc) return rc;
+    if (count > (1 << 26) || !texels || (count > 0 && (!colour_in || !colour_out)))
+        return fail(PT_ERR_INVALID, "pt_probe_texture: bad argument (count %d)", count);
+    if (count == 0) return PT_OK;
+    std::vector<float> inv;
+    std::vector<int32_t> type;
+    texture_geoms(geoms, num_geoms, inv, type);
+    const size_t nt = (size_t)6 * (size_t)n * (size_t)n;
+    std::vector<float> quad(nt * 4, 0.0f);                         // the session's device layout: {r, g, b, 0}
+    for (size_t k = 0; k < nt; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    ProbeBufs b;
+    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
+    const float *d_inv = (const float *)b.get(inv.size() * 4, inv.data());
+    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
+    const int32_t *d_hit = (const int32_t *)b.get((size_t)count * 4, hit_geom);
+    const float *d_pts = (const float *)b.get((size_t)count * 12, points);
+    const float *d_in = (const float *)b.get((size_t)count * 12, colour_in);
+    float *d_out = (float *)b.get((size_t)count * 12, nullptr);
+    if (!d_tex || !d_inv || !d_type || !d_hit || !d_pts || !d_in || !d_out) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_texture: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_texture, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_inv, d_type, d_hit, d_pts, count, d_tex, n, d_in, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(colour_out, d_out, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                    const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                    const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                    const int32_t *tex_n, const int32_t *tex_offset) {
+    const char *who = "pt_probe_shade_scatter_textured";
+    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)) ||
+        num_geoms < 0 || (num_geoms > 0 && !geoms) || (n > 0 && !hit_geom) || !tex_n || !tex_offset)
+        return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    for (int i = 0; i < n; ++i) {
+        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
+            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
+        if (isects[i].t > 0.0f && (hit_geom[i] < 0 || hit_geom[i] >= num_geoms))
+            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
+    }
+    size_t total = 0;                                              // texels the table reaches
+    for (int m = 0; m < num_materials; ++m) {
+        if (tex_n[m] < 0 || tex_n[m] > 1024 || (tex_n[m] > 0 && tex_offset[m] < 0))
+            return fail(PT_ERR_INVALID, "%s: material %d has a texture of n = %d at offset %d", who, m, tex_n[m], tex_offset[m]);
+        if (tex_n[m] > 0) total = std::max(total, (size_t)tex_offset[m] + (size_t)6 * (size_t)tex_n[m] * (size_t)tex_n[m]);
+    }
+    if (total > 0 && !tex_texels) return fail(PT_ERR_INVALID, "%s: null tex_texels", who);
+    if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "%s: %zu texels in all (at most 2^31 - 1)", who, total);
+    if (n == 0) return PT_OK;
+    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
+    pack_materials(materials, num_materials, mrec.data(), false);
+    std::vector<float> inv;
+    std::vector<int32_t> type;
+    texture_geoms(geoms, num_geoms, inv, type);
+    std::vector<float> quad(std::max<size_t>(total, 1) * 4, 0.0f);
+    for (size_t k = 0; k < total; ++k) { quad[4 * k] = tex_texels[3 * k]; quad[4 * k + 1] = tex_texels[3 * k + 1]; quad[4 * k + 2] = tex_texels[3 * k + 2]; }
+    std::vector<int2> tab((size_t)num_materials);
+    for (int m = 0; m < num_materials; ++m) tab[(size_t)m] = make_int2(tex_n[m] > 0 ? tex_offset[m] : 0, tex_n[m]);
+    ProbeBufs b;
+    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
+    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
+    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
+    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
+    const float *d_inv = (const float *)b.get(inv.size() * 4, inv.data());
+    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
+    const int32_t *d_hit = (const int32_t *)b.get((size_t)n * 4, hit_geom);
+    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
+    const int2 *d_tab = (const int2 *)b.get(tab.size() * sizeof(int2), tab.data());
+    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside) || !d_inv || !d_type || !d_hit || !d_tex || !d_tab) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
+    }
+    hipLaunchKernelGGL(k_probe_shade_scatter_textured, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
+                       d_outside, n, deferred, d_inv, d_type, d_hit, d_tex, d_tab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
     HIPCHK(hipDeviceSynchronize());

@@ -361,6 +361,11 @@ struct BounceArgs {
     // a session launches for its last two bounces only.
     const float *lights;
     int nlights;
+    // ... and behind them PT_TEXTURES' cube textures: every texture's texels {r, g, b, 0} back to back
+    // and, per material, {offset in texels, n} (n == 0: that material has none).  tex_tab == nullptr: the session has no flag or
+    // no texture set.  Read by the TEX instantiations of k_bounce, which such a session launches for every bounce.
+    const float4 *tex;
+    const int2 *tex_tab;
 };
 
 // the shading kernels' variant switch (template parameter SH of k_bounce, k_iteration, k_shade_sorted, k_shade_sorted_w): the
@@ -368,7 +373,8 @@ struct BounceArgs {
 enum : int {
     SH_ENV = 1,        // the session has an environment map
     SH_GLOSSY = 2,     // the session has PT_GLOSSY
-    SH_DIRECT = 4      // bounces D - 1 and D of a PT_DIRECT_LIGHT session (k_bounce only)
+    SH_DIRECT = 4,     // bounces D - 1 and D of a PT_DIRECT_LIGHT session (k_bounce only)
+    SH_TEX = 8         // every bounce of a PT_TEXTURES session while a texture is set (k_bounce only)
 };
 
 // what k_intersect needs to generate bounce 0's camera rays itself (sorted batches: no k_raygen, no pool to read)

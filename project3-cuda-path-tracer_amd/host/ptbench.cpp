@@ -6,7 +6,11 @@
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
-//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct]
+//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures]
+//
+// --textures: PT_TEXTURES -- the cube textures the scene's TEXTURE blocks declare (pthost.h: pth_scene_texture) are uploaded with
+// pt_set_texture after pathtraceInit; each multiplies its material's colour on spheres and cubes (include/ptmi355.h, DESIGN.md
+// section 6.19).  scenes/cornell_textured.txt.  Without the switch the blocks are loaded and ignored.
 //
 // --direct: PT_DIRECT_LIGHT -- the last bounce of a path that hits a diffuse surface aims a final ray at a sampled point of an
 // emissive cube or sphere (DEPTH + 1 bounces; include/ptmi355.h).  scenes/cornell_two_lamps.txt.
@@ -72,7 +76,7 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -105,6 +109,7 @@ int main(int argc, char **argv) {
         else if (a == "--aa") flags |= PT_AA_JITTER;
         else if (a == "--glossy") flags |= PT_GLOSSY;
         else if (a == "--direct") flags |= PT_DIRECT_LIGHT;
+        else if (a == "--textures") flags |= PT_TEXTURES;
         else if (a == "--lens" && i + 2 < argc) { lens_radius = (float)atof(argv[++i]); focal_distance = (float)atof(argv[++i]); }
         else if (a == "--pfm") pfm = true;
         else if (a == "--save-sum") save_sum = true;
@@ -211,6 +216,19 @@ int main(int argc, char **argv) {
                 }
         if (pt_set_environment(tex.data(), n) != PT_OK) { fprintf(stderr, "pt_set_environment: %s\n", pt_last_error()); return 1; }
         printf("sky: %d x %d x 6 texels\n", n, n);
+    }
+
+    if (flags & PT_TEXTURES) {                            // the scene's TEXTURE blocks (pthost.h: pth_scene_texture)
+        int set = 0;
+        for (int m = 0; m < sc->num_materials; ++m) {
+            const float *tex = nullptr;
+            int n = 0;
+            if (pth_scene_texture(sc, m, &tex, &n) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+            if (n == 0) continue;
+            if (pt_set_texture(m, tex, n) != PT_OK) { fprintf(stderr, "pt_set_texture: %s\n", pt_last_error()); return 1; }
+            ++set;
+        }
+        printf("textures: %d of %d materials\n", set, sc->num_materials);
     }
 
     std::vector<float> image((size_t)W * H * 3, 0.0f);    // scene->state.image

@@ -291,11 +291,47 @@ bool load_obj(const std::string &path, const M4 &T, std::vector<pt_triangle> &ou
     return true;
 }
 
+// what pth_load_scene hands out: the public struct first (its layout is the ABI and does not change), the scene's cube
+// textures (TEXTURE blocks, a format extension) behind it -- per material n (0: none) and 6 * n * n RGB texels
+struct SceneFull {
+    pth_scene pub;
+    int32_t *tex_n;
+    float **tex;
+};
+
+// the cube texture of a `CHECKER <n> <cells> r0 g0 b0 r1 g1 b1` line: texel (face, j, i) takes colour 0 or 1 by the parity of
+// i * cells / n + j * cells / n + face, in integer arithmetic
+bool checker_texture(const std::vector<std::string> &t, std::vector<float> &out, int &n) {
+    if (t.size() < 9) return false;
+    n = atoi(t[1].c_str());
+    const int cells = atoi(t[2].c_str());
+    if (n < 1 || n > 1024 || cells < 1 || cells > 1024) return false;
+    float col[2][3];
+    for (int k = 0; k < 6; ++k) col[k / 3][k % 3] = (float)atof(t[3 + k].c_str());
+    out.resize((size_t)6 * n * n * 3);
+    for (int face = 0; face < 6; ++face)
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) {
+                const int odd = (i * cells / n + j * cells / n + face) & 1;
+                float *o = out.data() + ((size_t)(face * n + j) * n + i) * 3;
+                o[0] = col[odd][0]; o[1] = col[odd][1]; o[2] = col[odd][2];
+            }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *pth_last_error(void) { return g_err; }
+
+int pth_scene_texture(const pth_scene *s, int material, const float **texels, int *n) {
+    if (!s || !n || material < 0 || material >= s->num_materials) { snprintf(g_err, sizeof g_err, "pth_scene_texture: bad argument"); return -1; }
+    const SceneFull *f = reinterpret_cast<const SceneFull *>(s);
+    *n = f->tex_n[material];
+    if (texels) *texels = f->tex[material];
+    return 0;
+}
 
 void pth_build_geom_matrices(pt_geom *g) {
     // The object-to-world matrix the reference's loader builds (utilities.cpp:65-72): translate * (rotX * rotY * rotZ) *
@@ -322,7 +358,10 @@ pth_scene *pth_load_scene(const char *path) {
     whole << file.rdbuf();
     Lines fp(whole.str());
     Builder b;
-    pth_scene *s = (pth_scene *)calloc(1, sizeof(pth_scene));
+    std::vector<std::pair<int, std::vector<float>>> textures;        // TEXTURE blocks in file order: (material, texels)
+    std::vector<int> texture_n;                                       // ... and their sizes
+    SceneFull *full = (SceneFull *)calloc(1, sizeof(SceneFull));
+    pth_scene *s = &full->pub;
     std::string dir(path);
     size_t slash = dir.find_last_of('/');
     dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
@@ -424,6 +463,37 @@ pth_scene *pth_load_scene(const char *path) {
             camera.pixelLength[1] = 2 * yscaled / (float)camera.resolution[1];
             camera.view = P(normalize(sub(U(camera.lookAt), U(camera.position))));
             have_cam = true;
+        } else if (tok[0] == "TEXTURE") {                             // format extension (the reference's loader skips the block)
+            // TEXTURE <material id>, then one line: CHECKER <n> <cells> r0 g0 b0 r1 g1 b1 | PFM <file> (n wide, 6 n tall, faces 0..5
+            // top to bottom, relative to the scene's directory)
+            if (tok.size() < 2 || atoi(tok[1].c_str()) < 0) { snprintf(g_err, sizeof g_err, "TEXTURE needs a material id"); goto fail; }
+            const int mat = atoi(tok[1].c_str());
+            fp.next(line);
+            std::vector<std::string> t = tokens_of(line);
+            std::vector<float> tex;
+            int n = 0;
+            if (!t.empty() && t[0] == "CHECKER") {
+                if (!checker_texture(t, tex, n)) { snprintf(g_err, sizeof g_err, "TEXTURE %d: bad CHECKER line (n and cells in [1, 1024], two colours)", mat); goto fail; }
+            } else if (t.size() >= 2 && t[0] == "PFM") {
+                const std::string fullp = t[1][0] == '/' ? t[1] : dir + "/" + t[1];
+                int fw = 0, fh = 0;
+                {   // the size from the header; the floats through pth_read_pfm
+                    FILE *f = fopen(fullp.c_str(), "rb");
+                    char magic[3] = {0, 0, 0};
+                    if (!f || fscanf(f, "%2s %d %d", magic, &fw, &fh) != 3 || strcmp(magic, "PF") != 0) fw = fh = 0;
+                    if (f) fclose(f);
+                }
+                if (fw < 1 || fw > 1024 || fh != 6 * fw) {
+                    snprintf(g_err, sizeof g_err, "TEXTURE %d: %s is not a colour PFM n wide and 6 n tall, n in [1, 1024]", mat, fullp.c_str()); goto fail;
+                }
+                n = fw;
+                tex.resize((size_t)6 * n * n * 3);
+                if (pth_read_pfm(fullp.c_str(), tex.data(), fw, fh) != 0) goto fail;
+            } else {
+                snprintf(g_err, sizeof g_err, "TEXTURE %d: expected CHECKER or PFM", mat); goto fail;
+            }
+            textures.push_back(std::make_pair(mat, tex));
+            texture_n.push_back(n);
         }
     }
     if (!have_cam || b.mats.empty()) { snprintf(g_err, sizeof g_err, "scene %s has no CAMERA or no MATERIAL", path); goto fail; }
@@ -431,6 +501,20 @@ pth_scene *pth_load_scene(const char *path) {
         if (b.geoms[i].materialid < 0 || b.geoms[i].materialid >= (int)b.mats.size()) {
             snprintf(g_err, sizeof g_err, "OBJECT %zu links material %d of %zu", i, b.geoms[i].materialid, b.mats.size()); goto fail;
         }
+    for (size_t i = 0; i < textures.size(); ++i)
+        if (textures[i].first >= (int)b.mats.size()) {
+            snprintf(g_err, sizeof g_err, "TEXTURE %d names a material of %zu", textures[i].first, b.mats.size()); goto fail;
+        }
+    full->tex_n = (int32_t *)calloc(b.mats.size(), sizeof(int32_t));
+    full->tex = (float **)calloc(b.mats.size(), sizeof(float *));
+    for (size_t i = 0; i < textures.size(); ++i) {                     // a later block for the same material replaces the earlier
+        const int m = textures[i].first;
+        const std::vector<float> &tex = textures[i].second;
+        free(full->tex[m]);
+        full->tex[m] = (float *)malloc(tex.size() * sizeof(float));
+        memcpy(full->tex[m], tex.data(), tex.size() * sizeof(float));
+        full->tex_n[m] = (int32_t)texture_n[i];
+    }
     s->camera = s->camera_loaded;
     orbit_recompute(s->camera);
     s->num_geoms = (int32_t)b.geoms.size(); s->num_materials = (int32_t)b.mats.size();
@@ -446,13 +530,16 @@ pth_scene *pth_load_scene(const char *path) {
     g_err[0] = 0;
     return s;
 fail:
-    free(s);
+    free(full);
     return NULL;
 }
 
 void pth_free_scene(pth_scene *s) {
     if (!s) return;
-    free(s->geoms); free(s->materials); free(s->triangles); free(s->meshes); free(s);
+    SceneFull *full = reinterpret_cast<SceneFull *>(s);
+    if (full->tex) for (int32_t m = 0; m < s->num_materials; ++m) free(full->tex[m]);
+    free(full->tex); free(full->tex_n);
+    free(s->geoms); free(s->materials); free(s->triangles); free(s->meshes); free(full);
 }
 
 // main.cpp:78-99 + image.cpp:22-39

@@ -30,6 +30,14 @@ typedef struct pth_scene {
 pth_scene *pth_load_scene(const char *path);
 void pth_free_scene(pth_scene *s);
 const char *pth_last_error(void);
+/* The scene's cube textures (format extension; include/ptmi355.h "texture mapping"): a top-level block
+ *   TEXTURE <material id>
+ *   CHECKER <n> <cells> r0 g0 b0 r1 g1 b1   |   PFM <file>
+ * CHECKER: texel (face, j, i) takes colour 0 or 1 by the parity of i * cells / n + j * cells / n + face (integer arithmetic);
+ * PFM: a colour PFM n wide and 6 n tall, faces 0..5 top to bottom, relative to the scene's directory.  *n = the size of that
+ * material's texture (0: none), *texels = its 6 * n * n RGB triples (owned by the scene; NULL when none).  0, or -1 for a bad
+ * argument. */
+int pth_scene_texture(const pth_scene *s, int material, const float **texels, int *n);
 
 /* utilityCore::buildTransformationMatrix (utilities.cpp:65-72) + glm::inverse + glm::inverseTranspose
  * (scene.cpp:82-85), GLM 0.9.6.3 operation order */

@@ -64,6 +64,7 @@ def host_library():
         L.pth_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
         L.pth_write_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
         L.pth_read_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
+        L.pth_scene_texture.argtypes = [C.POINTER(_PthScene), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -92,6 +93,14 @@ def load_scene(path):
         scene = Scene(geoms, mats, cam, s.trace_depth, iterations=s.iterations, triangles=tris, meshes=meshes,
                       name=s.image_name.decode())
         scene.camera_loaded = cam_loaded
+        # the scene's TEXTURE blocks (host/pthost.h: pth_scene_texture): {material: [6, n, n, 3] float32}
+        scene.textures = {}
+        for m in range(s.num_materials):
+            tex, n = C.c_void_p(None), C.c_int(0)
+            if L.pth_scene_texture(p, m, C.byref(tex), C.byref(n)) != 0:
+                raise PtError("load_scene(%s): %s" % (path, L.pth_last_error().decode()))
+            if n.value > 0:
+                scene.textures[m] = _copy(tex.value, 6 * n.value * n.value * 3, np.dtype("<f4")).reshape(6, n.value, n.value, 3)
     finally:
         L.pth_free_scene(p)
     return scene
