@@ -332,8 +332,9 @@ int pt_environment_texel(const float *dirs, int count, int n, int32_t *index);
  * and mcol stands exactly where material.color stands: the emitter exit (colour *= mcol * emittance) and the diffuse multiply.
  * For a cube this is planar mapping of the face that was hit, for a sphere the cube-sphere mapping.  Mirrors and dielectrics
  * look as before (specular.color has no texture).  Meshes have no parametrisation: their hits read material.color as it is.
- * pt_gbuffer, pt_denoise and pt_denoise_temporal are unchanged: they filter the textured running sum (demodulating by albedo
- * is out of scope).  PT_TEXTURES together with PT_DIRECT_LIGHT is a later change.
+ * pt_gbuffer, pt_denoise and pt_denoise_temporal are unchanged: they filter the textured running sum, unless the host asks
+ * them to demodulate by the first hit's albedo (pt_set_denoise_albedo, below).  PT_TEXTURES together with PT_DIRECT_LIGHT is a
+ * later change.
  * pt_set_texture: copies the texels to the device(s) -- every context of a session over several devices keeps its own copy;
  * texels == NULL or n == 0 removes that material's texture.  Session state: it survives pt_set_camera and pt_clear_image and
  * ends with pt_free.  The call synchronises the session and discards the PT_LOOKAHEAD windows, as pt_set_environment does, and
@@ -522,6 +523,42 @@ int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_param
  * rgb W*H*3 floats, length W*H floats (0 = no history for the pixel) */
 int pt_history(float *rgb, float *length);
 int pt_history_reset(void);       /* forget everything; the next temporal call equals pt_denoise bit for bit */
+
+/* ---- the filters on irradiance: first-hit albedo demodulation ---------------------------------------------------------------
+ * A texture on a flat wall has one normal and one plane: only the colour stop keeps its texels apart, and at 16-64 samples
+ * that stop sits inside the noise.  With the switch on, pt_denoise and pt_denoise_temporal filter colour / albedo and return
+ * filtered * albedo (DESIGN.md section 6.20 has the complete specification; tests/albedo_model.py is its numpy form, equal bit
+ * for bit).  All arithmetic binary32, one rounding per operation in the order written, no FMA.
+ * Albedo plane A[P], for pixel P of the current camera, from the G-buffer's first hit (pinhole, unjittered, production cull and
+ * exact tests, the winner by strict less with the lowest index on ties):
+ *   a miss (!(t > 0)): (1, 1, 1);  a material with hasReflective > 0 or hasRefractive > 0 (the shader's tests): (1, 1, 1) --
+ *   such a pixel shows another surface and material.color does not multiply it;
+ *   every other hit, diffuse or emitter: v = mcol, the colour the shader puts where material.color stands -- the texture
+ *   section's mcol (P = getPointOnRay's point, not the G-buffer's position) on a sphere or cube while the session launches its
+ *   textured kernels (PT_TEXTURES without PT_FAKE_SHADER, at least one texture set), plain material.color everywhere else
+ *   (meshes, PT_FAKE_SHADER, no texture set);  then per component a = fminf(fmaxf(v, 2^-6), 2^6) -- C's fmaxf / fminf: a NaN
+ *   gives 2^-6.  (A texel below 1/64 therefore receives up to 1/64 of its neighbours' irradiance; the upper clamp keeps
+ *   inf * 0 out.)
+ * The plane is recomputed when the camera's bytes differ from those it was made for and after a pt_set_texture that changed
+ * a texel or a size; it is kept otherwise.  12 bytes per pixel, allocated on first use, released by pt_free.
+ * pt_denoise with the switch on, levels >= 1: c_0[P] = (sum[P] / (float)iter) / A[P] per component (two divides, the mean
+ * first); the levels as above on c -- the colour stop compares demodulated colours, the sigmas are unchanged --; the result is
+ * c_levels[P] * A[P], and the RGBA bytes come from that.  levels = 0 returns the mean untouched.
+ * pt_denoise_temporal with the switch on: steps 1 and 2 are unchanged -- history, blend, cur.C and pt_history stay in
+ * modulated colour (a diffuse surface's colour, texture included, does not depend on the view) --; step 3 filters c0 / A and
+ * multiplies back as above; levels = 0 returns c0.
+ * Where A is 1 in every component of every pixel the results equal those of the switch off bit for bit (x / 1 * 1), and
+ * switching on and off again restores them bit for bit.  A switched-on call still launches one kernel per level (the first
+ * divides as it loads, the last multiplies as it stores) and the G-buffer kernel only when the plane is stale.
+ * pt_set_denoise_albedo: 0 / 1; off after pt_init.  Session state: it survives pt_set_camera, pt_clear_image and
+ * pt_set_texture and ends with pt_free.  pt_albedo: the plane of the current camera as the filter would use it, whatever the
+ * switch says (rgb: W*H*3 floats, host; NULL computes the plane and copies nothing).  Both are synchronous, sit on the
+ * session's stream behind everything enqueued, and like pt_gbuffer read the session and change nothing in it: no
+ * PT_LOOKAHEAD window is discarded and no counter moves.
+ * PT_ERR_INVALID (both): before pt_init; a tiled session (tile_count > 1) or one over several devices; enable outside {0, 1}.
+ * Out of scope: demodulating by specular.color or by the albedo seen through a mirror or glass; history kept demodulated. */
+int pt_set_denoise_albedo(int enable);
+int pt_albedo(float *rgb);
 int pt_get_stats(pt_stats *stats);
 /* rays traced since pt_init, read from the device-side counter (includes
  * asynchronous batches); synchronises the stream.  Negative = pt_status. */

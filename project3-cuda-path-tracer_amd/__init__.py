@@ -11,7 +11,7 @@ from .binding import (  # noqa: F401
     trace_end, clear_image, version, has_experiments, set_profiling, get_profile, STAGES, total_rays, counters, cull_boxes, num_devices, exchange_transport, tri_bounds, tri_records,
     set_image, probe_rng, probe_sincos, probe_sincos_sums, probe_hemisphere, probe_shade_scatter, probe_sqrt, probe_clock, probe_tri_form, probe_own_surface_plan,
     gbuffer, denoise, denoised_device_ptr, DenoiseParams,
-    denoise_temporal, history, history_reset, TemporalParams,
+    denoise_temporal, history, history_reset, TemporalParams, set_denoise_albedo, albedo,
     set_environment, get_environment, gradient_cubemap, environment_texel, probe_environment,
     glossy_alpha2, probe_glossy_lobe, probe_shade_scatter_glossy,
     PT_DIRECT_LIGHT, LIGHT_DT, light_elements, probe_direct_sample, probe_shade_scatter_direct,

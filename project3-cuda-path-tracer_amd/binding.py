@@ -177,6 +177,8 @@ def library():
             L.pt_denoised_device_image.restype = C.c_void_p
             L.pt_denoise_temporal.argtypes = [C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_int, C.c_void_p, C.c_void_p]
             L.pt_history.argtypes = [C.c_void_p, C.c_void_p]
+            L.pt_set_denoise_albedo.argtypes = [C.c_int]
+            L.pt_albedo.argtypes = [C.c_void_p]
             L.pt_set_environment.argtypes = [C.c_void_p, C.c_int]
             L.pt_get_environment.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
             L.pt_environment_texel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -582,6 +584,22 @@ def history():
 def history_reset():
     """Forget the history: the next denoise_temporal() equals denoise() bit for bit."""
     _chk(library().pt_history_reset())
+
+
+def set_denoise_albedo(on):
+    """The filters' first-hit albedo demodulation on / off (include/ptmi355.h: pt_set_denoise_albedo): denoise() and
+    denoise_temporal() filter colour / albedo and return filtered * albedo.  Off after pathtraceInit."""
+    _chk(library().pt_set_denoise_albedo(1 if on is True else 0 if on is False else int(on)))
+
+
+def albedo():
+    """The albedo plane of the current camera as the filters would use it (include/ptmi355.h: pt_albedo): [npix, 3] float32."""
+    if _scene is None:
+        _chk(library().pt_albedo(None))                                     # raises "not initialised"
+    w, h = _scene.resolution
+    out = np.zeros((w * h, 3), dtype=np.float32)
+    _chk(library().pt_albedo(_p(out)))
+    return out
 
 
 def denoised_device_ptr():

@@ -65,6 +65,7 @@ void pt_free(void) {
     for (int k = 0; k < 2; ++k) if (R.dn_plane[k]) (void)hipFree(R.dn_plane[k]);
     if (R.dn_rgba) (void)hipFree(R.dn_rgba);
     if (R.gb_alt) (void)hipFree(R.gb_alt);
+    if (R.alb_mem) (void)hipFree(R.alb_mem);       // (R = Renderer{} below clears the switch)
     for (int k = 0; k < 2; ++k) {
         if (R.tp_c[k]) (void)hipFree(R.tp_c[k]);
         if (R.tp_n[k]) (void)hipFree(R.tp_n[k]);
@@ -747,6 +748,10 @@ int pt_set_texture(int material, const float *texels, int n) {
         if (!R.d_tex_tab) HIPCHK(hipMalloc((void **)&R.d_tex_tab, tab.size() * sizeof(int2)));
         HIPCHK(hipMemcpy(R.d_tex_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
     }
+    // the albedo plane follows the table: stale unless this call left every texel as it was
+    const int old_n = R.tex_n[(size_t)material];
+    if (old_n != n || (n > 0 && memcmp(R.tex_keep[(size_t)material].data(), texels, (size_t)6 * (size_t)n * (size_t)n * 12) != 0))
+        R.alb_valid = false;
     if (R.d_tex) (void)hipFree(R.d_tex);
     R.d_tex = d_new;
     R.tex_n = tn;

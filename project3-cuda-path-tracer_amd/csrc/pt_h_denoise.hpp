@@ -19,39 +19,71 @@ static int denoise_session_ok(const char *who) {
     return PT_OK;
 }
 
-// the G-buffer of R.cam: computed once per camera, kept until the camera's bytes differ
-static int ensure_gbuffer(void) {
+// the G-buffer of R.cam: computed once per camera, kept until the camera's bytes differ.  `albedo` (pt_albedo, the filters
+// of a session with pt_set_denoise_albedo(1)): the albedo plane of R.cam as well -- made by the same
+// launch (the ALB form of k_gbuffer, which rewrites the G-buffer of an unchanged camera in place with the values it holds),
+// kept until the camera's bytes differ or pt_set_texture changes the session's table (alb_valid).
+static int ensure_gbuffer(bool albedo = false) {
     if (!R.gb_mem) HIPCHK(hipMalloc((void **)&R.gb_mem, (size_t)R.npix * 2 * sizeof(float4)));
+    if (albedo && !R.alb_mem) HIPCHK(hipMalloc((void **)&R.alb_mem, (size_t)R.npix * 3 * sizeof(float)));
     const bool same = memcmp(&R.gb_cam, &R.cam, sizeof R.cam) == 0;
-    if (R.gb_valid && same) return PT_OK;
+    const bool need_alb = albedo && !(R.alb_valid && memcmp(&R.alb_cam, &R.cam, sizeof R.cam) == 0);
+    if (R.gb_valid && same && !need_alb) return PT_OK;
     // the record of the last temporal call refers to this allocation and to another camera: it keeps it, the new camera's
     // G-buffer goes to the second allocation (which exists: only a temporal call sets tp_cur)
     if (!same && R.tp_cur && R.tp_gb == R.gb_mem) std::swap(R.gb_mem, R.gb_alt);
     float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
     const int blocks = std::min(R.grid, (R.npix + BLOCK - 1) / BLOCK);
-    PT_MESH_DISPATCH(hipLaunchKernelGGL((k_gbuffer<MESH, SLDS>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream, gA, gB, R.scene,
-                                        R.cam, R.map));
+    if (need_alb) {
+        // tinted only while the session's bounce kernels are launched in their textured form (bounce_args, launch_k_bounce)
+        const bool textured = R.ntex > 0 && !(R.flags & PT_FAKE_SHADER);
+        const GbAlbedo alb{R.alb_mem, textured ? (const int2 *)R.d_tex_tab : (const int2 *)nullptr,
+                           textured ? (const float4 *)R.d_tex : (const float4 *)nullptr};
+        PT_MESH_DISPATCH(hipLaunchKernelGGL((k_gbuffer<MESH, SLDS, true>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream, gA, gB,
+                                            R.scene, R.cam, R.map, alb));
+    } else {
+        const GbAlbedo alb{nullptr, nullptr, nullptr};
+        PT_MESH_DISPATCH(hipLaunchKernelGGL((k_gbuffer<MESH, SLDS, false>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream, gA, gB,
+                                            R.scene, R.cam, R.map, alb));
+    }
     HIPCHK(hipGetLastError());
     R.dn_launches[0]++;
     R.gb_cam = R.cam; R.gb_valid = true;
+    if (need_alb) { R.alb_cam = R.cam; R.alb_valid = true; }
     return PT_OK;
 }
 
 // level l of the filter: step 2^l, from the accumulation buffer (l = 0: the mean is formed as it is read) or the plane the
 // level before wrote, into plane l & 1.  `c0` (l = 0 of a temporal call): the blended colours, read as they are.
-static int launch_atrous(int l, float div, float sc2, float sn2, float sp2, uint8_t *rgba, const float *c0 = nullptr) {
+// `dm` (a session with pt_set_denoise_albedo(1)): AT_DIV at level 0 -- the staged form divides by the
+// albedo plane as it loads, a temporal call's c0 included (div = 1.0f) --, AT_MUL at the last level; the levels between
+// are the launches of a session without the switch.  Still one launch per level.
+static int launch_atrous(int l, float div, float sc2, float sn2, float sp2, uint8_t *rgba, const float *c0 = nullptr, int dm = 0) {
     const float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
     const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
     const int out = l & 1;
-    if (l == 0 && c0)
+    const float *none = nullptr, *alb = R.alb_mem;
+    if (l == 0 && (dm & AT_DIV)) {
+        const float *src = c0 ? c0 : (const float *)R.image;
+        const float d = c0 ? 1.0f : div;
+        if (dm & AT_MUL)
+            hipLaunchKernelGGL((k_atrous<true, AT_DIV | AT_MUL>), grid, dim3(BLOCK), 0, R.stream, src, gA, gB, R.dn_plane[out], rgba, R.map.W,
+                               R.map.H, 1, d, sc2, sn2, sp2, alb);
+        else
+            hipLaunchKernelGGL((k_atrous<true, AT_DIV>), grid, dim3(BLOCK), 0, R.stream, src, gA, gB, R.dn_plane[out], rgba, R.map.W,
+                               R.map.H, 1, d, sc2, sn2, sp2, alb);
+    } else if (l == 0 && c0)
         hipLaunchKernelGGL(k_atrous<false>, grid, dim3(BLOCK), 0, R.stream, c0, gA, gB, R.dn_plane[out], rgba, R.map.W, R.map.H, 1, 1.0f,
-                           sc2, sn2, sp2);
+                           sc2, sn2, sp2, none);
     else if (l == 0)
         hipLaunchKernelGGL(k_atrous<true>, grid, dim3(BLOCK), 0, R.stream, (const float *)R.image, gA, gB, R.dn_plane[out], rgba,
-                           R.map.W, R.map.H, 1, div, sc2, sn2, sp2);
+                           R.map.W, R.map.H, 1, div, sc2, sn2, sp2, none);
+    else if (dm & AT_MUL)
+        hipLaunchKernelGGL((k_atrous<false, AT_MUL>), grid, dim3(BLOCK), 0, R.stream, (const float *)R.dn_plane[out ^ 1], gA, gB,
+                           R.dn_plane[out], rgba, R.map.W, R.map.H, 1 << l, 1.0f, sc2, sn2, sp2, alb);
     else
         hipLaunchKernelGGL(k_atrous<false>, grid, dim3(BLOCK), 0, R.stream, (const float *)R.dn_plane[out ^ 1], gA, gB, R.dn_plane[out],
-                           rgba, R.map.W, R.map.H, 1 << l, 1.0f, sc2, sn2, sp2);
+                           rgba, R.map.W, R.map.H, 1 << l, 1.0f, sc2, sn2, sp2, none);
     HIPCHK(hipGetLastError());
     R.dn_launches[1]++;
     return PT_OK;
@@ -74,6 +106,29 @@ int pt_gbuffer(float *normals, float *positions, float *t, int32_t *material) {
         if (positions) { positions[3 * i + 0] = b.x; positions[3 * i + 1] = b.y; positions[3 * i + 2] = b.z; }
         if (material) memcpy(&material[i], &b.w, 4);
     }
+    return PT_OK;
+}
+
+// the bits launch_atrous gets for level l of `levels` in a session whose switch is on
+static int albedo_bits(int l, int levels) { return R.alb_on ? ((l == 0 ? AT_DIV : 0) | (l == levels - 1 ? AT_MUL : 0)) : 0; }
+
+// pt_set_denoise_albedo / pt_albedo.  Like pt_gbuffer they read the session and change nothing in
+// it: the switch is a word of the host's, the plane a buffer of its own behind everything enqueued on the launch stream.
+int pt_set_denoise_albedo(int enable) {
+    int rc = denoise_session_ok("pt_set_denoise_albedo");
+    if (rc) return rc;
+    if (enable != 0 && enable != 1) return fail(PT_ERR_INVALID, "pt_set_denoise_albedo: enable %d is neither 0 nor 1", enable);
+    R.alb_on = enable == 1;
+    return PT_OK;
+}
+
+int pt_albedo(float *rgb) {
+    int rc = denoise_session_ok("pt_albedo");
+    if (rc) return rc;
+    rc = ensure_gbuffer(true);
+    if (rc) return rc;
+    if (rgb) HIPCHK(hipMemcpyAsync(rgb, R.alb_mem, (size_t)R.npix * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
     return PT_OK;
 }
 
@@ -122,11 +177,11 @@ int pt_denoise(const pt_denoise_params *params, int iter, float *host_rgb, uint8
         HIPCHK(hipGetLastError());
         R.dn_launches[2]++;
     } else {
-        rc = ensure_gbuffer();
+        rc = ensure_gbuffer(R.alb_on);
         if (rc) return rc;
         for (int l = 0; l < levels; ++l) {
             out = l & 1;
-            rc = launch_atrous(l, div, sc2[l], sn2, sp2, l == levels - 1 ? rgba : (uint8_t *)nullptr);
+            rc = launch_atrous(l, div, sc2[l], sn2, sp2, l == levels - 1 ? rgba : (uint8_t *)nullptr, nullptr, albedo_bits(l, levels));
             if (rc) return rc;
         }
     }
@@ -214,7 +269,7 @@ int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_param
     uint8_t *rgba = host_rgba ? R.dn_rgba : (uint8_t *)nullptr;
     rc = ensure_temporal();
     if (rc) return rc;
-    rc = ensure_gbuffer();                      // (a camera other than cur's: into the allocation cur does not refer to)
+    rc = ensure_gbuffer(R.alb_on && levels > 0);   // (a camera other than cur's: into the allocation cur does not refer to)
     if (rc) return rc;
     if (R.tp_cur && memcmp(&R.tp_cam, &R.cam, sizeof R.cam) != 0) {
         rc = launch_reproject(R.tp_cam, R.tp_gb, R.tp_c[R.tp_k], R.tp_n[R.tp_k], *temporal);
@@ -228,7 +283,7 @@ int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_param
     int out = 0;
     for (int l = 0; l < levels; ++l) {
         out = l & 1;
-        rc = launch_atrous(l, 1.0f, sc2[l], sn2, sp2, l == levels - 1 ? rgba : (uint8_t *)nullptr, c0);
+        rc = launch_atrous(l, 1.0f, sc2[l], sn2, sp2, l == levels - 1 ? rgba : (uint8_t *)nullptr, c0, albedo_bits(l, levels));
         if (rc) return rc;
     }
     R.dn_result = levels == 0 ? c0 : R.dn_plane[out];
@@ -265,13 +320,15 @@ int pt_history_reset(void) {
 // session's stream.  After one pt_denoise(params, iter) as warm-up, `reps` rounds of: k_gbuffer (forced), every level of
 // k_atrous, and a device-to-device hipMemcpyAsync of the 56 bytes per pixel one level moves (colour + two G-buffer planes
 // in, colour out: the streaming yardstick).  ms[rep * (levels + 2) + k]: k = 0 the G-buffer, 1 .. levels the levels,
-// levels + 1 the copy.  The result of the last round is a valid pt_denoise result.
+// levels + 1 the copy.  The result of the last round is a valid pt_denoise result.  In a session with
+// pt_set_denoise_albedo(1) the rounds are the switched-on call's: the ALB form of k_gbuffer (forced), the first and last level
+// in their demodulating forms, and 68 bytes per pixel in the copy (what such a first or last level moves).
 int denoise_times(const pt_denoise_params *params, int iter, int reps, float *ms) {
     int rc = one::pt_denoise(params, iter, nullptr, nullptr);
     if (rc) return rc;
     if (reps < 1 || !ms || params->levels < 1) return fail(PT_ERR_INVALID, "ptdbg_denoise_times: reps >= 1, levels >= 1 and a buffer");
     const int levels = params->levels, items = levels + 2;
-    const size_t copy_bytes = (size_t)R.npix * 56;
+    const size_t copy_bytes = (size_t)R.npix * (R.alb_on ? 68 : 56);
     void *src = nullptr, *dst = nullptr;
     std::vector<hipEvent_t> ev((size_t)2 * items, nullptr);
     auto cleanup = [&] {
@@ -287,14 +344,14 @@ int denoise_times(const pt_denoise_params *params, int iter, int reps, float *ms
         const float sn2 = params->sigma_normal * params->sigma_normal, sp2 = params->sigma_position * params->sigma_position;
         for (int rep = -1; rep < reps; ++rep) {              // (-1: the copy's warm-up)
             HIPCHK(hipEventRecord(ev[0], R.stream));
-            R.gb_valid = false;
-            int r = ensure_gbuffer();
+            R.gb_valid = false; R.alb_valid = false;
+            int r = ensure_gbuffer(R.alb_on);
             if (r) return r;
             HIPCHK(hipEventRecord(ev[1], R.stream));
             for (int l = 0; l < levels; ++l) {
                 const float s = params->sigma_color * ldexpf(1.0f, -l);
                 HIPCHK(hipEventRecord(ev[2 * (l + 1)], R.stream));
-                r = launch_atrous(l, (float)iter, s * s, sn2, sp2, nullptr);
+                r = launch_atrous(l, (float)iter, s * s, sn2, sp2, nullptr, nullptr, albedo_bits(l, levels));
                 if (r) return r;
                 HIPCHK(hipEventRecord(ev[2 * (l + 1) + 1], R.stream));
             }

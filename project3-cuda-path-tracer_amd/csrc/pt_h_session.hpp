@@ -232,6 +232,11 @@ struct Renderer {
     uint8_t *dn_rgba = nullptr;
     float *dn_result = nullptr;
     uint64_t dn_launches[3] = {0, 0, 0};   // k_gbuffer / k_atrous / k_denoise_mean launches since pt_init (ptdbg_denoise)
+    // pt_set_denoise_albedo / pt_albedo: the switch, and the albedo plane (packed float3) of camera
+    // alb_cam -- one per session, written by the ALB form of k_gbuffer, stale once pt_set_texture changes the table
+    bool alb_on = false, alb_valid = false;
+    float *alb_mem = nullptr;
+    pt_camera alb_cam{};
     // pt_denoise_temporal (pt_h_denoise.hpp), allocated by the first temporal call.  `cur` = what the
     // last temporal call saw: its camera, its G-buffer (tp_gb: gb_mem or gb_alt -- when the camera changes while cur refers
     // to gb_mem, ensure_gbuffer swaps the two allocations instead of overwriting it), the blended colour tp_c[tp_k] and its

@@ -14,9 +14,19 @@ namespace {
 // the same loop with another output).  Whole-frame sessions only: local pixel = pixelIndex.
 // (Register budget: PT_MIN_WAVES waves per SIMD like k_cache_first, except with the every-triangle loop inline, which does
 // not fit 128 registers -- k_cache_first spills 28-33 there --: two waves per SIMD for a kernel that runs once per camera.)
-template <int MESH, bool SLDS>
+// ALB (pt_set_denoise_albedo / pt_albedo): the same launch also writes the albedo plane the filter
+// demodulates by, gC[pixel] = {a.r, a.g, a.b} -- PACKED float3 like every colour plane k_atrous reads (12 bytes per pixel
+// where a float4 would move 16, and the staging loop of k_atrous reads it beside the running sum with the same index).
+// A miss and a specular hit (the shader's own tests: hasReflective > 0, hasRefractive > 0) give 1; every other hit the
+// colour the shader puts where material.color stands -- ptd::texture_mcol called as tile_shade<.., SH_TEX> calls it while
+// the session launches its textured kernels (alb.tab != nullptr), plain material.color otherwise, no gather -- clamped per
+// component to [2^-6, 2^6] (fmaxf first: a NaN gives 2^-6).  The instantiations without ALB do not touch `alb`.
+constexpr float ALB_MIN = 0.015625f, ALB_MAX = 64.0f;
+struct GbAlbedo { float *plane; const int2 *tab; const float4 *tex; };
+__device__ __forceinline__ float albedo_clamp(float v) { return fminf(fmaxf(v, ALB_MIN), ALB_MAX); }
+template <int MESH, bool SLDS, bool ALB = false>
 __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? 2 : PT_MIN_WAVES) void k_gbuffer(float4 *__restrict__ gA, float4 *__restrict__ gB, SceneDev sc,
-                                                                  pt_camera cam, TileMap map) {
+                                                                  pt_camera cam, TileMap map, GbAlbedo alb) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
     const LdsCarve lc = carve_lds(lds_raw, sc, SLDS);
     const SceneAcc acc = stage_scene<SLDS>(lc.scene, sc);
@@ -32,8 +42,9 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? 2 : PT_MIN_WAVES) void 
         cull_scene<MESH>(sc, acc, q, 0, lc.tri, active, ro, rd, mb, nullptr);
         drain_to(q, acc, q.total);
         if (active) {
-            float t; f3 nrm; int mat, outside;
-            tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside);
+            float t; f3 nrm; int mat, outside, geom = -1;
+            if constexpr (ALB) tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside, geom);
+            else tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside);
             float4 a = make_float4(0.0f, 0.0f, 0.0f, -1.0f), b = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
             if (t > 0.0f) {
                 // position = origin + direction * t, per component one multiply then one add (not getPointOnRay)
@@ -41,6 +52,21 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? 2 : PT_MIN_WAVES) void 
                 b = make_float4(ro.x + rd.x * t, ro.y + rd.y * t, ro.z + rd.z * t, __int_as_float(mat));
             }
             gA[j] = a; gB[j] = b;
+            if constexpr (ALB) {
+                f3 v = ptd::mk(1.0f, 1.0f, 1.0f);
+                if (t > 0.0f) {
+                    const float *m = acc.mats + mat * ptd::MAT_WORDS;
+                    if (!(m[6] > 0.0f) && !(m[7] > 0.0f)) {
+                        if (alb.tab != nullptr)
+                            v = ptd::texture_mcol(acc.mats, mat, acc.ginfo[geom] >> 28, acc.grec + (size_t)geom * GREC_WORDS, ro, rd, t,
+                                                  alb.tab, alb.tex);
+                        else
+                            v = ptd::mk(m[0], m[1], m[2]);
+                        v = ptd::mk(albedo_clamp(v.x), albedo_clamp(v.y), albedo_clamp(v.z));
+                    }
+                }
+                alb.plane[3 * (size_t)j + 0] = v.x; alb.plane[3 * (size_t)j + 1] = v.y; alb.plane[3 * (size_t)j + 2] = v.z;
+            }
         }
     }
 }
@@ -82,12 +108,20 @@ __device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, f
 // 12-byte entries, so consecutive lanes are 3 banks apart and a wave's read is conflict-free.  Dividing per tap instead (78
 // divides per pixel, the same quotients) measured 0.92 against 0.72 ms at 3840x2160 (profiles/denoise/ab_level0_forms.json).
 // `rgba` (the last level, optional): tonemap_pixel of the result with divisor 1.
+// DM (pt_set_denoise_albedo), two independent bits, `alb` = the albedo plane A (packed float3):
+//   AT_DIV (FIRST only): the staging loop also loads A[Q] and stores (cin[Q] / div) / A[Q] -- 12 more bytes and 3 more
+//     divides per staged pixel, the taps unchanged.  A temporal call's blended plane comes through here with div = 1.0f
+//     (x / 1.0f = x exactly) instead of the per-tap loads of k_atrous<false>: dividing per tap would be 78 divides per pixel.
+//   AT_MUL (the last level): out = (s / cum) * A[P], and `rgba` from that.
+// DM = 0 does not touch `alb`: the two instantiations of a session without the switch.
 constexpr int AT_LW = 64 + 4, AT_LH = WAVES + 4;       // a workgroup's tile with the halo of a step-1 level
-template <bool FIRST>
+constexpr int AT_DIV = 1, AT_MUL = 2;
+template <bool FIRST, int DM = 0>
 __global__ __launch_bounds__(BLOCK) void k_atrous(const float *__restrict__ cin, const float4 *__restrict__ gA,
                                                   const float4 *__restrict__ gB, float *__restrict__ cout,
                                                   uint8_t *__restrict__ rgba, int W, int H, int step, float div,
-                                                  float sc2, float sn2, float sp2) {
+                                                  float sc2, float sn2, float sp2, const float *__restrict__ alb) {
+    static_assert(FIRST || !(DM & AT_DIV), "the divide on load belongs to the staged form");
     __shared__ float mean_lds[FIRST ? AT_LH * AT_LW * 3 : 1];
     const int tx = (int)(threadIdx.x & 63), ty = (int)(threadIdx.x >> 6);
     const int x = (int)blockIdx.x * 64 + tx;
@@ -99,7 +133,13 @@ __global__ __launch_bounds__(BLOCK) void k_atrous(const float *__restrict__ cin,
             const int gx = x0 + lx, gy = y0 + ly;
             if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
                 const size_t Q = (size_t)gy * (size_t)W + (size_t)gx;
-                mean_lds[3 * i + 0] = cin[3 * Q + 0] / div; mean_lds[3 * i + 1] = cin[3 * Q + 1] / div; mean_lds[3 * i + 2] = cin[3 * Q + 2] / div;
+                if constexpr ((DM & AT_DIV) != 0) {
+                    const float sr0 = cin[3 * Q + 0], sg0 = cin[3 * Q + 1], sb0 = cin[3 * Q + 2];
+                    const float ar = alb[3 * Q + 0], ag = alb[3 * Q + 1], ab = alb[3 * Q + 2];
+                    mean_lds[3 * i + 0] = (sr0 / div) / ar; mean_lds[3 * i + 1] = (sg0 / div) / ag; mean_lds[3 * i + 2] = (sb0 / div) / ab;
+                } else {
+                    mean_lds[3 * i + 0] = cin[3 * Q + 0] / div; mean_lds[3 * i + 1] = cin[3 * Q + 1] / div; mean_lds[3 * i + 2] = cin[3 * Q + 2] / div;
+                }
             }
         }
         __syncthreads();
@@ -145,7 +185,8 @@ __global__ __launch_bounds__(BLOCK) void k_atrous(const float *__restrict__ cin,
             cum = cum + wt;
         }
     }
-    const float outr = sr / cum, outg = sg / cum, outb = sb / cum;      // cum >= 9/64: the centre tap has w = 1
+    float outr = sr / cum, outg = sg / cum, outb = sb / cum;            // cum >= 9/64: the centre tap has w = 1
+    if constexpr ((DM & AT_MUL) != 0) { outr = outr * alb[3 * P + 0]; outg = outg * alb[3 * P + 1]; outb = outb * alb[3 * P + 2]; }
     cout[3 * P + 0] = outr; cout[3 * P + 1] = outg; cout[3 * P + 2] = outb;
     if (rgba) reinterpret_cast<uchar4 *>(rgba)[P] = tonemap_pixel(outr, outg, outb, 1);
 }

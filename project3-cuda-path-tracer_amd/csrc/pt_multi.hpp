@@ -934,6 +934,14 @@ int pt_denoise_temporal(const pt_denoise_params *params, const pt_temporal_param
     if (G.live) return fail(PT_ERR_INVALID, "pt_denoise_temporal: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
     return one::pt_denoise_temporal(params, temporal, iter, host_rgb, host_rgba);
 }
+int pt_set_denoise_albedo(int enable) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_set_denoise_albedo: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_set_denoise_albedo(enable);
+}
+int pt_albedo(float *rgb) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_albedo: this session tiles the frame over %d devices; the albedo plane needs a single-device session", G.K);
+    return one::pt_albedo(rgb);
+}
 int pt_history(float *rgb, float *length) {
     if (G.live) return fail(PT_ERR_INVALID, "pt_history: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
     return one::pt_history(rgb, length);

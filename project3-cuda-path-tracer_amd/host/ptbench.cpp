@@ -6,7 +6,11 @@
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
-//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures]
+//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures] [--albedo]
+//
+// --albedo (needs --denoise): pt_set_denoise_albedo(1) before the first filtered picture -- every one of them, the --move /
+// --temporal ones included, is filtered as colour / first-hit albedo and multiplied back (include/ptmi355.h, DESIGN.md section
+// 6.20), which keeps the texels of --textures apart where the colour stop alone cannot.
 //
 // --textures: PT_TEXTURES -- the cube textures the scene's TEXTURE blocks declare (pthost.h: pth_scene_texture) are uploaded with
 // pt_set_texture after pathtraceInit; each multiplies its material's colour on spheres and cubes (include/ptmi355.h, DESIGN.md
@@ -76,14 +80,14 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures] [--albedo]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
     unsigned flags = PT_COMPACT | PT_PIN_IMAGE | PT_HOST_SPARSE;      // `image` below lives until pt_free and is only read here
     bool pfm = false, save_sum = false, per_call = false, lookahead = true;
     int warmup = 64;
-    bool denoise = false;
+    bool denoise = false, albedo = false;
     pt_denoise_params dn = {0, 0.0f, 0.0f, 0.0f};
     bool move = false;
     float move_by[3] = {0.0f, 0.0f, 0.0f};
@@ -110,6 +114,7 @@ int main(int argc, char **argv) {
         else if (a == "--glossy") flags |= PT_GLOSSY;
         else if (a == "--direct") flags |= PT_DIRECT_LIGHT;
         else if (a == "--textures") flags |= PT_TEXTURES;
+        else if (a == "--albedo") albedo = true;
         else if (a == "--lens" && i + 2 < argc) { lens_radius = (float)atof(argv[++i]); focal_distance = (float)atof(argv[++i]); }
         else if (a == "--pfm") pfm = true;
         else if (a == "--save-sum") save_sum = true;
@@ -165,6 +170,7 @@ int main(int argc, char **argv) {
     pth_scene *sc = pth_load_scene(argv[1]);
     if (!sc) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     if (iters < 0) iters = sc->iterations;
+    if (albedo && !denoise) { fprintf(stderr, "--albedo needs --denoise (the filter it switches to irradiance)\n"); return 1; }
     if (move && !denoise) { fprintf(stderr, "--move needs --denoise (the filter its pictures go through)\n"); return 1; }
     if (per_call) {
         flags |= PT_PIN_IMAGE | PT_HOST_SPARSE | (lookahead ? PT_LOOKAHEAD : 0u);
@@ -298,6 +304,7 @@ int main(int argc, char **argv) {
     pth_image_to_rgb8(image.data(), W, H, (float)iteration, rgb.data());
     if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     printf("Saved %s.\n", name);
+    if (albedo && pt_set_denoise_albedo(1) != PT_OK) { fprintf(stderr, "pt_set_denoise_albedo: %s\n", pt_last_error()); return 1; }
     if (denoise) {
         // the first call computes the G-buffer of this camera as well; the second is the filter alone
         std::vector<float> mean((size_t)W * H * 3);
@@ -306,8 +313,8 @@ int main(int argc, char **argv) {
         const auto d1 = std::chrono::steady_clock::now();
         if (pt_denoise(&dn, iteration, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise: %s\n", pt_last_error()); return 1; }
         const auto d2 = std::chrono::steady_clock::now();
-        printf("denoise: %d levels, sigmas %g / %g / %g: %.3f ms with the G-buffer, %.3f ms the filter alone (with the copy of the result)\n",
-               dn.levels, dn.sigma_color, dn.sigma_normal, dn.sigma_position, std::chrono::duration<double, std::milli>(d1 - d0).count(),
+        printf("denoise: %d levels, sigmas %g / %g / %g%s: %.3f ms with the G-buffer, %.3f ms the filter alone (with the copy of the result)\n",
+               dn.levels, dn.sigma_color, dn.sigma_normal, dn.sigma_position, albedo ? ", albedo demodulated" : "", std::chrono::duration<double, std::milli>(d1 - d0).count(),
                std::chrono::duration<double, std::milli>(d2 - d1).count());
         snprintf(name, sizeof name, "%s.%dsamp.denoised.png", out.c_str(), iteration);
         pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
