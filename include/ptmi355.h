@@ -124,7 +124,19 @@ enum pt_flags {
                                     no compaction, runs the separate intersect -> key histogram -> sorted-shade kernels */
     PT_FAKE_SHADER   = 1u << 2,  /* the reference as shipped: one bounce + shadeFakeMaterial
                                     (pathtrace.cu:224-266,339-377) */
-    PT_CACHE_FIRST   = 1u << 3,  /* cache the bounce-0 intersections (INSTRUCTION.md:87-89) */
+    PT_CACHE_FIRST   = 1u << 3,  /* cache the bounce-0 intersections (INSTRUCTION.md:87-89): a table of every pixel's first
+                                    hit (t, normal, material, inside / outside, primitive), filled once per camera by the
+                                    first batch that needs it; bounce 0 of every batch looks its hits up instead of
+                                    intersecting.  Results are bit-identical either way, and the ray counters still count
+                                    bounce-0 paths (pt_stats.rays, pt_total_rays: one ray per live path and bounce, whether
+                                    its intersection was computed or looked up).
+                                    The plain fused pipeline (no PT_UNFUSED, PT_SORT_MATERIAL, PT_FAKE_SHADER, no triangle
+                                    meshes) uses the same table WITHOUT the flag whenever its camera rays repeat -- no
+                                    PT_AA_JITTER, no lens at the time of the call, no texture set, bounce 0 not one of
+                                    PT_DIRECT_LIGHT's two sampling bounces -- except for batches small enough to run as one
+                                    launch.  The flag forces the table form for every batch (no one-launch iterations, no
+                                    PT_LOOKAHEAD windows) and keeps its refusals: PT_AA_JITTER, a lens, PT_DIRECT_LIGHT,
+                                    PT_TEXTURES. */
     PT_UNFUSED       = 1u << 4,  /* debug: separate intersect / shade kernels with the
                                     ShadeableIntersection planes materialised in HBM */
     PT_MESH_BVH      = 1u << 5,  /* cull triangle tests with a bounding-volume hierarchy built at

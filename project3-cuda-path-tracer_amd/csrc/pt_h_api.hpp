@@ -169,7 +169,7 @@ static int init_impl(const pt_scene_desc *d) {
         if (d->flags & PT_UNFUSED)
             return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_UNFUSED (its intersection planes do not carry the winning primitive)");
         if (d->flags & PT_CACHE_FIRST)
-            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_CACHE_FIRST (the first-bounce cache keeps no primitive number)");
+            return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_CACHE_FIRST (the table form of bounce 0 has no DIRECT variant)");
         if (d->trace_depth > MAX_DEPTH - 1)
             return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT runs trace_depth + 1 bounces: trace_depth %d outside [1,%d]", d->trace_depth, MAX_DEPTH - 1);
         const int ne = ptlight::elements(d->geoms, d->num_geoms, d->materials, d->num_materials, light_el);
@@ -183,7 +183,7 @@ static int init_impl(const pt_scene_desc *d) {
         if (d->flags & PT_UNFUSED)
             return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_UNFUSED (its intersection planes do not carry the winning primitive)");
         if (d->flags & PT_CACHE_FIRST)
-            return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_CACHE_FIRST (the first-bounce cache keeps no primitive number)");
+            return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_CACHE_FIRST (the table form of bounce 0 has no TEX variant)");
         if (d->flags & PT_DIRECT_LIGHT)
             return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_DIRECT_LIGHT (the direct kernels have no textured form yet)");
     }
@@ -215,6 +215,8 @@ static int init_impl(const pt_scene_desc *d) {
     if (const char *e = pt_experiment("PTMI355_DEFER_DIR")) R.defer_enabled = atoi(e) != 0;
     R.own_enabled = true;
     if (const char *e = pt_experiment("PTMI355_OWN_SURFACE")) R.own_enabled = atoi(e) != 0;
+    R.first_hit_enabled = true;
+    if (const char *e = pt_experiment("PTMI355_FIRST_HIT")) R.first_hit_enabled = atoi(e) != 0;
     R.host_sparse_enabled = (d->flags & (PT_HOST_SPARSE | PT_SHARED_IMAGE)) != 0;
     if (const char *e = pt_experiment("PTMI355_ASYNC_DIRECT")) R.async_direct_enabled = atoi(e) != 0;
     R.pin_enabled = true;
@@ -475,7 +477,10 @@ static int init_impl(const pt_scene_desc *d) {
             else if (R.mesh_mode == MESH_TILES) { fns[0] = bounce_fn<MESH_TILES, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_TILES, SH>(R.scene_lds, true, sorted); }
             else { fns[0] = bounce_fn<MESH_NONE, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE, SH>(R.scene_lds, true, sorted); }
             const void *fns_own[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true) : fns[1]};
-            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1]}) {
+            // (... and the table form of bounce 0, stepped or generating, with and without the own-surface bits: enqueue_bounce)
+            const void *fns_tab[4] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true) : fns[1],
+                                      own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true) : fns[1]};
+            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3]}) {
                 int n = 0;
                 HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
                 per_cu = std::min(per_cu, n);
@@ -536,7 +541,13 @@ static int init_impl(const pt_scene_desc *d) {
         R.grid_mesh = (int)std::min<uint32_t>((R.max_tiles + MESH_WG_WAVES - 1) / MESH_WG_WAVES, (uint32_t)cus);
         if (R.grid_mesh < 1) R.grid_mesh = 1;
     }
-    if (R.flags & PT_CACHE_FIRST) HIPCHK(hipMalloc(&R.cache_mem, (size_t)R.map.tile_pixels * 5 * 4));
+    if (R.flags & PT_CACHE_FIRST) {
+        HIPCHK(hipMalloc(&R.cache_mem, (size_t)R.map.tile_pixels * Isect::FIRST_HIT_BYTES));
+    } else if (R.first_hit_enabled && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_AA_JITTER)) && R.mesh_mode == MESH_NONE) {
+        // the plain fused pipeline reads bounce 0 from the first-hit table whenever its camera rays repeat (enqueue_bounce).
+        // The table is an optimisation: a session that cannot have one traces bounce 0 as before.
+        if (hipMalloc(&R.cache_mem, (size_t)R.map.tile_pixels * Isect::FIRST_HIT_BYTES) != hipSuccess) { (void)hipGetLastError(); R.cache_mem = nullptr; }
+    }
     if ((R.flags & PT_SORT_MATERIAL) && !R.sort_keys) {
         if (d->num_materials + 1 > SORT_MAX_BINS)
             return fail(PT_ERR_INVALID, "pt_init: PT_SORT_MATERIAL keeps one bin per material in LDS: at most %d materials", SORT_MAX_BINS - 1);

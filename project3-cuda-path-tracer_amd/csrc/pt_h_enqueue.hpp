@@ -127,9 +127,20 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // the fused compacting kernel that launch_bounce_at picks for (scene in LDS, ray generation, material keys)
 // SH: the shading variant the grid is sized for -- 0, SH_DIRECT for the last two bounces of a PT_DIRECT_LIGHT session, or SH_TEX
 // for a PT_TEXTURES session
+// `table`: the table form of bounce 0 (MODE_CACHE0; enqueue_bounce) of a session without mesh or material keys -- it has the
+// ENV and GLOSSY variants only, so SH's other bits do not apply
 template <int MESH, int SH = 0>
-const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false) {
+const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool table = false) {
     if constexpr (MESH == MESH_NONE) {
+        if (table && !sorted) {
+            constexpr int SH0 = SH & (SH_ENV | SH_GLOSSY);
+            if (own) {
+                if (slds) return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, true, true, false, true, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, true, false, false, true, SH0>;
+                return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, false, true, false, true, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, false, false, false, true, SH0>;
+            }
+            if (slds) return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, true, true, false, false, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, true, false, false, false, SH0>;
+            return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, false, true, false, false, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, false, false, false, false, SH0>;
+        }
         if (own && !sorted) {
             if (slds) return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, true, true, false, true, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, true, false, false, true, SH>;
             return gen ? (const void *)k_bounce<MODE_FUSED, true, MESH, false, true, false, true, SH> : (const void *)k_bounce<MODE_FUSED, true, MESH, false, false, false, true, SH>;
@@ -187,8 +198,8 @@ void launch_bounce_at(const BounceArgs &a) {
             return;
         }
     }
-    if constexpr (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE) {
-        if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce)
+    if constexpr ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE) {
+        if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce); MODE_CACHE0 writes its bits
             if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>(a);
             else launch_k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>(a);
             return;
@@ -264,7 +275,17 @@ int enqueue_bounce(int depth) {
         R.step_depth = depth + 1;
         return PT_OK;
     }
-    const bool cached0 = depth == 0 && !unfused && (R.flags & PT_CACHE_FIRST);
+    // Bounce 0 from the first-hit table: with PT_CACHE_FIRST always; without the flag whenever the
+    // plain fused pipeline -- compacting or not -- would trace the same camera rays again that it traced for this camera
+    // before: no jitter and no lens at enqueue time (bounce_args' same_rays), no mesh, no material keys, no fake shader, no
+    // texture set (the TEX forms shade with the hit point's primitive record, which MODE_CACHE0 has no form for) and bounce 0
+    // not one of a PT_DIRECT_LIGHT session's two DIRECT bounces.  Nothing here depends on the candidate masks (cull0): scenes
+    // of more than 64 primitives and tiles that are no multiple of 64 pixels qualify.  k_iteration never comes here.
+    const bool same_rays = !R.lens.aa && !(R.lens.radius > 0.0f);
+    const bool auto0 = depth == 0 && !unfused && R.first_hit_enabled && R.cache_mem != nullptr && !(R.flags & PT_FAKE_SHADER) &&
+                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && same_rays && a.tex_tab == nullptr &&
+                       !(a.nlights > 0 && depth >= a.trace_depth - 1);
+    const bool cached0 = depth == 0 && !unfused && ((R.flags & PT_CACHE_FIRST) || auto0);
     // Diffuse survivors leave their direction to the next bounce (pt_types.hpp: PENDING_DIR) when that bounce is the fused
     // compacting k_bounce without mesh pre-pass or material keys, the one kernel that draws it when it loads the path
     // (tile_load<RESOLVE>).  The pipeline is fixed for the session (pt_init's flags), so the next bounce of this batch --
@@ -274,22 +295,38 @@ int enqueue_bounce(int depth) {
                    R.defer_enabled) ? 1 : 0;
     // The own-surface form of the cull (pt_types.hpp: OWN_MASK): survivors carry the primitive they leave in their pid and
     // the next bounce tests that primitive's row once per ray.  Writer and reader must both be the plain fused compacting
-    // k_bounce -- no mesh pre-pass, no material keys, no first-bounce cache (it keeps no primitive number) -- the batch's pids
-    // must leave the bits free and the primitives must fit the code.  All of that is fixed for the batch, so every bounce of
+    // k_bounce -- no mesh pre-pass, no material keys; bounce 0 may be the table form, whose records name the primitive -- the
+    // batch's pids must leave the bits free and the primitives must fit the code.  All of that is fixed for the batch, so every bounce of
     // it takes the same form: a bounce of this form reads what one of this form (or k_raygen: plain pids below 2^26) wrote.
     // The last bounce writes no survivors, so "a next bounce exists" needs no case of its own.  Every other reader of a
     // pool only ever sees plain pids.
     R.own_form = own_surface_plan((uint64_t)a.pool_n, R.scene.ngeoms,
                                   compact && !unfused && R.mesh_mode == MESH_NONE && R.sort_keys == 0 &&
-                                  !(R.flags & PT_CACHE_FIRST) && R.own_enabled);
+                                  R.own_enabled);
     if (cached0 && !R.cache_valid) {
+        // The table is filled once per camera, by the first bounce 0 that wants it (a session that only ever runs
+        // k_iteration never pays), on the session's LAUNCH stream -- also when this batch is being enqueued on a lane.
+        // Behind every reader of the old table: the table is only invalid after pt_init or a camera change; every earlier
+        // batch's gather is on the launch stream behind that batch's last kernel (enqueue_end), every window traced ahead
+        // was either waited for on the launch stream when a call consumed it or drained by pt_set_camera (la_discard(LA_HOST)),
+        // and a serial batch ran on the launch stream itself.  In front of every reader of the new one: this lane's stream
+        // waits for the fill's event here, before its bounce 0 is launched, and ov_active is left false (enqueue_on_lane) so
+        // that the next batch or window goes through enter_lanes' event, recorded on the launch stream after the fill, which
+        // every lane's stream -- the CU-masked ones of PT_LOOKAHEAD included -- waits for before its next launch.
         StageTimer tm(PT_STAGE_INTERSECT);
         const Isect cache{R.cache_mem, (uint32_t)R.map.tile_pixels};
         const int blocks = std::min(R.grid, (R.map.tile_pixels + BLOCK - 1) / BLOCK);
-        PT_MESH_DISPATCH(hipLaunchKernelGGL((k_cache_first<MESH, SLDS>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream,
+        const hipStream_t fs = R.lane_cur ? R.lane_main : R.stream;
+        PT_MESH_DISPATCH(hipLaunchKernelGGL((k_cache_first<MESH, SLDS>), dim3(blocks), dim3(BLOCK), R.lds_bytes, fs,
                                             cache, R.scene, R.cam, R.map));
         HIPCHK(hipGetLastError());
+        if (R.lane_cur) {
+            HIPCHK(hipEventRecord(R.ov_enter, fs));
+            HIPCHK(hipStreamWaitEvent(R.stream, R.ov_enter, 0));
+            R.first_hit_refence = true;
+        }
         R.cache_valid = true;
+        R.first_hit_fills++;
     }
     if (!cached0 && !unfused && R.mesh_mode == MESH_BVH) {
         StageTimer tm(PT_STAGE_MESH);
@@ -300,6 +337,7 @@ int enqueue_bounce(int depth) {
     StageTimer tm(PT_STAGE_BOUNCE);
     if (cached0) {
         a.isect = Isect{R.cache_mem, (uint32_t)R.map.tile_pixels};
+        R.first_hit_launches++;
         if (compact) launch_bounce<MODE_CACHE0, true>(a); else launch_bounce<MODE_CACHE0, false>(a);
     } else if (unfused) {
         if (compact) launch_bounce<MODE_ISECT, true>(a); else launch_bounce<MODE_ISECT, false>(a);
@@ -513,10 +551,11 @@ bool ensure_la_masks(void) {
 }
 
 // the fused pipelines only: the unfused / two-kernel-sort / fake-shader ones keep intersection planes and sort tables
-// (one set), the first-bounce cache is filled by the first batch that needs it
+// (one set).  The first-hit table is one per session too, but read-only between camera changes and its fill is ordered
+// against every lane (enqueue_bounce): PT_CACHE_FIRST sessions overlap like the others.
 bool overlap_eligible(int count) {
     return R.ov_ok && R.ov_enabled && !R.profiling && !R.epi_host && !R.dbg_counts &&
-           !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) &&
+           !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER)) && (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) &&
            count >= 1 && count <= R.max_batch;
 }
 
@@ -555,7 +594,8 @@ int enqueue_on_lane(Renderer::Lane &l, int iter0, int count) {
     const int rc = enqueue_batch_serial(iter0, count);                  // its gather goes to the launch stream (enqueue_end)
     R.stream = R.lane_main; put_bufs(home);
     R.lane_cur = nullptr; R.lane_main = nullptr;
-    R.ov_active = rc == PT_OK;
+    R.ov_active = rc == PT_OK && !R.first_hit_refence;                  // (the first-hit table was filled: enqueue_bounce)
+    R.first_hit_refence = false;
     return rc;
 }
 

@@ -48,8 +48,11 @@ struct Renderer {
     int cur = 0;                  // pool holding the current live prefix
     float *isect_mem = nullptr;
     uint32_t *sort_table = nullptr;
-    float *cache_mem = nullptr;   // first-bounce cache: 5 planes of tile_pixels (PT_CACHE_FIRST)
-    bool cache_valid = false;
+    float *cache_mem = nullptr;   // first-hit table: Isect::FIRST_HIT_BYTES per pixel of the tile (PT_CACHE_FIRST, and every session whose bounce 0 can take the table form)
+    bool cache_valid = false;     // ... holds R.cam's first hits (cleared by pt_set_camera; filled by the next bounce 0 that reads it)
+    bool first_hit_enabled = true;    // PTMI355_FIRST_HIT=0: only PT_CACHE_FIRST sessions read the table (the A/B control)
+    bool first_hit_refence = false;   // the batch being enqueued on a lane filled the table: the next one starts from enter_lanes' event
+    uint64_t first_hit_fills = 0, first_hit_launches = 0;   // k_cache_first launches / bounce-0 launches of the table form since pt_init (ptdbg_first_hit)
     Isect isect{};
     float *final_mem = nullptr;   // float4[cap]: {r, g, b, stamp} of the paths that ended with a non-zero colour, index = pid
     uint32_t fin_serial = 0;      // stamp of the current batch's entries (never 0; a wrap clears the buffer)

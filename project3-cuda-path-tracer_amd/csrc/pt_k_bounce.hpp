@@ -10,7 +10,8 @@ namespace {
 // ---------------------------------------------------------------------------
 // MODE_FUSED   : intersect inline (ShadeableIntersection never touches HBM)
 // MODE_ISECT   : read the materialised planes written by k_intersect (PT_UNFUSED / sort)
-// MODE_CACHE0  : bounce 0 with PT_CACHE_FIRST: the per-pixel intersection cache (INSTRUCTION.md:87-89)
+// MODE_CACHE0  : bounce 0 from the first-hit table (k_cache_first): PT_CACHE_FIRST (INSTRUCTION.md:87-89), and the plain fused
+//                pipeline by itself while its camera rays repeat (enqueue_bounce)
 enum { MODE_FUSED = 0, MODE_ISECT = 1, MODE_CACHE0 = 2 };
 
 // per-launch constants of a wave
@@ -386,11 +387,25 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
                 tile_finish<COMPACT, MESH, SORT, DEFER, OWN, SH>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
             }
             prev = tr; prev_ticket = ticket; pending = true; par ^= 1;
+        } else if (MODE == MODE_CACHE0) {
+            // the first-hit table: one record per pixel of the tile -- what tile_result returned for this ray when
+            // k_cache_first traced it (t, normal, material, outside, primitive).  The survivors carry the primitive to
+            // bounce 1 as the fused bounce 0's do (OWN); this bounce reads no own surface, a camera ray leaves none.
+            float t = -1.0f; f3 nrm = ptd::mk(0, 0, 0); int mat = 0, outside = 1, geom = -1;
+            if (tr.active) {
+                const size_t k = tr.pid - tr.smp * (uint32_t)a.map.tile_pixels;
+                const float4 h = *a.isect.first_hit(k);
+                const int2 id = *a.isect.first_id(k);
+                t = h.x; nrm = ptd::mk(h.y, h.z, h.w);
+                mat = id.x & 0x7fffffff; outside = (id.x < 0) ? 0 : 1; geom = id.y;
+            }
+            tile_shade<COMPACT, MESH_NONE, false, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, 0,
+                                                             OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom);
         } else {
-            // MODE_ISECT: planes in logical order; MODE_CACHE0: one record per pixel of the tile
+            // MODE_ISECT: planes in logical order
             float t = -1.0f; f3 nrm = ptd::mk(0, 0, 0); int mat = 0, outside = 1;
             if (tr.active) {
-                const uint32_t k = (MODE == MODE_CACHE0) ? tr.pid - tr.smp * (uint32_t)a.map.tile_pixels : i;
+                const uint32_t k = i;
                 t = at(a.isect.plane(0), k);
                 nrm = ptd::mk(at(a.isect.plane(1), k), at(a.isect.plane(2), k), at(a.isect.plane(3), k));
                 const int m = at(a.isect.mat(), k);
@@ -413,8 +428,10 @@ __device__ uint32_t g_wave_hw[8][8192];
 #endif
 
 template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN = false, bool SORT = false, bool OWN = false, int SH = 0>
-__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
-    static_assert(!OWN || (MODE == MODE_FUSED && COMPACT && MESH == MESH_NONE && !SORT), "own-surface form: the plain fused compacting kernel");
+__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
+    // (MODE_CACHE0 only writes the bits: bounce 0 reads no own surface)
+    static_assert(!OWN || ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE && !SORT),
+                  "own-surface form: the plain fused compacting kernel, or the table form of its bounce 0");
 #ifdef PT_WAVE_TIMES
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif

@@ -265,7 +265,8 @@ __global__ __launch_bounds__(BLOCK) void k_cull0_mask(SceneDev sc, pt_camera cam
 
 // First-bounce cache (INSTRUCTION.md:87-89): camera rays do not depend on the iteration (no
 // jitter, pathtrace.cu:134), so computeIntersections of bounce 0 is evaluated once per pixel and
-// camera and reused by every sample.
+// camera and reused by every sample.  The table (pt_types.hpp: Isect::first_hit / first_id) is indexed by the tile's local
+// pixel; one workgroup pass covers BLOCK consecutive pixels, every wave writes 1024 + 512 consecutive bytes.
 template <int MESH, bool SLDS>
 __global__ __launch_bounds__(BLOCK, PT_MIN_WAVES) void k_cache_first(Isect cache, SceneDev sc, pt_camera cam,
                                                                       TileMap map) {
@@ -284,10 +285,12 @@ __global__ __launch_bounds__(BLOCK, PT_MIN_WAVES) void k_cache_first(Isect cache
         cull_scene<MESH>(sc, acc, q, 0, lc.tri, active, ro, rd, mb, nullptr);
         drain_to(q, acc, q.total);
         if (active) {
-            float t; f3 nrm; int mat, outside;
-            tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside);
-            cache.plane(0)[j] = t; cache.plane(1)[j] = nrm.x; cache.plane(2)[j] = nrm.y; cache.plane(3)[j] = nrm.z;
-            cache.mat()[j] = mat | (outside ? 0 : (int)0x80000000u);
+            // exactly what tile_result hands the fused kernel for this ray, the winning primitive included (a miss: t = -1,
+            // geom = -1): bounce 0 of the table form shades and tags its survivors as the fused bounce 0 does
+            float t; f3 nrm; int mat, outside, geom;
+            tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside, geom);
+            *cache.first_hit(j) = make_float4(t, nrm.x, nrm.y, nrm.z);
+            *cache.first_id(j) = make_int2(mat | (outside ? 0 : (int)0x80000000u), geom);
         }
     }
 }

@@ -58,8 +58,8 @@ constexpr int OWN_SHIFT = 26;
 constexpr uint32_t OWN_MASK = 0xfu << OWN_SHIFT;
 constexpr int OWN_MAX_GEOMS = 15;                          // codes 1..15
 constexpr uint64_t OWN_MAX_PATHS = 1ull << OWN_SHIFT;      // pids of a batch are below its path count
-// `plain_fused`: writer and reader are the fused compacting k_bounce without mesh pre-pass, material keys or first-bounce
-// cache (the cache keeps no primitive number)
+// `plain_fused`: writer and reader are the fused compacting k_bounce without mesh pre-pass or material keys (bounce 0 may be
+// the table form, MODE_CACHE0: the first-hit table names the primitive)
 inline bool own_surface_plan(uint64_t paths, int ngeoms, bool plain_fused) {
     return plain_fused && ngeoms >= 1 && ngeoms <= OWN_MAX_GEOMS && paths <= OWN_MAX_PATHS;
 }
@@ -126,6 +126,12 @@ struct Isect {           // ShadeableIntersection planes t nx ny nz mat (unfused
     uint32_t cap;
     __device__ __forceinline__ float *plane(int k) const { return base + (size_t)k * cap; }
     __device__ __forceinline__ int *mat() const { return reinterpret_cast<int *>(base + (size_t)4 * cap); }
+    // The first-hit table (k_cache_first -> k_bounce<MODE_CACHE0>; `cap` = pixels of the tile) is two arrays of records
+    // instead: [t nx ny nz], 16 B per pixel, then [mat geom], 8 B per pixel -- a 64-lane tile reads 1024 + 512 consecutive
+    // bytes with two loads.  mat as above; geom is the winning primitive (-1: a miss, t = -1).
+    __device__ __forceinline__ float4 *first_hit(size_t k) const { return reinterpret_cast<float4 *>(base) + k; }
+    __device__ __forceinline__ int2 *first_id(size_t k) const { return reinterpret_cast<int2 *>(base + (size_t)4 * cap) + k; }
+    static constexpr size_t FIRST_HIT_BYTES = 24;      // per pixel
 };
 
 struct TileMap {         // local pixel index -> global pixelIndex (x + y*W)

@@ -122,6 +122,19 @@ extern "C" int ptdbg_lookahead_masked(unsigned long long out[2]) {
     return 0;
 }
 
+// diagnostics (not in include/ptmi355.h): the first-hit table since pt_init -- out[0] = fills (k_cache_first launches), out[1] =
+// bounce-0 launches that read the table instead of intersecting (k_bounce<MODE_CACHE0>).  A multi-device session sums its contexts.
+extern "C" int ptdbg_first_hit(unsigned long long out[2]) {
+    if (G.live) {
+        out[0] = 0; out[1] = 0;
+        for (auto &wp : G.w) { out[0] += wp->ctx.first_hit_fills; out[1] += wp->ctx.first_hit_launches; }
+        return 0;
+    }
+    if (!g_single.live) return -1;
+    out[0] = g_single.first_hit_fills; out[1] = g_single.first_hit_launches;
+    return 0;
+}
+
 // diagnostics (not in include/ptmi355.h): launches of k_gbuffer / k_atrous / k_denoise_mean since pt_init (single-device sessions)
 extern "C" int ptdbg_denoise(unsigned long long out[3]) {
     if (!g_single.live) return -1;
