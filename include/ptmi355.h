@@ -361,6 +361,40 @@ int pt_get_texture(int material, float *texels, int capacity_texels, int *n);
  * PT_ERR_INVALID: a negative count, a null array with count > 0, a hit_geom entry outside [0, num_geoms), n outside [1, 1024]. */
 int pt_texture_texel(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n, int32_t *index);
 
+/* ---- bump mapping (PT_TEXTURES): one cube bump map per material perturbs the shading normal of spheres and cubes -------------
+ * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/bump_model.py is the numpy form, and
+ * the device's result equals it bit for bit).  A bump map has pt_set_texture's layout, 6 * n * n RGB
+ * float32 texels with n in [1, 1024]; a texel is (da, db, unused): the two slopes added to the object-space normal along the
+ * face's two in-plane axes (the negative height gradient, raw floats).  A material may carry a texture, a bump map, both or
+ * neither.  At a hit with t > 0 on primitive g of type PT_SPHERE or PT_CUBE whose material has a bump map B of size n, with I
+ * the ray's direction and nr the normal the intersection test reported:
+ *   1  dot(I, nr) < 0 is false: not perturbed (the inside of a cube reports the exit face)
+ *   2  P and q as for a texture (above)
+ *   3  k = the texel of q, axis / negative = its major axis and sign; k < 0: not perturbed
+ *   4  (da, db) = (B[k].r, B[k].g); da == 0 && db == 0: not perturbed (a NaN goes on)
+ *   5  a < b the other two axes in x, y, z order.  Cube: u[axis] = negative ? -1 : 1, u[a] = da, u[b] = db.
+ *      Sphere: u = q + q, then u[a] = u[a] + da, u[b] = u[b] + db
+ *   6  w = multiplyMV(cube ? g.transform : g.invTranspose, (u, 0));  ns = normalize(w) = w * (1 / sqrt(dot(w, w)))
+ *   7  dot(ns, nr) < 0: ns = -ns (a sphere hit from inside); then dot(ns, nr) > 0 is false: not perturbed
+ *   8  dot(I, ns) < 0 is false: not perturbed
+ * A perturbed hit is shaded with ns where nr stands (the glossy lobe, the mirror, the dielectric, the diffuse sampler; the same
+ * engine, the same draws).  Then, for a survivor whose material is a mirror or is neither mirror nor dielectric, a new direction
+ * with dot(dir, nr) > 0 false becomes reflect(dir, nr), not renormalised.  Everything else -- colours, origins, the emitter
+ * and last-bounce exits, misses, meshes, the G-buffer's normals, pt_albedo, the filters, the ray counters -- is unchanged, and a
+ * hit that is not perturbed is shaded exactly as without a map.  While a texture or a bump map is set the session runs a kernel
+ * per bounce, as section 6.19 says of textures.
+ * pt_set_bump_map / pt_get_bump_map: the contracts, refusals, synchronisation and per-context copies of pt_set_texture /
+ * pt_get_texture.  The state survives pt_set_camera, pt_clear_image and pt_set_texture, ends with pt_free, and does not
+ * invalidate the albedo plane.  PT_FAKE_SHADER ignores it. */
+int pt_set_bump_map(int material, const float *texels, int n);
+int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n);
+/* host-only (no GPU): steps 1-8 for each of `count` records (primitive hit_geom[i], world point points[3 i ..], reported normal
+ * normals[3 i ..], ray direction dirs[3 i ..]) on one map of n x n texels per face: out_normals = ns and perturbed = 1 where the
+ * hit is perturbed, out_normals = the reported normal and perturbed = 0 elsewhere and for mesh primitives.
+ * PT_ERR_INVALID: what pt_texture_texel refuses, and a null texels, normals, dirs, out_normals or perturbed with count > 0. */
+int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                   int count, const float *texels, int n, float *out_normals, uint8_t *perturbed);
+
 /* ---- glossy reflection and frosted glass (PT_GLOSSY): SPECEX gives the specular surfaces a GGX lobe ------------------------
  * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/glossy_model.py is the numpy form,
  * and the device's result equals it bit for bit).
@@ -687,6 +721,19 @@ int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *mate
                                     const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
                                     const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
                                     const int32_t *tex_n, const int32_t *tex_offset);
+/* pt_probe_bump_normal: pt_bump_normal's arguments, results and refusals (plus count above 2^26) through the function the kernels
+ * call, one lane per record.  No session is needed; count == 0 launches nothing.
+ * pt_probe_shade_scatter_bumped: pt_probe_shade_scatter_textured plus a bump table as parallel arrays -- bump_texels (all maps
+ * back to back, RGB), bump_n[num_materials] (0 = none), bump_offset[num_materials] (in texels) -- through the whole textured
+ * form as the kernels call it while a bump map is set: lookup, shader about the perturbed normal, guard, and no deferral on
+ * perturbed lanes (deferred = 0 and 1 give the same bytes there). */
+int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                         int count, const float *texels, int n, float *out_normals, uint8_t *perturbed);
+int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                  const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                  const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                  const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
+                                  const int32_t *bump_offset);
 /* pt_probe_direct_sample: PT_DIRECT_LIGHT's sampler (above; csrc/pt_device.hpp: direct_sample) on the device through the function
  * the kernels call, one lane per record: for each of `count` (P, n, engine seed) triples (P, n: count x 3 floats; seeded like
  * pt_probe_hemisphere) the direction (count x 3), the weight and the element picked, on the light table of the scene given as for

@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     glossy_alpha2, probe_glossy_lobe, probe_shade_scatter_glossy,
     PT_DIRECT_LIGHT, LIGHT_DT, light_elements, probe_direct_sample, probe_shade_scatter_direct,
     PT_TEXTURES, set_texture, get_texture, checker_cubemap, texture_texel, probe_texture, probe_shade_scatter_textured,
+    set_bump_map, get_bump_map, studs_bumpmap, bump_normal, probe_bump_normal, probe_shade_scatter_bumped,
 )
 from .build import build  # noqa: F401
 from . import sharding  # noqa: F401,E402

@@ -197,6 +197,12 @@ def library():
             L.pt_probe_texture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
             L.pt_probe_shade_scatter_textured.argtypes = L.pt_probe_shade_scatter.argtypes + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                                                               C.c_void_p, C.c_void_p]
+            L.pt_set_bump_map.argtypes = L.pt_set_texture.argtypes
+            L.pt_get_bump_map.argtypes = L.pt_get_texture.argtypes
+            L.pt_bump_normal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p]
+            L.pt_probe_bump_normal.argtypes = L.pt_bump_normal.argtypes
+            L.pt_probe_shade_scatter_bumped.argtypes = L.pt_probe_shade_scatter_textured.argtypes + [C.c_void_p, C.c_void_p, C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -455,6 +461,107 @@ def probe_shade_scatter_textured(iter, depth, materials, paths, isects, geoms, h
     tex = np.ascontiguousarray(np.concatenate(parts)) if parts else None
     _chk(library().pt_probe_shade_scatter_textured(int(iter), int(depth), _p(m), len(m), _p(p), _p(x), _p(o), len(p), 1 if deferred else 0,
                                                    _p(g), len(g), _p(h), _p(tex), _p(tn), _p(toff)))
+    return p
+
+
+def set_bump_map(material, texels):
+    """The cube bump map of one material (include/ptmi355.h: pt_set_bump_map): [6, n, n, 3] float32, indexed [face, j, i], a
+    texel (da, db, unused); None removes it.  Sessions initialised with PT_TEXTURES.  The running sum is not touched."""
+    if texels is None:
+        _chk(library().pt_set_bump_map(int(material), None, 0))
+        return
+    t, n = _cube_texels(texels)
+    _chk(library().pt_set_bump_map(int(material), _p(t), n))
+
+
+def get_bump_map(material):
+    """That material's bump map as it was set, [6, n, n, 3] float32, or None."""
+    n = C.c_int(0)
+    L = library()
+    rc = L.pt_get_bump_map(int(material), None, 0, C.byref(n))    # the size: PT_OK with n = 0 when none is set
+    if n.value == 0:
+        _chk(rc)
+        return None
+    out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
+    _chk(L.pt_get_bump_map(int(material), _p(out), 6 * n.value * n.value, C.byref(n)))
+    return out
+
+
+def studs_bumpmap(n, cells, slope):
+    """Bevelled studs for set_bump_map, [6, n, n, 3] float32: the integer rule of the scene format's `STUDS` line
+    (host/pthost.h) -- pa = (i * cells * 4 // n) % 4, sa = -1, 0, 0, 1 for pa = 0..3, sb likewise from j, texel
+    (slope * sa, slope * sb, 0)."""
+    n, cells = int(n), int(cells)
+    if n < 1 or n > 1024 or cells < 1 or cells > 1024:
+        raise PtError("studs_bumpmap: n = %d, cells = %d outside [1, 1024]" % (n, cells))
+    ph = (np.arange(n, dtype=np.int64) * cells * 4 // n) % 4
+    s = np.where(ph == 0, -1, np.where(ph == 3, 1, 0)).astype(np.float32) * np.float32(slope)
+    out = np.zeros((6, n, n, 3), dtype=np.float32)
+    out[..., 0] = s[None, None, :]
+    out[..., 1] = s[None, :, None]
+    return out
+
+
+def _bump_records(who, geoms, hit_geom, points, normals, dirs):
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    h = np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    if len(h) != len(pts) or len(nrm) != len(pts) or len(d) != len(pts):
+        raise PtError("%s: %d primitives, %d points, %d normals, %d directions" % (who, len(h), len(pts), len(nrm), len(d)))
+    return g, h, pts, nrm, d
+
+
+def bump_normal(geoms, hit_geom, points, normals, dirs, texels):
+    """Host-only: the shading normal of each (primitive, world point, reported normal, ray direction) record under one bump map
+    (include/ptmi355.h: pt_bump_normal).  Returns (normals [count, 3] float32, perturbed [count] bool)."""
+    g, h, pts, nrm, d = _bump_records("bump_normal", geoms, hit_geom, points, normals, dirs)
+    t, n = _cube_texels(texels)
+    out = np.zeros((len(h), 3), dtype=np.float32)
+    flag = np.zeros(len(h), dtype=np.uint8)
+    _chk(library().pt_bump_normal(_p(g), len(g), _p(h), _p(pts), _p(nrm), _p(d), len(h), _p(t), n, _p(out), _p(flag)))
+    return out, flag.astype(bool)
+
+
+def probe_bump_normal(geoms, hit_geom, points, normals, dirs, texels):
+    """bump_normal on the device through the function the kernels call (include/ptmi355.h: pt_probe_bump_normal)."""
+    g, h, pts, nrm, d = _bump_records("probe_bump_normal", geoms, hit_geom, points, normals, dirs)
+    t, n = _cube_texels(texels)
+    out = np.zeros((len(h), 3), dtype=np.float32)
+    flag = np.zeros(len(h), dtype=np.uint8)
+    _chk(library().pt_probe_bump_normal(_p(g), len(g), _p(h), _p(pts), _p(nrm), _p(d), len(h), _p(t), n, _p(out), _p(flag)))
+    return out, flag.astype(bool)
+
+
+def _cube_table(maps, count):
+    """{material: [6, n, n, 3]} as the probes' parallel arrays: texels back to back, n and offset per material."""
+    tn = np.zeros(count, dtype=np.int32)
+    toff = np.zeros(count, dtype=np.int32)
+    parts, total = [], 0
+    for mat in sorted(maps or {}):
+        t, n = _cube_texels(maps[mat])
+        tn[mat], toff[mat] = n, total
+        parts.append(t)
+        total += len(t)
+    return (np.ascontiguousarray(np.concatenate(parts)) if parts else None), tn, toff
+
+
+def probe_shade_scatter_bumped(iter, depth, materials, paths, isects, geoms, hit_geom, textures, bump_maps, outside=None, deferred=False):
+    """probe_shade_scatter_textured with bump maps ({material: [6, n, n, 3] float32}) through the whole textured form as the
+    kernels call it while a bump map is set (include/ptmi355.h: pt_probe_shade_scatter_bumped)."""
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    p = np.array(paths, dtype=PATH_DT, copy=True, order="C").reshape(-1)
+    x = np.ascontiguousarray(isects, dtype=ISECT_DT).reshape(-1)
+    o = None if outside is None else np.ascontiguousarray(outside, dtype=np.uint8).reshape(-1)
+    h = np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    if len(x) != len(p) or len(h) != len(p) or (o is not None and len(o) != len(p)):
+        raise PtError("probe_shade_scatter_bumped: %d paths, %d intersections, %d primitives" % (len(p), len(x), len(h)))
+    tex, tn, toff = _cube_table(textures, len(m))
+    bump, bn, boff = _cube_table(bump_maps, len(m))
+    _chk(library().pt_probe_shade_scatter_bumped(int(iter), int(depth), _p(m), len(m), _p(p), _p(x), _p(o), len(p), 1 if deferred else 0,
+                                                 _p(g), len(g), _p(h), _p(tex), _p(tn), _p(toff), _p(bump), _p(bn), _p(boff)))
     return p
 
 

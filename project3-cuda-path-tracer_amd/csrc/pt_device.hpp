@@ -583,6 +583,42 @@ template <typename P> PTD f3 texture_mcol(const float *mats, int matId, uint32_t
 }
 
 // ---------------------------------------------------------------------------
+// bump mapping (PT_TEXTURES): a cube bump map per material perturbs the shading normal at a hit
+// ---------------------------------------------------------------------------
+// (steps 1-8 themselves, host and device, plain C++: pt_bump.hpp -- ptd::env_texel_face, bump_normal_q, bump_normal)
+}  // namespace ptd
+#include "pt_bump.hpp"
+namespace ptd {
+static_assert(BUMP_SPHERE == (uint32_t)PT_SPHERE && BUMP_CUBE == (uint32_t)PT_CUBE, "pt_bump.hpp names the primitive types by value");
+// texture_mcol and the bump lookup of one hit (t > 0) together, as the TEX kernels and the probe need them: P and q are
+// computed once for a material that has both.  btab == nullptr (wave-uniform: the session has no bump map): texture_mcol.
+// `want_normal`: false where the shader uses no normal (the last bounce) -- no bump lookup.  Returns the material's colour,
+// tinted or not; `bumped` says whether ns replaces the reported normal nr.
+template <typename P> PTD f3 texture_bump_mcol(const float *mats, int matId, uint32_t type, P rec, f3 o, f3 d, float t, f3 nr,
+                                               const int2 *tab, const float4 *texels, const int2 *btab, const bump_texel *bumps,
+                                               bool want_normal, f3 &ns, bool &bumped) {
+    bumped = false;
+    if (btab == nullptr) return texture_mcol(mats, matId, type, rec, o, d, t, tab, texels);
+    const float *m = mats + matId * MAT_WORDS;
+    f3 mcol = mk(m[0], m[1], m[2]);
+    const int2 e = tab[matId];
+    int2 be = btab[matId];
+    if (!want_normal || m[9] > 0.0f) be.y = 0;                              // (the emitter exit uses no normal either)
+    if ((e.y > 0 || be.y > 0) && (type == (uint32_t)PT_SPHERE || type == (uint32_t)PT_CUBE)) {
+        const f3 q = mv_point(rec, point_on_ray(o, d, t));
+        if (e.y > 0) {
+            const int k = env_texel(q.x, q.y, q.z, e.y);
+            if (k >= 0) {
+                const float4 c = texels[e.x + k];
+                mcol = mk(mcol.x * c.x, mcol.y * c.y, mcol.z * c.z);
+            }
+        }
+        if (be.y > 0) bumped = bump_normal_q(type, rec, q.x, q.y, q.z, d.x, d.y, d.z, nr.x, nr.y, nr.z, bumps + be.x, be.y, ns.x, ns.y, ns.z);
+    }
+    return mcol;
+}
+
+// ---------------------------------------------------------------------------
 // direct lighting (PT_DIRECT_LIGHT): the last bounce of a diffuse hit aims at a sampled light
 // ---------------------------------------------------------------------------
 // light element record: 56 dwords, made on the host at pt_init (pt_lights.hpp: ptlight::records) from pt_light_elements'
@@ -770,6 +806,27 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
     if (missed) *missed = true;                            // ends with throughput * E(d), DESIGN.md section 6.16
     else ps.c = mk(0.0f, 0.0f, 0.0f);                      // pathtrace.cu:262-264
     return false;
+}
+
+// The TEX form as tile_shade calls it (DESIGN.md sections 6.19 and 6.22): mcol from the material's colour texture, the shading
+// normal from its bump map, then shade_scatter<GLOSSY, false, true> about that normal.  A perturbed lane never defers its
+// diffuse direction: the guard needs it -- a mirror's or a diffuse surface's new direction that does not leave the surface
+// the intersection test reported (nr) is reflected about nr, not renormalised.  Dielectrics keep what comes out.
+// btab == nullptr: no bump map in the session, and this is the call of section 6.19.
+template <bool GLOSSY, typename P>
+PTD bool shade_scatter_tex(PathState &ps, float t, f3 nr, int matId, int outside, const float *mats, int iter, int pixel, int depth,
+                           bool last_bounce, bool defer_diffuse, bool *deferred, bool *missed, uint32_t type, P rec,
+                           const int2 *tab, const float4 *texels, const int2 *btab, const bump_texel *bumps) {
+    f3 mcol = mk(0.0f, 0.0f, 0.0f), n = nr;
+    bool bumped = false;
+    if (t > 0.0f) mcol = texture_bump_mcol(mats, matId, type, rec, ps.o, ps.d, t, nr, tab, texels, btab, bumps, !last_bounce, n, bumped);
+    const bool alive = shade_scatter<GLOSSY, false, true>(ps, t, n, matId, outside, mats, iter, pixel, depth, last_bounce,
+                                                          defer_diffuse && !bumped, deferred, missed, nullptr, 0, &mcol);
+    if (bumped && alive) {
+        const float *m = mats + matId * MAT_WORDS;
+        if ((m[6] > 0.0f || !(m[7] > 0.0f)) && !(dot(ps.d, nr) > 0.0f)) ps.d = reflect(ps.d, nr);
+    }
+    return alive;
 }
 
 #undef PTD

@@ -44,6 +44,8 @@ void pt_free(void) {
     if (R.d_lights) (void)hipFree(R.d_lights);
     if (R.d_tex) (void)hipFree(R.d_tex);
     if (R.d_tex_tab) (void)hipFree(R.d_tex_tab);
+    if (R.d_bump) (void)hipFree(R.d_bump);
+    if (R.d_bump_tab) (void)hipFree(R.d_bump_tab);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -756,9 +758,10 @@ int pt_set_texture(int material, const float *texels, int n) {
             return fail(PT_ERR_NOMEM, "pt_set_texture: %zu bytes of device memory for the session's textures", total * 16);
         }
         HIPCHK(hipMemcpy(d_new, quad.data(), total * 16, hipMemcpyHostToDevice));
-        if (!R.d_tex_tab) HIPCHK(hipMalloc((void **)&R.d_tex_tab, tab.size() * sizeof(int2)));
-        HIPCHK(hipMemcpy(R.d_tex_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
     }
+    // (the table also while no texture is left: a session with a bump map alone launches the TEX forms, which read it)
+    if (!R.d_tex_tab) HIPCHK(hipMalloc((void **)&R.d_tex_tab, tab.size() * sizeof(int2)));
+    HIPCHK(hipMemcpy(R.d_tex_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
     // the albedo plane follows the table: stale unless this call left every texel as it was
     const int old_n = R.tex_n[(size_t)material];
     if (old_n != n || (n > 0 && memcmp(R.tex_keep[(size_t)material].data(), texels, (size_t)6 * (size_t)n * (size_t)n * 12) != 0))
@@ -784,6 +787,83 @@ int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
     if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
         return fail(PT_ERR_INVALID, "pt_get_texture: room for %d texels, the texture has %zu", texels ? capacity_texels : 0, count);
     memcpy(texels, R.tex_keep[(size_t)material].data(), count * 12);
+    return PT_OK;
+}
+
+// Bump mapping (include/ptmi355.h): pt_set_texture's contract with a table and an array of its own.  A
+// texel keeps its first two floats {da, db}; the albedo plane reads no normal and stays valid.
+int pt_set_bump_map(int material, const float *texels, int n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_bump_map: not initialised");
+    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_set_bump_map: the session was not initialised with PT_TEXTURES");
+    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_set_bump_map: material %d outside [0, %d)", material, R.scene.nmats);
+    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_bump_map: n = %d outside [0, 1024]", n);
+    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_bump_map: null texels with n = %d", n);
+    if (!texels) n = 0;
+    const int rc = la_discard(LA_HOST);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(R.stream));
+    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
+        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
+        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
+    }
+    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    R.ov_active = false;
+    if (R.bump_n.empty()) { R.bump_n.assign((size_t)R.scene.nmats, 0); R.bump_keep.resize((size_t)R.scene.nmats); }
+    std::vector<int> bn = R.bump_n;
+    bn[(size_t)material] = n;
+    std::vector<int2> tab((size_t)R.scene.nmats);
+    size_t total = 0;
+    int nbump = 0;
+    for (int m = 0; m < R.scene.nmats; ++m) {
+        tab[(size_t)m] = make_int2((int)total, bn[(size_t)m]);
+        total += (size_t)6 * (size_t)bn[(size_t)m] * (size_t)bn[(size_t)m];
+        if (bn[(size_t)m] > 0) ++nbump;
+    }
+    if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "pt_set_bump_map: %zu texels in all (at most 2^31 - 1)", total);
+    ptd::bump_texel *d_new = nullptr;
+    if (nbump > 0) {
+        std::vector<float> pair(total * 2);
+        for (int m = 0; m < R.scene.nmats; ++m) {
+            const size_t cnt = (size_t)6 * (size_t)bn[(size_t)m] * (size_t)bn[(size_t)m];
+            const float *src = m == material ? texels : R.bump_keep[(size_t)m].data();
+            float *dst = pair.data() + (size_t)tab[(size_t)m].x * 2;
+            for (size_t k = 0; k < cnt; ++k) { dst[2 * k] = src[3 * k]; dst[2 * k + 1] = src[3 * k + 1]; }
+        }
+        if (hipMalloc((void **)&d_new, total * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PT_ERR_NOMEM, "pt_set_bump_map: %zu bytes of device memory for the session's bump maps", total * 8);
+        }
+        HIPCHK(hipMemcpy(d_new, pair.data(), total * 8, hipMemcpyHostToDevice));
+    }
+    if (!R.d_bump_tab) HIPCHK(hipMalloc((void **)&R.d_bump_tab, tab.size() * sizeof(int2)));
+    HIPCHK(hipMemcpy(R.d_bump_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
+    if (!R.d_tex_tab) {                                         // no pt_set_texture yet: the TEX forms read a table without textures
+        const std::vector<int2> none((size_t)R.scene.nmats, make_int2(0, 0));
+        HIPCHK(hipMalloc((void **)&R.d_tex_tab, none.size() * sizeof(int2)));
+        HIPCHK(hipMemcpy(R.d_tex_tab, none.data(), none.size() * sizeof(int2), hipMemcpyHostToDevice));
+    }
+    if (R.d_bump) (void)hipFree(R.d_bump);
+    R.d_bump = d_new;
+    R.bump_n = bn;
+    if (n > 0) R.bump_keep[(size_t)material].assign(texels, texels + (size_t)6 * (size_t)n * (size_t)n * 3);
+    else std::vector<float>().swap(R.bump_keep[(size_t)material]);
+    R.nbump = nbump;
+    return PT_OK;
+}
+
+int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_bump_map: not initialised");
+    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_get_bump_map: the session was not initialised with PT_TEXTURES");
+    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_get_bump_map: material %d outside [0, %d)", material, R.scene.nmats);
+    if (!n) return fail(PT_ERR_INVALID, "pt_get_bump_map: null n");
+    const int bn = R.bump_n.empty() ? 0 : R.bump_n[(size_t)material];
+    *n = bn;
+    if (bn == 0) return PT_OK;
+    const size_t count = (size_t)6 * (size_t)bn * (size_t)bn;
+    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
+        return fail(PT_ERR_INVALID, "pt_get_bump_map: room for %d texels, the map has %zu", texels ? capacity_texels : 0, count);
+    memcpy(texels, R.bump_keep[(size_t)material].data(), count * 12);
     return PT_OK;
 }
 
@@ -825,7 +905,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex == 0 && R.epi_enabled &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex + R.nbump == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 

@@ -88,6 +88,14 @@ struct Renderer {
     float4 *d_tex = nullptr;
     int2 *d_tex_tab = nullptr;
     int ntex = 0;
+    // ... and at most one cube bump map per material, kept the same way: bump_keep[m] / bump_n[m] as
+    // the caller gave them (pt_get_bump_map); d_bump: every map's {da, db} back to back, d_bump_tab: per material {offset in
+    // texels, n}, both rebuilt by pt_set_bump_map.  nbump = maps set; ntex + nbump > 0: the TEX forms, a kernel per bounce.
+    std::vector<std::vector<float>> bump_keep;
+    std::vector<int> bump_n;
+    ptd::bump_texel *d_bump = nullptr;
+    int2 *d_bump_tab = nullptr;
+    int nbump = 0;
     size_t lds_bytes = 0;
     Control *ctl = nullptr;
     Persist *persist = nullptr;

@@ -164,6 +164,8 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 // TEX: a PT_TEXTURES session while a texture is set (k_bounce only) -- a hit on a sphere or cube whose
 // material has a cube texture shades with material.color * texel (ptd::texture_mcol, shade_scatter<.., TEX>).  The gather runs on
 // those lanes only; the two pointers are read from the argument block where a lane hit, like the map's.
+// While a bump map is set too (BounceArgs::bump_tab, null otherwise) the same lanes read their material's
+// map and shade about the perturbed normal: ptd::shade_scatter_tex.
 template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = false, int SH = 0>
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
@@ -219,14 +221,17 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
                                                          depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr, lights, nlights);
             }
         } else if constexpr (TEX) {
-            f3 mcol = ptd::mk(0.0f, 0.0f, 0.0f);
-            if (t > 0.0f)                                      // (the fused pipelines name the primitive hit; without one, no tint)
-                mcol = ptd::texture_mcol(c.acc.mats, mat, geom >= 0 ? c.acc.ginfo[geom] >> 28 : (uint32_t)PT_TRIANGLE_MESH,
-                                         c.acc.grec + (size_t)(geom >= 0 ? geom : 0) * GREC_WORDS, ro, rd, t,
-                                         c.kargs ? karg_field<const int2 *>(offsetof(BounceArgs, tex_tab)) : a.tex_tab,
-                                         c.kargs ? karg_field<const float4 *>(offsetof(BounceArgs, tex)) : a.tex);
-            alive = ptd::shade_scatter<GLOSSY, false, true>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
-                                   depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr, nullptr, 0, &mcol);
+            // the bump table's pointer: a scalar, null while the session has no bump map -- tested before any per-lane work
+            const int2 *btab = c.kargs ? karg_field<const int2 *>(offsetof(BounceArgs, bump_tab)) : a.bump_tab;
+            // (the fused pipelines name the primitive hit; without one -- a mesh -- no tint and no bump.  With btab null this is
+            // texture_mcol and shade_scatter<.., TEX> of section 6.19; otherwise section 6.22's lookup, shader and guard)
+            alive = ptd::shade_scatter_tex<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
+                                   depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr,
+                                   geom >= 0 ? c.acc.ginfo[geom] >> 28 : (uint32_t)PT_TRIANGLE_MESH,
+                                   c.acc.grec + (size_t)(geom >= 0 ? geom : 0) * GREC_WORDS,
+                                   c.kargs ? karg_field<const int2 *>(offsetof(BounceArgs, tex_tab)) : a.tex_tab,
+                                   c.kargs ? karg_field<const float4 *>(offsetof(BounceArgs, tex)) : a.tex, btab,
+                                   c.kargs ? karg_field<const ptd::bump_texel *>(offsetof(BounceArgs, bumps)) : a.bumps);
         } else {
             alive = ptd::shade_scatter<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
                                    depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr);

@@ -776,6 +776,19 @@ int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
     return on_one(0, [&](Worker &) -> int { return one::pt_get_texture(material, texels, capacity_texels, n); });
 }
 
+// ... and the same bump maps
+int pt_set_bump_map(int material, const float *texels, int n) {
+    if (!G.live) return one::pt_set_bump_map(material, texels, n);
+    const int rc = multi_sync();
+    if (rc) return rc;
+    return on_all([&](Worker &) -> int { return one::pt_set_bump_map(material, texels, n); });
+}
+
+int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
+    if (!G.live) return one::pt_get_bump_map(material, texels, capacity_texels, n);
+    return on_one(0, [&](Worker &) -> int { return one::pt_get_bump_map(material, texels, capacity_texels, n); });
+}
+
 int pt_synchronize(void) {
     if (!G.live) return one::pt_synchronize();
     return multi_sync();
@@ -846,7 +859,7 @@ static int multi_trace(uint8_t *pbo_rgba, int iter0, int count, float *host_imag
     // own tile's pixels (those whose sum changed) into the caller's image while it traces (pt_trace_mapped)
     // (G.direct_ok was asked at pt_init; a PT_TEXTURES session runs a kernel per bounce while a texture is set -- the contexts'
     // threads are idle between calls, and every context has the same textures)
-    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange && G.w[0]->ctx.ntex == 0 &&
+    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange && G.w[0]->ctx.ntex + G.w[0]->ctx.nbump == 0 &&
         (G.w[0]->ctx.flags & PT_PIN_IMAGE) && multi_pin(host_image_sum, (size_t)G.npix * 12)) {
         int rc = exchange_settled();
         if (rc) return rc;
@@ -1106,6 +1119,22 @@ int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *mate
                                     const int32_t *tex_n, const int32_t *tex_offset) {
     return one::pt_probe_shade_scatter_textured(iter, depth, materials, num_materials, paths, isects, outside, n, deferred, geoms, num_geoms,
                                                 hit_geom, tex_texels, tex_n, tex_offset);
+}
+int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                   int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    return one::pt_bump_normal(geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
+}
+int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                         int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    return one::pt_probe_bump_normal(geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
+}
+int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                  const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                  const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                  const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
+                                  const int32_t *bump_offset) {
+    return one::pt_probe_shade_scatter_bumped(iter, depth, materials, num_materials, paths, isects, outside, n, deferred, geoms, num_geoms,
+                                              hit_geom, tex_texels, tex_n, tex_offset, bump_texels, bump_n, bump_offset);
 }
 int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
 int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }

@@ -156,6 +156,59 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_textured(int iter, i
     q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
 }
 
+// bump mapping through the kernels' own ptd::bump_normal: one lane per (primitive, world point, reported
+// normal, ray direction) record; rec: 36 words per primitive (inverseTransform, transform, invTranspose, 4 columns x 3 rows each)
+__global__ __launch_bounds__(64) void k_probe_bump_normal(const float *__restrict__ rec, const int32_t *__restrict__ type, const int32_t *__restrict__ hit_geom,
+                                                           const float *__restrict__ points, const float *__restrict__ normals,
+                                                           const float *__restrict__ dirs, int count, const ptd::bump_texel *__restrict__ texels, int n,
+                                                           float *__restrict__ out_normals, uint8_t *__restrict__ perturbed) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const int g = hit_geom[i];
+    float x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
+    bool hit = false;
+    if (type[g] == PT_SPHERE || type[g] == PT_CUBE)
+        hit = ptd::bump_normal((uint32_t)type[g], rec + (size_t)g * 36, points[3 * i], points[3 * i + 1], points[3 * i + 2],
+                               dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], x, y, z, texels, n, x, y, z);
+    out_normals[3 * i] = x; out_normals[3 * i + 1] = y; out_normals[3 * i + 2] = z;
+    perturbed[i] = hit ? 1 : 0;
+}
+
+// k_probe_shade_scatter_textured through ptd::shade_scatter_tex, the call of tile_shade<.., SH_TEX>: lookup, shader, guard
+__global__ __launch_bounds__(64) void k_probe_shade_scatter_bumped(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
+                                                                    const pt_shadeable_intersection *__restrict__ isects,
+                                                                    const uint8_t *__restrict__ outside, int n, int defer,
+                                                                    const float *__restrict__ rec, const int32_t *__restrict__ type,
+                                                                    const int32_t *__restrict__ hit_geom, const float4 *__restrict__ texels,
+                                                                    const int2 *__restrict__ tab, const ptd::bump_texel *__restrict__ bumps,
+                                                                    const int2 *__restrict__ btab) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    pt_path_segment p = paths[i];
+    if (p.remainingBounces <= 0) return;
+    const pt_shadeable_intersection x = isects[i];
+    ptd::PathState ps;
+    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
+    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
+    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    bool deferred = false;
+    const int g = x.t > 0.0f ? hit_geom[i] : 0;
+    const bool alive = ptd::shade_scatter_tex<false>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
+                                                     outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                                     defer != 0, &deferred, nullptr, (uint32_t)type[g], rec + (size_t)g * 36, tab, texels, btab, bumps);
+    if (deferred) {
+        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
+        ps.d = ptd::hemisphere(ps.d, rng);
+    }
+    pt_path_segment *q = paths + i;
+    if (alive) {
+        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
+        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
+    }
+    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
+    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
+}
+
 // PT_DIRECT_LIGHT's sampler through the kernels' own ptd::direct_sample, seeded like k_probe_hemisphere
 __global__ __launch_bounds__(64) void k_probe_direct_sample(const float *__restrict__ lights, int nlights, const float *__restrict__ P,
                                                              const float *__restrict__ nrm, const uint32_t *__restrict__ seeds, int count,
@@ -623,6 +676,152 @@ int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *mate
     }
     hipLaunchKernelGGL(k_probe_shade_scatter_textured, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
                        d_outside, n, deferred, d_inv, d_type, d_hit, d_tex, d_tab);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+// ---- bump mapping (PT_TEXTURES) ----
+// the primitives as ptd::bump_normal reads them: inverseTransform, transform, invTranspose, 12 words each, and the type
+static void bump_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &rec, std::vector<int32_t> &type) {
+    rec.assign((size_t)std::max(1, num_geoms) * 36, 0.0f);
+    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
+    for (int g = 0; g < num_geoms; ++g) {
+        const pt_mat4 *ms[3] = {&geoms[g].inverseTransform, &geoms[g].transform, &geoms[g].invTranspose};
+        for (int m = 0; m < 3; ++m)
+            for (int c = 0; c < 4; ++c)
+                for (int r = 0; r < 3; ++r) rec[(size_t)g * 36 + m * 12 + c * 3 + r] = ms[m]->m[c][r];
+        type[(size_t)g] = (int32_t)geoms[g].type;
+    }
+}
+// {da, db} of `count` RGB texels
+static std::vector<float> bump_pairs(const float *texels, size_t count) {
+    std::vector<float> pair(std::max<size_t>(count, 1) * 2, 0.0f);
+    for (size_t k = 0; k < count; ++k) { pair[2 * k] = texels[3 * k]; pair[2 * k + 1] = texels[3 * k + 1]; }
+    return pair;
+}
+static int bump_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals,
+                     const float *dirs, int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    const int rc = texture_args(who, geoms, num_geoms, hit_geom, points, count, n);
+    if (rc) return rc;
+    if (!texels || (count > 0 && (!normals || !dirs || !out_normals || !perturbed)))
+        return fail(PT_ERR_INVALID, "%s: null array (count %d)", who, count);
+    return PT_OK;
+}
+
+int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                   int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    const int rc = bump_args("pt_bump_normal", geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
+    if (rc) return rc;
+    std::vector<float> rec;
+    std::vector<int32_t> type;
+    bump_geoms(geoms, num_geoms, rec, type);
+    const std::vector<float> pair = bump_pairs(texels, (size_t)6 * (size_t)n * (size_t)n);
+    for (int i = 0; i < count; ++i) {
+        const int g = hit_geom[i];
+        float x = normals[3 * i], y = normals[3 * i + 1], z = normals[3 * i + 2];
+        bool hit = false;
+        if (type[(size_t)g] == PT_SPHERE || type[(size_t)g] == PT_CUBE)
+            hit = ptd::bump_normal((uint32_t)type[(size_t)g], rec.data() + (size_t)g * 36, points[3 * i], points[3 * i + 1], points[3 * i + 2],
+                                   dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], x, y, z, (const ptd::bump_texel *)pair.data(), n, x, y, z);
+        out_normals[3 * i] = x; out_normals[3 * i + 1] = y; out_normals[3 * i + 2] = z;
+        perturbed[i] = hit ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
+                         int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    const int rc = bump_args("pt_probe_bump_normal", geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
+    if (rc) return rc;
+    if (count > (1 << 26)) return fail(PT_ERR_INVALID, "pt_probe_bump_normal: bad argument (count %d)", count);
+    if (count == 0) return PT_OK;
+    std::vector<float> rec;
+    std::vector<int32_t> type;
+    bump_geoms(geoms, num_geoms, rec, type);
+    const std::vector<float> pair = bump_pairs(texels, (size_t)6 * (size_t)n * (size_t)n);
+    ProbeBufs b;
+    const ptd::bump_texel *d_tex = (const ptd::bump_texel *)b.get(pair.size() * 4, pair.data());
+    const float *d_rec = (const float *)b.get(rec.size() * 4, rec.data());
+    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
+    const int32_t *d_hit = (const int32_t *)b.get((size_t)count * 4, hit_geom);
+    const float *d_pts = (const float *)b.get((size_t)count * 12, points);
+    const float *d_nrm = (const float *)b.get((size_t)count * 12, normals);
+    const float *d_dir = (const float *)b.get((size_t)count * 12, dirs);
+    float *d_out = (float *)b.get((size_t)count * 12, nullptr);
+    uint8_t *d_flag = (uint8_t *)b.get((size_t)count, nullptr);
+    if (!d_tex || !d_rec || !d_type || !d_hit || !d_pts || !d_nrm || !d_dir || !d_out || !d_flag) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_bump_normal: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_bump_normal, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_rec, d_type, d_hit, d_pts, d_nrm, d_dir, count,
+                       d_tex, n, d_out, d_flag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_normals, d_out, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(perturbed, d_flag, (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                  const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
+                                  const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
+                                  const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
+                                  const int32_t *bump_offset) {
+    const char *who = "pt_probe_shade_scatter_bumped";
+    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)) ||
+        num_geoms < 0 || (num_geoms > 0 && !geoms) || (n > 0 && !hit_geom) || !tex_n || !tex_offset || !bump_n || !bump_offset)
+        return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    for (int i = 0; i < n; ++i) {
+        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
+            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
+        if (isects[i].t > 0.0f && (hit_geom[i] < 0 || hit_geom[i] >= num_geoms))
+            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
+    }
+    size_t total = 0, btotal = 0;                                  // texels the two tables reach
+    for (int m = 0; m < num_materials; ++m) {
+        if (tex_n[m] < 0 || tex_n[m] > 1024 || (tex_n[m] > 0 && tex_offset[m] < 0))
+            return fail(PT_ERR_INVALID, "%s: material %d has a texture of n = %d at offset %d", who, m, tex_n[m], tex_offset[m]);
+        if (bump_n[m] < 0 || bump_n[m] > 1024 || (bump_n[m] > 0 && bump_offset[m] < 0))
+            return fail(PT_ERR_INVALID, "%s: material %d has a bump map of n = %d at offset %d", who, m, bump_n[m], bump_offset[m]);
+        if (tex_n[m] > 0) total = std::max(total, (size_t)tex_offset[m] + (size_t)6 * (size_t)tex_n[m] * (size_t)tex_n[m]);
+        if (bump_n[m] > 0) btotal = std::max(btotal, (size_t)bump_offset[m] + (size_t)6 * (size_t)bump_n[m] * (size_t)bump_n[m]);
+    }
+    if ((total > 0 && !tex_texels) || (btotal > 0 && !bump_texels)) return fail(PT_ERR_INVALID, "%s: null texels", who);
+    if (total > (size_t)0x7fffffff || btotal > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "%s: %zu texels in all (at most 2^31 - 1)", who, std::max(total, btotal));
+    if (n == 0) return PT_OK;
+    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
+    pack_materials(materials, num_materials, mrec.data(), false);
+    std::vector<float> rec;
+    std::vector<int32_t> type;
+    bump_geoms(geoms, num_geoms, rec, type);
+    std::vector<float> quad(std::max<size_t>(total, 1) * 4, 0.0f);
+    for (size_t k = 0; k < total; ++k) { quad[4 * k] = tex_texels[3 * k]; quad[4 * k + 1] = tex_texels[3 * k + 1]; quad[4 * k + 2] = tex_texels[3 * k + 2]; }
+    const std::vector<float> pair = bump_pairs(bump_texels, btotal);
+    std::vector<int2> tab((size_t)num_materials), btab((size_t)num_materials);
+    for (int m = 0; m < num_materials; ++m) {
+        tab[(size_t)m] = make_int2(tex_n[m] > 0 ? tex_offset[m] : 0, tex_n[m]);
+        btab[(size_t)m] = make_int2(bump_n[m] > 0 ? bump_offset[m] : 0, bump_n[m]);
+    }
+    ProbeBufs b;
+    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
+    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
+    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
+    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
+    const float *d_rec = (const float *)b.get(rec.size() * 4, rec.data());
+    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
+    const int32_t *d_hit = (const int32_t *)b.get((size_t)n * 4, hit_geom);
+    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
+    const int2 *d_tab = (const int2 *)b.get(tab.size() * sizeof(int2), tab.data());
+    const ptd::bump_texel *d_bump = (const ptd::bump_texel *)b.get(pair.size() * 4, pair.data());
+    const int2 *d_btab = (const int2 *)b.get(btab.size() * sizeof(int2), btab.data());
+    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside) || !d_rec || !d_type || !d_hit || !d_tex || !d_tab || !d_bump || !d_btab) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
+    }
+    hipLaunchKernelGGL(k_probe_shade_scatter_bumped, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
+                       d_outside, n, deferred, d_rec, d_type, d_hit, d_tex, d_tab, d_bump, d_btab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
     HIPCHK(hipDeviceSynchronize());

@@ -372,6 +372,11 @@ struct BounceArgs {
     // no texture set.  Read by the TEX instantiations of k_bounce, which such a session launches for every bounce.
     const float4 *tex;
     const int2 *tex_tab;
+    // ... and the same session's cube bump maps: every map's texels {da, db} back to back and, per
+    // material, {offset in texels, n}.  bump_tab == nullptr: no bump map set.  While one is set tex_tab is not null either (a
+    // table of n == 0 where no colour texture is), so the TEX instantiations are launched; no other kernel reads these words.
+    const ptd::bump_texel *bumps;
+    const int2 *bump_tab;
 };
 
 // the shading kernels' variant switch (template parameter SH of k_bounce, k_iteration, k_shade_sorted, k_shade_sorted_w): the

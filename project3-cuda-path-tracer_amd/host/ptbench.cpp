@@ -14,7 +14,8 @@
 //
 // --textures: PT_TEXTURES -- the cube textures the scene's TEXTURE blocks declare (pthost.h: pth_scene_texture) are uploaded with
 // pt_set_texture after pathtraceInit; each multiplies its material's colour on spheres and cubes (include/ptmi355.h, DESIGN.md
-// section 6.19).  scenes/cornell_textured.txt.  Without the switch the blocks are loaded and ignored.
+// section 6.19).  scenes/cornell_textured.txt.  The bump maps of its BUMPMAP blocks go up with pt_set_bump_map the same way (DESIGN.md
+// section 6.22; scenes/cornell_bumped.txt).  Without the switch the blocks are loaded and ignored.
 //
 // --direct: PT_DIRECT_LIGHT -- the last bounce of a path that hits a diffuse surface aims a final ray at a sampled point of an
 // emissive cube or sphere (DEPTH + 1 bounces; include/ptmi355.h).  scenes/cornell_two_lamps.txt.
@@ -235,6 +236,16 @@ int main(int argc, char **argv) {
             ++set;
         }
         printf("textures: %d of %d materials\n", set, sc->num_materials);
+        int bumps = 0;                                    // ... and its BUMPMAP blocks (pthost.h: pth_scene_bump_map)
+        for (int m = 0; m < sc->num_materials; ++m) {
+            const float *tex = nullptr;
+            int n = 0;
+            if (pth_scene_bump_map(sc, m, &tex, &n) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+            if (n == 0) continue;
+            if (pt_set_bump_map(m, tex, n) != PT_OK) { fprintf(stderr, "pt_set_bump_map: %s\n", pt_last_error()); return 1; }
+            ++bumps;
+        }
+        if (bumps > 0) printf("bump maps: %d of %d materials\n", bumps, sc->num_materials);
     }
 
     std::vector<float> image((size_t)W * H * 3, 0.0f);    // scene->state.image

@@ -1,6 +1,7 @@
 // pthost.cpp -- see pthost.h.  Host-only C++ (no GPU code): scene text -> reference-layout structs
 // with GLM 0.9.6.3's exact arithmetic, camera set-up, image output.
 #include "pthost.h"
+#include "pth_studs.h"
 
 #include <cmath>
 #include <cstdio>
@@ -293,10 +294,13 @@ bool load_obj(const std::string &path, const M4 &T, std::vector<pt_triangle> &ou
 
 // what pth_load_scene hands out: the public struct first (its layout is the ABI and does not change), the scene's cube
 // textures (TEXTURE blocks, a format extension) behind it -- per material n (0: none) and 6 * n * n RGB texels
+// ... and its cube bump maps (BUMPMAP blocks) the same way
 struct SceneFull {
     pth_scene pub;
     int32_t *tex_n;
     float **tex;
+    int32_t *bump_n;
+    float **bump;
 };
 
 // the cube texture of a `CHECKER <n> <cells> r0 g0 b0 r1 g1 b1` line: texel (face, j, i) takes colour 0 or 1 by the parity of
@@ -324,6 +328,14 @@ bool checker_texture(const std::vector<std::string> &t, std::vector<float> &out,
 extern "C" {
 
 const char *pth_last_error(void) { return g_err; }
+
+int pth_scene_bump_map(const pth_scene *s, int material, const float **texels, int *n) {
+    if (!s || !n || material < 0 || material >= s->num_materials) { snprintf(g_err, sizeof g_err, "pth_scene_bump_map: bad argument"); return -1; }
+    const SceneFull *f = reinterpret_cast<const SceneFull *>(s);
+    *n = f->bump_n[material];
+    if (texels) *texels = f->bump[material];
+    return 0;
+}
 
 int pth_scene_texture(const pth_scene *s, int material, const float **texels, int *n) {
     if (!s || !n || material < 0 || material >= s->num_materials) { snprintf(g_err, sizeof g_err, "pth_scene_texture: bad argument"); return -1; }
@@ -360,6 +372,8 @@ pth_scene *pth_load_scene(const char *path) {
     Builder b;
     std::vector<std::pair<int, std::vector<float>>> textures;        // TEXTURE blocks in file order: (material, texels)
     std::vector<int> texture_n;                                       // ... and their sizes
+    std::vector<std::pair<int, std::vector<float>>> bumps;           // BUMPMAP blocks likewise
+    std::vector<int> bump_n;
     SceneFull *full = (SceneFull *)calloc(1, sizeof(SceneFull));
     pth_scene *s = &full->pub;
     std::string dir(path);
@@ -463,17 +477,24 @@ pth_scene *pth_load_scene(const char *path) {
             camera.pixelLength[1] = 2 * yscaled / (float)camera.resolution[1];
             camera.view = P(normalize(sub(U(camera.lookAt), U(camera.position))));
             have_cam = true;
-        } else if (tok[0] == "TEXTURE") {                             // format extension (the reference's loader skips the block)
+        } else if (tok[0] == "TEXTURE" || tok[0] == "BUMPMAP") {      // format extensions (the reference's loader skips the blocks)
             // TEXTURE <material id>, then one line: CHECKER <n> <cells> r0 g0 b0 r1 g1 b1 | PFM <file> (n wide, 6 n tall, faces 0..5
-            // top to bottom, relative to the scene's directory)
-            if (tok.size() < 2 || atoi(tok[1].c_str()) < 0) { snprintf(g_err, sizeof g_err, "TEXTURE needs a material id"); goto fail; }
+            // top to bottom, relative to the scene's directory).  BUMPMAP <material id>, then STUDS <n> <cells> <slope> | PFM <file>
+            const bool bump = tok[0] == "BUMPMAP";
+            const char *what = bump ? "BUMPMAP" : "TEXTURE";
+            if (tok.size() < 2 || atoi(tok[1].c_str()) < 0) { snprintf(g_err, sizeof g_err, "%s needs a material id", what); goto fail; }
             const int mat = atoi(tok[1].c_str());
             fp.next(line);
             std::vector<std::string> t = tokens_of(line);
             std::vector<float> tex;
             int n = 0;
-            if (!t.empty() && t[0] == "CHECKER") {
+            if (!bump && !t.empty() && t[0] == "CHECKER") {
                 if (!checker_texture(t, tex, n)) { snprintf(g_err, sizeof g_err, "TEXTURE %d: bad CHECKER line (n and cells in [1, 1024], two colours)", mat); goto fail; }
+            } else if (bump && !t.empty() && t[0] == "STUDS") {
+                n = t.size() >= 4 ? atoi(t[1].c_str()) : 0;
+                if (t.size() < 4 || !pth_studs_texels(n, atoi(t[2].c_str()), (float)atof(t[3].c_str()), tex)) {
+                    snprintf(g_err, sizeof g_err, "BUMPMAP %d: bad STUDS line (n and cells in [1, 1024], a slope)", mat); goto fail;
+                }
             } else if (t.size() >= 2 && t[0] == "PFM") {
                 const std::string fullp = t[1][0] == '/' ? t[1] : dir + "/" + t[1];
                 int fw = 0, fh = 0;
@@ -484,16 +505,16 @@ pth_scene *pth_load_scene(const char *path) {
                     if (f) fclose(f);
                 }
                 if (fw < 1 || fw > 1024 || fh != 6 * fw) {
-                    snprintf(g_err, sizeof g_err, "TEXTURE %d: %s is not a colour PFM n wide and 6 n tall, n in [1, 1024]", mat, fullp.c_str()); goto fail;
+                    snprintf(g_err, sizeof g_err, "%s %d: %s is not a colour PFM n wide and 6 n tall, n in [1, 1024]", what, mat, fullp.c_str()); goto fail;
                 }
                 n = fw;
                 tex.resize((size_t)6 * n * n * 3);
                 if (pth_read_pfm(fullp.c_str(), tex.data(), fw, fh) != 0) goto fail;
             } else {
-                snprintf(g_err, sizeof g_err, "TEXTURE %d: expected CHECKER or PFM", mat); goto fail;
+                snprintf(g_err, sizeof g_err, "%s %d: expected %s or PFM", what, mat, bump ? "STUDS" : "CHECKER"); goto fail;
             }
-            textures.push_back(std::make_pair(mat, tex));
-            texture_n.push_back(n);
+            (bump ? bumps : textures).push_back(std::make_pair(mat, tex));
+            (bump ? bump_n : texture_n).push_back(n);
         }
     }
     if (!have_cam || b.mats.empty()) { snprintf(g_err, sizeof g_err, "scene %s has no CAMERA or no MATERIAL", path); goto fail; }
@@ -505,6 +526,20 @@ pth_scene *pth_load_scene(const char *path) {
         if (textures[i].first >= (int)b.mats.size()) {
             snprintf(g_err, sizeof g_err, "TEXTURE %d names a material of %zu", textures[i].first, b.mats.size()); goto fail;
         }
+    for (size_t i = 0; i < bumps.size(); ++i)
+        if (bumps[i].first >= (int)b.mats.size()) {
+            snprintf(g_err, sizeof g_err, "BUMPMAP %d names a material of %zu", bumps[i].first, b.mats.size()); goto fail;
+        }
+    full->bump_n = (int32_t *)calloc(b.mats.size(), sizeof(int32_t));
+    full->bump = (float **)calloc(b.mats.size(), sizeof(float *));
+    for (size_t i = 0; i < bumps.size(); ++i) {
+        const int m = bumps[i].first;
+        const std::vector<float> &tex = bumps[i].second;
+        free(full->bump[m]);
+        full->bump[m] = (float *)malloc(tex.size() * sizeof(float));
+        memcpy(full->bump[m], tex.data(), tex.size() * sizeof(float));
+        full->bump_n[m] = (int32_t)bump_n[i];
+    }
     full->tex_n = (int32_t *)calloc(b.mats.size(), sizeof(int32_t));
     full->tex = (float **)calloc(b.mats.size(), sizeof(float *));
     for (size_t i = 0; i < textures.size(); ++i) {                     // a later block for the same material replaces the earlier
@@ -539,6 +574,8 @@ void pth_free_scene(pth_scene *s) {
     SceneFull *full = reinterpret_cast<SceneFull *>(s);
     if (full->tex) for (int32_t m = 0; m < s->num_materials; ++m) free(full->tex[m]);
     free(full->tex); free(full->tex_n);
+    if (full->bump) for (int32_t m = 0; m < s->num_materials; ++m) free(full->bump[m]);
+    free(full->bump); free(full->bump_n);
     free(s->geoms); free(s->materials); free(s->triangles); free(s->meshes); free(full);
 }
 

@@ -38,6 +38,13 @@ const char *pth_last_error(void);
  * material's texture (0: none), *texels = its 6 * n * n RGB triples (owned by the scene; NULL when none).  0, or -1 for a bad
  * argument. */
 int pth_scene_texture(const pth_scene *s, int material, const float **texels, int *n);
+/* ... and its cube bump maps (include/ptmi355.h "bump mapping"): a top-level block
+ *   BUMPMAP <material id>
+ *   STUDS <n> <cells> <slope>   |   PFM <file>
+ * STUDS, integer arithmetic only: for texel (face, j, i), pa = (i * cells * 4 / n) % 4 and sa = -1, 0, 0, 1 for pa = 0..3, sb
+ * likewise from j; the texel is (slope * sa, slope * sb, 0) -- bevelled studs, every value 0 or +-slope exactly.  PFM as for
+ * TEXTURE, a texel (da, db, unused).  The accessor has pth_scene_texture's contract. */
+int pth_scene_bump_map(const pth_scene *s, int material, const float **texels, int *n);
 
 /* utilityCore::buildTransformationMatrix (utilities.cpp:65-72) + glm::inverse + glm::inverseTranspose
  * (scene.cpp:82-85), GLM 0.9.6.3 operation order */

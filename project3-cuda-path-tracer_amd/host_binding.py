@@ -12,7 +12,7 @@ from .binding import CAMERA_DT, GEOM_DT, MATERIAL_DT, MESH_DT, TRI_DT, PtError, 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libpthost.so")
-SRC = [os.path.join(HERE, "host", "pthost.cpp"), os.path.join(HERE, "host", "pthost.h")]
+SRC = [os.path.join(HERE, "host", "pthost.cpp"), os.path.join(HERE, "host", "pthost.h"), os.path.join(HERE, "host", "pth_studs.h")]
 
 
 class _PthScene(C.Structure):
@@ -38,7 +38,7 @@ PTBENCH = os.path.join(HERE, "ptbench")
 
 def build_ptbench(force=False):
     """The headless host binary (host/ptbench.cpp): links libptmi355.so by rpath."""
-    src = [os.path.join(HERE, "host", "ptbench.cpp"), SRC[0], SRC[1], os.path.join(HERE, "libptmi355.so")]
+    src = [os.path.join(HERE, "host", "ptbench.cpp"), SRC[0], SRC[1], os.path.join(HERE, "libptmi355.so"), SRC[2]]
     stale = force or not os.path.exists(PTBENCH) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(PTBENCH) for s in src)
     if stale:
@@ -65,6 +65,7 @@ def host_library():
         L.pth_write_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
         L.pth_read_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
         L.pth_scene_texture.argtypes = [C.POINTER(_PthScene), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        L.pth_scene_bump_map.argtypes = L.pth_scene_texture.argtypes
         _lib = L
     return _lib
 
@@ -101,6 +102,14 @@ def load_scene(path):
                 raise PtError("load_scene(%s): %s" % (path, L.pth_last_error().decode()))
             if n.value > 0:
                 scene.textures[m] = _copy(tex.value, 6 * n.value * n.value * 3, np.dtype("<f4")).reshape(6, n.value, n.value, 3)
+        # ... and its BUMPMAP blocks (pth_scene_bump_map), the same way
+        scene.bump_maps = {}
+        for m in range(s.num_materials):
+            tex, n = C.c_void_p(None), C.c_int(0)
+            if L.pth_scene_bump_map(p, m, C.byref(tex), C.byref(n)) != 0:
+                raise PtError("load_scene(%s): %s" % (path, L.pth_last_error().decode()))
+            if n.value > 0:
+                scene.bump_maps[m] = _copy(tex.value, 6 * n.value * n.value * 3, np.dtype("<f4")).reshape(6, n.value, n.value, 3)
     finally:
         L.pth_free_scene(p)
     return scene
