@@ -620,7 +620,8 @@ enum pt_stage { PT_STAGE_RAYGEN = 0, PT_STAGE_BOUNCE = 1, PT_STAGE_INTERSECT = 2
                 PT_STAGE_SORT = 3, PT_STAGE_GATHER = 4, PT_STAGE_MESH = 5, PT_STAGE_COUNT = 6 };
 typedef struct pt_profile {
     double  ms[PT_STAGE_COUNT];        /* summed event-elapsed time per stage */
-    int64_t launches[PT_STAGE_COUNT];  /* launches measured */
+    int64_t launches[PT_STAGE_COUNT];  /* launches measured; PT_STAGE_BOUNCE: bounces measured -- the one launch that
+                                        * does a batch's bounces 0 and 1 counts as two */
 } pt_profile;
 int pt_set_profiling(int enable);      /* also clears the accumulated profile */
 int pt_get_profile(pt_profile *out);   /* synchronises the stream, drains pending events */

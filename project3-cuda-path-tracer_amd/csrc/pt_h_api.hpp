@@ -219,6 +219,8 @@ static int init_impl(const pt_scene_desc *d) {
     if (const char *e = pt_experiment("PTMI355_OWN_SURFACE")) R.own_enabled = atoi(e) != 0;
     R.first_hit_enabled = true;
     if (const char *e = pt_experiment("PTMI355_FIRST_HIT")) R.first_hit_enabled = atoi(e) != 0;
+    R.first_two_enabled = true;
+    if (const char *e = pt_experiment("PTMI355_FIRST_TWO")) R.first_two_enabled = atoi(e) != 0;
     R.host_sparse_enabled = (d->flags & (PT_HOST_SPARSE | PT_SHARED_IMAGE)) != 0;
     if (const char *e = pt_experiment("PTMI355_ASYNC_DIRECT")) R.async_direct_enabled = atoi(e) != 0;
     R.pin_enabled = true;
@@ -482,7 +484,10 @@ static int init_impl(const pt_scene_desc *d) {
             // (... and the table form of bounce 0, stepped or generating, with and without the own-surface bits: enqueue_bounce)
             const void *fns_tab[4] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true) : fns[1],
                                       own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true) : fns[1]};
-            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3]}) {
+            // (... and the launch that does bounces 0 and 1, with and without the own-surface form)
+            const void *fns_two[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true, true) : fns[0],
+                                      own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true, true) : fns[0]};
+            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3], fns_two[0], fns_two[1]}) {
                 int n = 0;
                 HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
                 per_cu = std::min(per_cu, n);

@@ -130,11 +130,16 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // for a PT_TEXTURES session
 // `table`: the table form of bounce 0 (MODE_CACHE0; enqueue_bounce) of a session without mesh or material keys -- it has the
 // ENV and GLOSSY variants only, so SH's other bits do not apply
+// `first2` (with `table`): the launch that does bounces 0 and 1 (MODE_FIRST2; enqueue_bounce) -- it always generates its paths
 template <int MESH, int SH = 0>
-const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool table = false) {
+const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool table = false, bool first2 = false) {
     if constexpr (MESH == MESH_NONE) {
         if (table && !sorted) {
             constexpr int SH0 = SH & (SH_ENV | SH_GLOSSY);
+            if (first2) {
+                if (own) return slds ? (const void *)k_bounce<MODE_FIRST2, true, MESH, true, true, false, true, SH0> : (const void *)k_bounce<MODE_FIRST2, true, MESH, false, true, false, true, SH0>;
+                return slds ? (const void *)k_bounce<MODE_FIRST2, true, MESH, true, true, false, false, SH0> : (const void *)k_bounce<MODE_FIRST2, true, MESH, false, true, false, false, SH0>;
+            }
             if (own) {
                 if (slds) return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, true, true, false, true, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, true, false, false, true, SH0>;
                 return gen ? (const void *)k_bounce<MODE_CACHE0, true, MESH, false, true, false, true, SH0> : (const void *)k_bounce<MODE_CACHE0, true, MESH, false, false, false, true, SH0>;
@@ -199,7 +204,7 @@ void launch_bounce_at(const BounceArgs &a) {
             return;
         }
     }
-    if constexpr ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE) {
+    if constexpr ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE) {
         if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce); MODE_CACHE0 writes its bits
             if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>(a);
             else launch_k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>(a);
@@ -215,6 +220,9 @@ void launch_bounce(const BounceArgs &a) {
         launch_bounce_at<MODE, COMPACT, MESH_NONE, false>(a);
     } else if constexpr (MODE == MODE_CACHE0) {                  // bounce 0 by definition: batches generate their rays here too
         if (a.gen_rays) launch_bounce_at<MODE, COMPACT, MESH_NONE, true>(a); else launch_bounce_at<MODE, COMPACT, MESH_NONE, false>(a);
+    } else if constexpr (MODE == MODE_FIRST2) {                  // bounces 0 and 1 of a compacting batch: the paths are generated
+        static_assert(COMPACT, "MODE_FIRST2 compacts");
+        launch_bounce_at<MODE, COMPACT, MESH_NONE, true>(a);
     } else {
         const bool gen = a.gen_rays != 0;
         if (R.mesh_mode == MESH_BVH) { if (gen) launch_bounce_at<MODE, COMPACT, MESH_PRE, true>(a); else launch_bounce_at<MODE, COMPACT, MESH_PRE, false>(a); }
@@ -223,7 +231,9 @@ void launch_bounce(const BounceArgs &a) {
     }
 }
 
-int enqueue_bounce(int depth) {
+// `may_fuse`: the caller enqueues the whole batch and continues at R.step_depth (enqueue_batch_serial) -- bounce 0 may then take
+// bounce 1 with it in one launch (MODE_FIRST2, below).  The stepping interface never asks.
+int enqueue_bounce(int depth, bool may_fuse = false) {
     BounceArgs a = bounce_args(depth);
     R.own_form = false;
     const bool compact = (R.flags & PT_COMPACT) != 0;
@@ -287,6 +297,20 @@ int enqueue_bounce(int depth) {
                        R.mesh_mode == MESH_NONE && R.sort_keys == 0 && same_rays && a.tex_tab == nullptr &&
                        !(a.nlights > 0 && depth >= a.trace_depth - 1);
     const bool cached0 = depth == 0 && !unfused && ((R.flags & PT_CACHE_FIRST) || auto0);
+    // Bounces 0 and 1 in one launch: where a compacting batch's bounce 0 would take the table form by
+    // itself (not through the flag) and a plain bounce 1 follows it -- traceDepth >= 2, bounce 1 not one of a PT_DIRECT_LIGHT
+    // session's DIRECT bounces (auto0 has already excluded textures) -- the table form's survivors stay in their lanes and run
+    // through bounce 1's pipeline: the 40 B per survivor written to the pool and read straight back, a launch, a directory scan
+    // and an election are gone.  The launch is bounce 1's in every respect (depth, directory, buckets, defer_dir) except that it
+    // generates its paths and counts bounce 0's rays too.
+    const bool first2 = may_fuse && auto0 && !(R.flags & PT_CACHE_FIRST) && compact && R.gen_fused && R.first_two_enabled &&
+                        R.trace_depth >= 2 && !(a.nlights > 0 && 1 >= a.trace_depth - 1);
+    if (first2) {
+        depth = 1;
+        a.depth = 1;
+        a.dir_out = tile_dir(1);
+        a.gen_rays = 1;
+    }
     // Diffuse survivors leave their direction to the next bounce (pt_types.hpp: PENDING_DIR) when that bounce is the fused
     // compacting k_bounce without mesh pre-pass or material keys, the one kernel that draws it when it loads the path
     // (tile_load<RESOLVE>).  The pipeline is fixed for the session (pt_init's flags), so the next bounce of this batch --
@@ -339,7 +363,8 @@ int enqueue_bounce(int depth) {
     if (cached0) {
         a.isect = Isect{R.cache_mem, (uint32_t)R.map.tile_pixels};
         R.first_hit_launches++;
-        if (compact) launch_bounce<MODE_CACHE0, true>(a); else launch_bounce<MODE_CACHE0, false>(a);
+        if (first2) { R.first_two_launches++; tm.two_bounces(); launch_bounce<MODE_FIRST2, true>(a); }
+        else if (compact) launch_bounce<MODE_CACHE0, true>(a); else launch_bounce<MODE_CACHE0, false>(a);
     } else if (unfused) {
         if (compact) launch_bounce<MODE_ISECT, true>(a); else launch_bounce<MODE_ISECT, false>(a);
     } else {
@@ -694,8 +719,8 @@ int enqueue_batch_serial(int iter0, int count) {
         R.step_depth = R.trace_depth;
         R.whole = true;
     } else {
-        for (int d = 0; d < session_bounces(); ++d) {
-            rc = enqueue_bounce(d);
+        for (int d = 0; d < session_bounces(); d = R.step_depth) {      // (bounce 0 may take bounce 1 with it: enqueue_bounce)
+            rc = enqueue_bounce(d, true);
             if (rc) return rc;
         }
     }

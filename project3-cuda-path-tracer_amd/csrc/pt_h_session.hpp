@@ -52,6 +52,8 @@ struct Renderer {
     bool cache_valid = false;     // ... holds R.cam's first hits (cleared by pt_set_camera; filled by the next bounce 0 that reads it)
     bool first_hit_enabled = true;    // PTMI355_FIRST_HIT=0: only PT_CACHE_FIRST sessions read the table (the A/B control)
     bool first_hit_refence = false;   // the batch being enqueued on a lane filled the table: the next one starts from enter_lanes' event
+    bool first_two_enabled = true;    // PTMI355_FIRST_TWO=0: bounce 0 of the table form stays a launch of its own (the A/B control)
+    uint64_t first_two_launches = 0;  // launches that did bounces 0 and 1 (k_bounce<MODE_FIRST2>) since pt_init (ptdbg_first_two)
     uint64_t first_hit_fills = 0, first_hit_launches = 0;   // k_cache_first launches / bounce-0 launches of the table form since pt_init (ptdbg_first_hit)
     Isect isect{};
     float *final_mem = nullptr;   // float4[cap]: {r, g, b, stamp} of the paths that ended with a non-zero colour, index = pid
@@ -289,8 +291,8 @@ int drain_events(void) {
     for (size_t k = 0; k < R.ev_used; ++k) {
         float ms = 0.0f;
         HIPCHK(hipEventElapsedTime(&ms, R.ev[2 * k], R.ev[2 * k + 1]));
-        R.prof.ms[R.ev_stage[k]] += (double)ms;
-        R.prof.launches[R.ev_stage[k]] += 1;
+        R.prof.ms[R.ev_stage[k] & 0xff] += (double)ms;
+        R.prof.launches[R.ev_stage[k] & 0xff] += 1 + (R.ev_stage[k] >> 8);      // (a launch that did two bounces: StageTimer::two_bounces)
     }
     R.ev_used = 0;
     return PT_OK;
@@ -307,6 +309,9 @@ struct StageTimer {                  // brackets one launch when profiling is on
         on = hipEventRecord(R.ev[2 * k], R.stream) == hipSuccess;
     }
     ~StageTimer() { if (on) (void)hipEventRecord(R.ev[2 * k + 1], R.stream); }
+    // the bracketed launch does a batch's bounces 0 and 1 (enqueue_bounce): pt_profile::launches[PT_STAGE_BOUNCE] counts bounces, so
+    // that a profile's count stays steps x bounces whichever plan the batch took
+    void two_bounces() { if (on) R.ev_stage[k] |= 0x100; }
 };
 
 Pool carve_pool(float *mem, uint32_t cap) { return Pool{mem, cap}; }

@@ -12,7 +12,10 @@ namespace {
 // MODE_ISECT   : read the materialised planes written by k_intersect (PT_UNFUSED / sort)
 // MODE_CACHE0  : bounce 0 from the first-hit table (k_cache_first): PT_CACHE_FIRST (INSTRUCTION.md:87-89), and the plain fused
 //                pipeline by itself while its camera rays repeat (enqueue_bounce)
-enum { MODE_FUSED = 0, MODE_ISECT = 1, MODE_CACHE0 = 2 };
+// MODE_FIRST2  : the first launch of a batch does bounces 0 AND 1: every tile shades bounce 0 from the
+//                first-hit table in registers (tile_first) and its survivors go through the fused pipeline as bounce 1 in the
+//                lanes they have -- no pool in between
+enum { MODE_FUSED = 0, MODE_ISECT = 1, MODE_CACHE0 = 2, MODE_FIRST2 = 3 };
 
 // per-launch constants of a wave
 // A field of the kernel's argument block read again where it is used (k_bounce: BounceArgs is the one kernel
@@ -59,6 +62,7 @@ struct TileCtx {
 // a tile in flight: what its shading needs besides the wave's LDS block (rays, best keys, winner records)
 struct TileRegs {
     bool have, active;
+    bool miss0;                 // MODE_FIRST2 with an environment map: the path missed at bounce 0; tile_finish ends it (col and the LDS ray are bounce 0's)
     uint32_t i, src, tile, pid, smp;
     int pixel;
     f3 col;
@@ -79,6 +83,7 @@ __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c,
     own = 0u;
     constexpr bool gen_rays = GEN;
     tr.have = have; tr.i = i; tr.src = src; tr.tile = tile;
+    tr.miss0 = false;
     tr.pid = DEAD_PID; tr.smp = 0; tr.pixel = 0;
     tr.col = ptd::mk(1.0f, 1.0f, 1.0f);
     tr.mb.t = FLT_MAX; tr.mb.geom = -1; tr.mb.tri = -1;
@@ -117,6 +122,42 @@ __device__ __forceinline__ void tile_load(const BounceArgs &a, const TileCtx &c,
         rd = ptd::hemisphere(rd, rng);
     }
     tr.active = active;
+}
+
+// MODE_FIRST2: bounce 0 of a tile whose paths tile_load<GEN> has just generated, in registers.  The pixel's first-hit record is
+// read as the MODE_CACHE0 branch of run_tiles reads it and shaded by the shader that branch reaches through tile_shade (depth 0,
+// not the last bounce -- the launch plan asks for traceDepth >= 2 -- and the session's ENV / GLOSSY variant), with the diffuse
+// direction drawn on the spot: nobody is left to resolve a pending one, and the eager draw is the same engine and sampler.  A
+// survivor keeps its lane: ro / rd / tr.col become bounce 1's ray and throughput, `own` the primitive it leaves, and
+// tr.active means "survived bounce 0" from here on.  A path that ends writes its final colour here (stores only), except one
+// that missed under an environment map: its texel gather would make the whole wave wait in front of the cull, so the lane
+// stays marked (tr.miss0; its throughput is still tr.col, its direction goes to the wave's LDS block with the tile's rays) and
+// tile_finish ends it behind the survivors' stores, where the ENV kernels end every path.
+template <bool OWN, int SH>
+__device__ __forceinline__ void tile_first(const BounceArgs &a, const TileCtx &c, TileRegs &tr, f3 &ro, f3 &rd, uint32_t &own) {
+    constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0;
+    bool alive = false;
+    if (tr.active) {
+        const Isect tab = c.kargs ? karg_struct<Isect>(offsetof(BounceArgs, isect)) : a.isect;
+        const uint32_t tile_pixels = (uint32_t)(c.kargs ? karg_field<int>(offsetof(BounceArgs, map) + offsetof(TileMap, tile_pixels)) : a.map.tile_pixels);
+        const size_t k = tr.pid - tr.smp * tile_pixels;
+        const float4 h = *tab.first_hit(k);
+        const int2 id = *tab.first_id(k);
+        bool deferred = false, missed = false;
+        ptd::PathState ps;
+        ps.o = ro; ps.d = rd; ps.c = tr.col;
+        alive = ptd::shade_scatter<GLOSSY>(ps, h.x, ptd::mk(h.y, h.z, h.w), id.x & 0x7fffffff, (id.x < 0) ? 0 : 1, c.acc.mats,
+                                           c.iter0 + (int)tr.smp, tr.pixel, 0, false, false, &deferred, ENV ? &missed : nullptr);
+        if (alive) {
+            ro = ps.o; rd = ps.d; tr.col = ps.c;
+            if (OWN) own = (uint32_t)(id.y + 1);
+        } else if (ENV && missed) {
+            tr.miss0 = true;
+        } else {
+            put_final(c.kargs ? karg_field<float *>(offsetof(BounceArgs, fin)) : a.fin, tr.pid, ps.c, c.stamp);
+        }
+    }
+    tr.active = alive;
 }
 
 // Second half: shade / scatter with the intersection (t, nrm, mat, outside), write the final colour of the paths
@@ -280,7 +321,8 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
 
 // the tile with parity `par` has been fully tested: read its rays back from the wave's LDS block, fold the
 // winner and shade
-template <bool COMPACT, int MESH, bool SORT = false, bool DEFER = false, bool OWN = false, int SH = 0>
+// FIRST (MODE_FIRST2): the tile's lanes that missed at bounce 0 under an environment map end here (tile_first)
+template <bool COMPACT, int MESH, bool SORT = false, bool DEFER = false, bool OWN = false, int SH = 0, bool FIRST = false>
 __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &c, const WaveQ &q, int par, const Pool &in,
                                             const Pool &out, int depth, const TileRegs &tr, uint32_t n, uint32_t dst_base,
                                             uint32_t &packed, uint32_t &traced, uint32_t key_stride = 0) {
@@ -293,6 +335,11 @@ __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &
     // OWN: the launch plan admits scenes of up to OWN_MAX_GEOMS primitives, so geom + 1 fits the pid's four bits
     tile_shade<COMPACT, MESH, SORT, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
                                            OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom);
+    if constexpr (FIRST && (SH & SH_ENV) != 0) {
+        if (tr.miss0)
+            put_final(karg_field<float *>(offsetof(BounceArgs, fin)), tr.pid,
+                      ptd::miss_colour(tr.col, rd, karg_field<const float4 *>(offsetof(BounceArgs, env)), karg_field<int>(offsetof(BounceArgs, env_n))), c.stamp);
+    }
 }
 
 // The tiles [first, first + count) of one wave's run at one bounce, two in flight (see the intersection stages
@@ -370,7 +417,8 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
         f3 ro, rd;
         uint32_t own;
         tile_load<GEN, RESOLVE, OWN>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd, own);
-        if (MODE == MODE_FUSED) {
+        if (MODE == MODE_FIRST2) tile_first<OWN, SH>(a, c, tr, ro, rd, own);
+        if (MODE == MODE_FUSED || MODE == MODE_FIRST2) {
             const float4 *pre_hit = nullptr;
             if (MESH == MESH_PRE && tr.active) {
                 // slots whose flag is set carry a mesh result from k_mesh (a hit, or "walked, nothing hit")
@@ -385,11 +433,11 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
             }
             // (after the load has drawn a pending direction: the row test needs the ray as it is traced)
             cull_scene<MESH, OWN>(a.scene, c.acc, q, par, c.tri_lds, tr.active, ro, rd, tr.mb, pre_hit, masked, gmask,
-                                  (OWN && !GEN) ? own_surface_miss(c.acc, own, ro, rd) : 0xffffffffu);
+                                  (OWN && (!GEN || MODE == MODE_FIRST2)) ? own_surface_miss(c.acc, own, ro, rd) : 0xffffffffu);
             const uint32_t ticket = q.total;
             if (pending) {
                 drain_to(q, c.acc, prev_ticket);
-                tile_finish<COMPACT, MESH, SORT, DEFER, OWN, SH>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+                tile_finish<COMPACT, MESH, SORT, DEFER, OWN, SH, MODE == MODE_FIRST2>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
             }
             prev = tr; prev_ticket = ticket; pending = true; par ^= 1;
         } else if (MODE == MODE_CACHE0) {
@@ -421,7 +469,7 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
     }
     if (pending) {
         drain_to(q, c.acc, prev_ticket);
-        tile_finish<COMPACT, MESH, SORT, DEFER, OWN, SH>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
+        tile_finish<COMPACT, MESH, SORT, DEFER, OWN, SH, MODE == MODE_FIRST2>(a, c, q, par ^ 1, in, out, depth, prev, n, dst_base, packed, traced, key_stride);
     }
 }
 
@@ -433,10 +481,12 @@ __device__ uint32_t g_wave_hw[8][8192];
 #endif
 
 template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN = false, bool SORT = false, bool OWN = false, int SH = 0>
-__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
+__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
     // (MODE_CACHE0 only writes the bits: bounce 0 reads no own surface)
-    static_assert(!OWN || ((MODE == MODE_FUSED || MODE == MODE_CACHE0) && COMPACT && MESH == MESH_NONE && !SORT),
+    static_assert(!OWN || ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE && !SORT),
                   "own-surface form: the plain fused compacting kernel, or the table form of its bounce 0");
+    // (the launch of bounces 0 and 1: BounceArgs::depth is 1 -- directory, election and scan are bounce 1's -- and the paths are generated)
+    static_assert(MODE != MODE_FIRST2 || (COMPACT && MESH == MESH_NONE && GEN && !SORT), "MODE_FIRST2: the plain compacting pipeline's first launch");
 #ifdef PT_WAVE_TIMES
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -518,7 +568,17 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
 #endif
     // paths traced this bounce: with compaction it is simply the live count; otherwise count the alive
     // slots, one atomic per workgroup (summed through LDS) rather than one per wave on a single address
-    if (COMPACT) {
+    if (MODE == MODE_FIRST2) {
+        // bounce 0 traced the whole pool; bounce 1 the survivors tile_shade has counted per wave (`traced`): no directory holds
+        // their number, so it is summed like the non-compacting kernels' -- one atomic per workgroup (Control is zeroed per batch)
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->alive[0] = n;
+        if (lane == 0) sctl[8 + (threadIdx.x >> 6)] = traced;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t tb = sctl[8] + sctl[9] + sctl[10] + sctl[11];
+            if (tb) { atomicAdd(&a.ctl->nlive[1], tb); atomicAdd(&a.ctl->alive[1], tb); }
+        }
+    } else if (COMPACT) {
         if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->alive[a.depth] = n;
     } else {
         if (lane == 0) sctl[8 + (threadIdx.x >> 6)] = traced;

@@ -135,6 +135,19 @@ extern "C" int ptdbg_first_hit(unsigned long long out[2]) {
     return 0;
 }
 
+// diagnostics (not in include/ptmi355.h): launches since pt_init that did bounces 0 and 1 in one (k_bounce<MODE_FIRST2>; each is
+// also one of ptdbg_first_hit's out[1]).  A multi-device session sums its contexts.
+extern "C" int ptdbg_first_two(unsigned long long out[1]) {
+    if (G.live) {
+        out[0] = 0;
+        for (auto &wp : G.w) out[0] += wp->ctx.first_two_launches;
+        return 0;
+    }
+    if (!g_single.live) return -1;
+    out[0] = g_single.first_two_launches;
+    return 0;
+}
+
 // diagnostics (not in include/ptmi355.h): launches of k_gbuffer / k_atrous / k_denoise_mean since pt_init (single-device sessions)
 extern "C" int ptdbg_denoise(unsigned long long out[3]) {
     if (!g_single.live) return -1;
