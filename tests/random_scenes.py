@@ -1,0 +1,374 @@
+"""Random hostile scenes, shared by tests/tools/fuzz_gpu.py, tests/test_gpu_random_scenes.py and
+tests/test_random_scenes_cpu.py: cubes and spheres under arbitrary rotations, thin slabs (0.001), scales of 100 and 1e-4, a zero
+scale (no finite inverse: the primitive is never hit), enclosing shells, an eye inside primitives, 1 to 39 primitives, depths 1 to
+11, random materials.
+
+`scene(pt, seed, w, h)` draws from default_rng(seed) in the order the fuzz tool always drew: seed N is the scene it always was.
+Everything newer -- the GGX exponents, textures, bump maps, the sky -- comes from a second stream, default_rng([seed, 1]), in
+`features()`, so the first stream never moves."""
+import os
+
+import numpy as np
+
+import bump_model as bm
+import texture_model as tm
+from gpu_common import _resized
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F32 = np.float32
+MAX_DEPTH = 64                                                       # pt_stats::live; a PT_DIRECT_LIGHT session traces depth + 1 bounces
+_base = {}
+
+
+def base_camera():
+    """The 64 x 64 Cornell camera every scene's camera is a perturbation of."""
+    if "cam" not in _base:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "scenes.npz"))
+        _base["cam"] = np.array(z["cornell_64__camera"], copy=True).reshape(1)
+    return _base["cam"].copy()
+
+
+def draw(pt, seed, w, h):
+    """The first stream, whole: (geoms, materials, camera, depth, per_bounce, rng).  per_bounce is the tool's draw of a launch plan
+    (a kernel per bounce, or small batches in one launch) -- the caller's to apply; rng stands where the tool's cull-stress rays
+    continue."""
+    H = pt.host_binding.host_library()
+    rng = np.random.default_rng(seed)
+    nm = int(rng.integers(2, 12))
+    mats = np.zeros(nm, dtype=pt.MATERIAL_DT)
+    for m in mats:
+        m["color"] = rng.uniform(0.1, 1.0, 3)
+        m["spec_color"] = rng.uniform(0.5, 1.0, 3)
+        kind = rng.integers(4)
+        m["hasReflective"], m["hasRefractive"] = (1.0, 0.0) if kind == 1 else ((0.0, 1.0) if kind == 2 else (0.0, 0.0))
+        m["indexOfRefraction"] = rng.uniform(1.05, 2.5)
+        m["emittance"] = rng.uniform(1, 6) if kind == 3 else 0.0
+    mats[0]["emittance"] = 4.0
+    ng = int(rng.integers(1, 40))
+    geoms = np.zeros(ng, dtype=pt.GEOM_DT)
+    for k, g in enumerate(geoms):
+        g["type"] = rng.integers(2)
+        g["materialid"] = rng.integers(nm)
+        g["translation"] = rng.uniform(-5, 5, 3) + (0, 5, 0)
+        g["rotation"] = rng.uniform(-180, 180, 3) * (rng.random() < 0.6) + rng.choice([0.0, 90.0, 180.0, 45.0], 3) * (rng.random() < 0.3)
+        sc = rng.uniform(0.2, 4.0, 3)
+        r = rng.random()
+        if r < 0.2:
+            sc[rng.integers(3)] = rng.choice([0.02, 0.005, 0.001])
+        elif r < 0.25:
+            sc = np.full(3, rng.choice([30.0, 100.0]))
+        elif r < 0.3:
+            sc = np.full(3, rng.choice([1e-2, 1e-4]))
+        elif r < 0.33:
+            sc[rng.integers(3)] = 0.0
+        g["scale"] = sc
+        H.pth_build_geom_matrices(geoms.ctypes.data + k * pt.GEOM_DT.itemsize)
+    depth = int(rng.integers(1, 12))
+    # the camera moves too (the bounce-0 candidate masks and the cull boxes' reach follow it): near the scene, far
+    # outside it, sometimes looking elsewhere
+    cam = _resized(base_camera(), w, h)
+    r = rng.random()
+    if r < 0.5:
+        cam["position"][0] += rng.uniform(-3, 3, 3).astype(np.float32)
+    elif r < 0.6:
+        cam["position"][0] += (rng.uniform(-1, 1, 3) * rng.choice([30.0, 300.0])).astype(np.float32)
+    if rng.random() < 0.2:
+        a = rng.uniform(-0.8, 0.8)
+        cam["view"][0] = np.float32([np.sin(a), 0.0, np.cos(a)]) * np.float32(np.sign(cam["view"][0][2]) or 1.0)
+    per_bounce = bool(rng.random() < 0.5)
+    return geoms, mats, cam, depth, per_bounce, rng
+
+
+def scene(pt, seed, w, h):
+    """(geoms, materials, camera at w x h, depth) of seed `seed`."""
+    return draw(pt, seed, w, h)[:4]
+
+
+def zero_scaled(geoms):
+    """Which primitives carry a zero scale (their inverse matrices have no finite entry)."""
+    return (np.asarray(geoms["scale"]) == 0).any(axis=1)
+
+
+class Features:
+    """What the second stream adds to a scene: `materials` (the scene's with spec_exponent drawn), `textures` and `bump_maps`
+    ({material: [6, n, n, 3] float32}), `sky` (a [6, 4, 4, 3] gradient or None), `direct_depth`."""
+
+
+def _gradient(rng):
+    """A 4-texel sky: a colour at the horizon, another overhead, blended by the height of each texel's direction."""
+    low, high = rng.uniform(0.0, 1.5, 3), rng.uniform(0.0, 2.5, 3)
+    out = np.zeros((6, 4, 4, 3), dtype=F32)
+    ramp = (np.arange(4) + 0.5) / 4.0
+    for face in range(6):
+        for j in range(4):
+            for i in range(4):
+                s = ramp[(i + j + face) % 4]
+                out[face, j, i] = low * (1.0 - s) + high * s
+    return out
+
+
+def features(seed, materials, depth):
+    """The second stream, default_rng([seed, 1]): exponents from {0, 2, 50, 1e4} (the lobe off and on); per material a
+    checker texture and / or a bump map (studs, or noise with a flat row) of 1, 4 or 8 texels a side with slopes up to 3;
+    a sky or none; the depth of the PT_DIRECT_LIGHT session."""
+    rng = np.random.default_rng([seed, 1])
+    f = Features()
+    f.materials = np.array(materials, copy=True)
+    f.materials["spec_exponent"] = rng.choice([0.0, 2.0, 50.0, 1e4], len(materials))
+    f.textures, f.bump_maps = {}, {}
+    for m in range(len(materials)):
+        r = rng.random(2)
+        n = int(rng.choice([1, 4, 8]))
+        cells = int(rng.choice([1, 2, 4]))
+        c0, c1 = rng.uniform(0.0, 2.0, 3), rng.uniform(0.0, 2.0, 3)
+        slope = float(rng.uniform(0.1, 3.0))
+        noise = rng.normal(0, slope, (6, n, n, 3)).astype(F32)
+        use_studs = rng.random() < 0.5
+        if r[0] < 0.5:
+            f.textures[m] = tm.checker(n, min(cells, n), c0, c1)
+        if r[1] < 0.4:
+            if use_studs:
+                f.bump_maps[m] = bm.studs(n, min(cells, n), slope)
+            else:
+                if n > 1:
+                    noise[:, 0, :, :2] = 0                           # a row of flat texels: not perturbed
+                f.bump_maps[m] = noise
+    f.sky = _gradient(rng) if rng.random() < 0.75 else None
+    f.direct_depth = min(int(depth), MAX_DEPTH - 1)
+    return f
+
+
+# ---- the seed lists and what the models say about them (no device) -------------------------------------------------------------
+W, H = 40, 26                                                        # 1040 paths: 16 full waves and a 16-lane tail
+WIDE = (130, 9)                                                      # one seed of every session also runs flat and wide
+BATCHES = ((4, 1), (5, 1), (6, 2), (8, 1), (9, 1))                   # the tool's batches on the lanes, after iterations 1-3
+MOVE = (0.3, 0.2, 0.0)
+SIGMAS = (1.0, 0.35, 0.5)
+_refs = {}
+# Chosen with the generator above so that tests/test_random_scenes_cpu.py's floors hold for every list (they are conditions on the
+# lists, asserted there).  The first seed of a list also runs at 130 x 9: 1029 has depth 11, 21 primitives, the eye inside one,
+# textures, bump maps, both kinds of light element.  1028 is a single primitive that every camera ray misses.
+COMMON_SEEDS = (1029, 1000, 1002, 1003, 1004, 1006, 1007, 1008, 1009, 1012, 1014, 1016, 1018, 1022, 1024, 1026)
+PLAIN_SEEDS = (1029, 1000, 1002, 1028, 1004, 1006, 1007, 1008, 1009, 1012, 1014, 1016, 1018, 1022, 1024, 1026)
+GLOSSY_SEEDS = COMMON_SEEDS
+TEXTURED_SEEDS = COMMON_SEEDS
+DIRECT_SEEDS = COMMON_SEEDS                                          # every one has between 1 and 1024 light elements
+FILTER_SEEDS = PLAIN_SEEDS
+MESH_SEEDS = (1029, 1009, 1012, 1024)
+
+
+def groups(seeds):
+    return [tuple(seeds[k:k + 4]) for k in range(0, len(seeds), 4)]
+
+
+def next_seed(seeds, seed):
+    return seeds[(seeds.index(seed) + 1) % len(seeds)]
+
+
+def moved(cam, d):
+    """position and lookAt translated by d: view / up / right stay"""
+    c = cam.copy()
+    c["position"][0] += np.asarray(d, dtype=F32)
+    c["lookAt"][0] += np.asarray(d, dtype=F32)
+    return c
+
+
+def _cached(key, make):
+    if key not in _refs:
+        _refs[key] = make()
+    return _refs[key]
+
+
+class Run:
+    """A model's side of a session: `images[it]` the running sum after iteration it (read-only), `live[it]` the paths traced at
+    every bounce of iteration it, `ended[it]` the bounce at which each pixel's path of iteration it ended."""
+
+    def __init__(self, n):
+        self.n, self.images, self.live, self.ended = n, {}, {}, {}
+
+    def record(self, it, image, survivors, live=None):
+        """survivors: per bounce, the pixelIndex of the paths that survived it"""
+        img = image.copy()
+        img.setflags(write=False)
+        self.images[it] = img
+        cnt = np.zeros(self.n, dtype=np.int32)
+        for pix in survivors:
+            cnt[pix] += 1
+        self.ended[it] = cnt
+        self.live[it] = list(live) if live is not None else [self.n] + [len(pix) for pix in survivors]
+
+    def live_sum(self, its, depth):
+        out = [0] * depth
+        for it in its:
+            for d, v in enumerate(self.live[it][:depth]):
+                out[d] += v
+        return out
+
+
+def mesh_of(pt, seed, geoms, n_materials):
+    """The mesh session's soup of 300 triangles (slivers, zero-area and metre-sized ones) from default_rng([seed, 2]):
+    (geoms with the mesh primitive, triangles, meshes)."""
+    import mesh_cases
+    rng = np.random.default_rng([seed, 2])
+    tris = mesh_cases.soup(pt.TRI_DT, rng, n=300)
+    return pt.meshes.add_mesh(geoms, tris, material_id=int(rng.integers(n_materials)))
+
+
+def plain_run(po, pt, seed, w, h, oflags, cam=None, mesh=False, last=9):
+    """po.Tracer over iterations 1 .. last; cam: another camera than the seed's own."""
+    def make():
+        geoms, mats, c, depth = scene(pt, seed, w, h)
+        tris = meshes = None
+        if mesh:
+            geoms, tris, meshes = mesh_of(pt, seed, geoms, len(mats))
+            tris, meshes = tris.view(po.TRI_DT), meshes.view(po.MESH_DT)
+        ref = po.Tracer(np.ascontiguousarray(geoms).view(po.GEOM_DT), mats.view(po.MATERIAL_DT), c if cam is None else cam, depth,
+                        flags=oflags, trig=po.TRIG_SHARED, tris=tris, meshes=meshes)
+        run = Run(w * h)
+        for it in range(1, last + 1):
+            snaps = []
+            st = ref.iterate(it, snapshots=snaps)
+            alive = [s["paths"]["pixelIndex"][s["paths"]["remainingBounces"] > 0] for s in snaps]
+            run.record(it, ref.image, alive, live=list(st.live[:depth]))
+            run.rays = getattr(run, "rays", {})
+            run.rays[it] = int(st.rays)
+        return run
+    return _cached(("plain", seed, w, h, oflags, None if cam is None else cam.tobytes(), mesh, last), make)
+
+
+def _model_run(m, n, depth, its, after=None, direct=False):
+    run = Run(n)
+    for it in its:
+        snaps = []
+        m.iterate(it, snaps)
+        run.record(it, m.image, [s["pixelIndex"] for s in snaps], live=list(m.live) if direct and m.direct else None)
+        run.live[it] = (run.live[it] + [0] * (depth + 1))[:depth + 1 if direct and m.direct else depth]
+        if after is not None:
+            after(it, m)
+    return run
+
+
+def glossy_run(po, pt, seed, w, h):
+    """glossy_model.Model with the seed's sky over iterations 1 .. 9: (run, counts, features)."""
+    def make():
+        import glossy_model as gm
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        f = features(seed, mats, depth)
+        m = gm.Model(po, geoms, f.materials, cam, depth, glossy=True)
+        m.set_environment(f.sky)
+        run = _model_run(m, w * h, depth, range(1, 10))
+        return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, f
+    return _cached(("glossy", seed, w, h), make)
+
+
+def dropped(f):
+    """The bump map and the texture the textured session removes after iteration 3: the lowest material that has one."""
+    return (min(f.bump_maps) if f.bump_maps else None), (min(f.textures) if f.textures else None)
+
+
+def textured_run(po, pt, seed, w, h, mesh=False):
+    """bump_model.Model with the seed's textures, bump maps, sky and exponents: iterations 1-3, one bump map and one texture
+    removed, iterations 4-5.  (run, counts, features); counts: tinted, bumped, guarded and the lobe's."""
+    def make():
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        f = features(seed, mats, depth)
+        tris = meshes = None
+        if mesh:
+            geoms, tris, meshes = mesh_of(pt, seed, geoms, len(mats))
+        m = bm.Model(po, geoms, f.materials, cam, depth, tris=tris, meshes=meshes, glossy=True)
+        for k, t in f.textures.items():
+            m.set_texture(k, t)
+        for k, t in f.bump_maps.items():
+            m.set_bump_map(k, t)
+        m.set_environment(f.sky)
+        b, t = dropped(f)
+
+        def after(it, m):
+            if it == 3:
+                if b is not None:
+                    m.set_bump_map(b, None)
+                if t is not None:
+                    m.set_texture(t, None)
+        run = _model_run(m, w * h, depth, range(1, 6), after)
+        counts = {k: v for k, v in m.counts.items() if isinstance(v, int)}
+        counts.update(tinted=m.tinted, bumped=m.bumped, guarded=m.guarded)
+        return run, counts, f
+    return _cached(("textured", seed, w, h, mesh), make)
+
+
+def direct_run(po, pt, seed, w, h):
+    """direct_model.Model with the seed's sky and exponents over iterations 1 .. 9: (run, counts, features, light elements)."""
+    def make():
+        import direct_model as dm
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        f = features(seed, mats, depth)
+        m = dm.Model(po, geoms, f.materials, cam, f.direct_depth, glossy=True)
+        m.set_environment(f.sky)
+        run = _model_run(m, w * h, f.direct_depth, range(1, 10), direct=True)
+        return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, f, len(m.table)
+    return _cached(("direct", seed, w, h), make)
+
+
+def light_table_size(po, pt, seed, w, h):
+    import direct_model as dm
+    geoms, mats, _, _ = scene(pt, seed, w, h)
+    return len(dm.light_elements(np.ascontiguousarray(geoms).view(po.GEOM_DT), mats.view(po.MATERIAL_DT)))
+
+
+def first_hits(po, pt, seed, w, h, cam=None):
+    """The oracle's G-buffer of the seed's scene under its own camera (or cam)."""
+    def make():
+        import atrous_model as am
+        geoms, mats, c, depth = scene(pt, seed, w, h)
+        return am.gbuffer_from_oracle(po, c if cam is None else cam, depth, np.ascontiguousarray(geoms).view(po.GEOM_DT))
+    return _cached(("g", seed, w, h, None if cam is None else cam.tobytes()), make)
+
+
+def filter_run(po, pt, seed, other, w, h):
+    """The filters on the plain compacting session after two iterations: the G-buffer, pt_denoise at 1 and 5 levels, and three
+    temporal calls -- under the seed's camera, after a move of MOVE, and under seed `other`'s perturbed camera (every time on two
+    fresh iterations).  A dict: cams, g, images, denoise {levels: plane}, temporal [(result, Hc, Hn)], kept [share with history]."""
+    def make():
+        import atrous_model as am
+        import temporal_model as tpm
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        cams = [cam, moved(cam, MOVE), scene(pt, other, w, h)[2]]
+        out = dict(cams=cams, g=[], images=[], denoise={}, temporal=[], kept=[])
+        t = tpm.Temporal(w, h, mats)
+        for k, c in enumerate(cams):
+            g = first_hits(po, pt, seed, w, h, None if k == 0 else c)
+            image = plain_run(po, pt, seed, w, h, po.F_COMPACT, None if k == 0 else c, last=9 if k == 0 else 2).images[2]
+            out["g"].append(g)
+            out["images"].append(image)
+            if k == 0:
+                for levels in (1, 5):
+                    out["denoise"][levels] = am.denoise(image.reshape(h, w, 3), 2, g["normal"].reshape(h, w, 3), g["position"].reshape(h, w, 3),
+                                                        levels, *SIGMAS).reshape(-1, 3)
+            res = t.call(image, 2, c, g, 5, *SIGMAS)
+            out["temporal"].append((res, t.hc.copy(), t.hn.copy()))
+            out["kept"].append(float((t.hn > 0).mean()))
+        return out
+    return _cached(("filters", seed, other, w, h), make)
+
+
+def albedo_run(po, pt, seed, w, h):
+    """The textured session's albedo plane and the demodulating filter (3 levels) on its running sum after iteration 3."""
+    def make():
+        import albedo_model as alm
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        run, _, f = textured_run(po, pt, seed, w, h)
+        g = first_hits(po, pt, seed, w, h)
+        A = alm.albedo(po, geoms, f.materials, f.textures, cam, depth)
+        out = alm.denoise(run.images[3].reshape(h, w, 3), 3, A.reshape(h, w, 3), g["normal"].reshape(h, w, 3), g["position"].reshape(h, w, 3),
+                          3, *SIGMAS).reshape(-1, 3)
+        return A, out
+    return _cached(("albedo", seed, w, h), make)
+
+
+def first_hit_facts(po, pt, seed, w, h):
+    """(share of the frame's pixels that miss at bounce 0, whether some camera ray starts inside the primitive it hits)"""
+    geoms, mats, cam, depth = scene(pt, seed, w, h)
+    paths = po.generate_rays(cam, depth)
+    isects, outside = po.compute_intersections(paths, np.ascontiguousarray(geoms).view(po.GEOM_DT))
+    hit = isects["t"] > 0
+    return float((~hit).mean()), bool((hit & (outside == 0)).any())

@@ -1,0 +1,316 @@
+"""GPU parity on random hostile scenes (tests/random_scenes.py: the fuzz tool's generator -- arbitrary rotations, slabs of 0.001,
+scales of 100 and 1e-4, zero scales, enclosing shells, an eye inside primitives, up to 39 primitives, depths 1 to 11) for every
+shading feature and the filters, which the other modules hold against their models on Cornell-shaped scenes only: the first-hit
+table and k_bounce<MODE_FIRST2>, the own-surface early miss and the cube face table, environment maps, PT_GLOSSY, PT_DIRECT_LIGHT,
+PT_TEXTURES with bump maps, the G-buffer, pt_albedo, the A-trous filter and its reprojected history.
+
+Every session is the tool's call sequence -- pt_trace_batch(1, 2), one pathtrace(), five batches on the lanes, pt_get_image --
+at 40 x 26 (16 full waves and a 16-lane tail; several tiles of the fused kernels), the first seed of a list also at 130 x 9, under
+both launch plans; running sums are compared byte for byte with the numpy models (computed here, once per seed; no golden files),
+live and ray counters wherever the model counts them.  A test item is one group of four seeds under one session.
+tests/test_random_scenes_cpu.py shows from the models alone that the seed lists reach the branches named above.
+
+A failure names the seed, the session, the number of differing pixels, the first of them with both values, and the bounce at which
+that pixel's path ended in the model (per iteration): enough to go straight to the stepping interface."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import __graft_entry__ as ge  # noqa: E402,F401
+import random_scenes as rs  # noqa: E402
+from gpu_common import pt, launch_plan, bits  # noqa: E402,F401
+
+pytestmark = pytest.mark.gpu
+
+W, H = rs.W, rs.H
+F32 = np.float32
+
+
+def first_two(pt):
+    """launches that did bounces 0 and 1 since pathtraceInit"""
+    out = (C.c_ulonglong * 1)()
+    assert pt.library().ptdbg_first_two(out) == 0
+    return int(out[0])
+
+
+def frames(seeds, group):
+    """(seed, w, h) of a group: every seed at 40 x 26, the list's first seed also at 130 x 9."""
+    out = [(s, W, H) for s in group]
+    if seeds[0] in group:
+        out.append((seeds[0],) + rs.WIDE)
+    return out
+
+
+class Report:
+    """Collects what differs in one test item, so that one run shows every seed of the group."""
+
+    def __init__(self, session, plan):
+        self.session, self.plan, self.lines = session, plan, []
+
+    def image(self, seed, w, what, got, want, run=None, its=()):
+        bad = (bits(got) != bits(want)).any(axis=1)
+        if not bad.any():
+            return True
+        p = int(np.nonzero(bad)[0][0])
+        ends = ", ".join("%d: %d" % (it, run.ended[it][p]) for it in its) if run is not None else "-"
+        self.lines.append("seed %d, %s [%s], %s: %d of %d pixels differ; first pixel %d (x %d, y %d): got %r, want %r; its path ended at "
+                          "bounce (iteration: bounce) %s" % (seed, self.session, self.plan, what, int(bad.sum()), len(bad), p, p % w, p // w,
+                                                             got[p].tolist(), want[p].tolist(), ends))
+        return False
+
+    def equal(self, seed, what, got, want):
+        if got != want:
+            self.lines.append("seed %d, %s [%s], %s: got %r, want %r" % (seed, self.session, self.plan, what, got, want))
+
+    def done(self):
+        assert not self.lines, "\n".join(self.lines)
+
+
+def trace_sequence(pt, rep, seed, w, h, run, depth, counters=True, rays=None, last=9, what=""):
+    """The tool's calls against a model's run: a batch of two with the host image, pathtrace() per call, batches nobody waits for on
+    the lanes, the device image.  counters: pt_get_stats' live and ray counts after the two synchronous calls."""
+    n = w * h
+    img = np.zeros((n, 3), dtype=F32)
+    pt.trace_batch(1, 2, img)
+    rep.image(seed, w, what + "batch of 2", img, run.images[2], run, (1, 2))
+    if counters:
+        gs = pt.get_stats()
+        live = run.live_sum((1, 2), depth)
+        rep.equal(seed, what + "live counts of the batch", list(gs.live[:depth]), live)
+        rep.equal(seed, what + "rays of the batch", int(gs.rays), sum(live) if rays is None else rays[1] + rays[2])
+    got = pt.pathtrace(None, 0, 3)
+    rep.image(seed, w, what + "pathtrace(3)", got, run.images[3], run, (3,))
+    if counters:
+        gs = pt.get_stats()
+        rep.equal(seed, what + "live counts of iteration 3", list(gs.live[:depth]), run.live_sum((3,), depth))
+    if last == 3:
+        return
+    for it0, count in rs.BATCHES:
+        if it0 + count - 1 <= last:
+            pt.trace_batch_async(it0, count)
+    pt.synchronize()
+    rep.image(seed, w, what + "after the lanes", pt.get_image(n), run.images[last], run, range(4, last + 1))
+
+
+# ---- plain sessions against the oracle ---------------------------------------------------------------------------------------------
+PLAIN = {"compact": lambda pt, po: (pt.PT_COMPACT, po.F_COMPACT), "non-compacting": lambda pt, po: (0, 0),
+         "sorted": lambda pt, po: (pt.PT_COMPACT | pt.PT_SORT_MATERIAL, po.F_COMPACT | po.F_SORT)}
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.PLAIN_SEEDS))
+@pytest.mark.parametrize("pipeline", list(PLAIN))
+def test_plain_sessions(pt, po, launch_plan, pipeline, group):
+    """PT_COMPACT, 0 and PT_COMPACT | PT_SORT_MATERIAL against po.Tracer.  The compacting session says whether its batches began
+    with the fused bounce 0 + 1 (ptdbg_first_two) wherever the rule of DESIGN.md section 6.23 takes it -- a kernel per bounce,
+    depth 2 or more --, and runs again under the NEXT seed's perturbed camera: the first-hit table is refilled and reused."""
+    rep = Report("plain " + pipeline, launch_plan)
+    for seed, w, h in frames(rs.PLAIN_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        flags, oflags = PLAIN[pipeline](pt, po)
+        scene = pt.Scene(geoms, mats, cam, depth)
+        pt.pathtraceInit(scene, flags=flags, max_batch=2)
+        try:
+            run = rs.plain_run(po, pt, seed, w, h, oflags)
+            trace_sequence(pt, rep, seed, w, h, run, depth, counters=pipeline != "non-compacting", rays=run.rays)
+            if pipeline == "compact":
+                fused = launch_plan == "one launch per bounce" and depth >= 2
+                if fused:
+                    rep.equal(seed, "fused bounce 0 + 1 launches > 0", first_two(pt) > 0, True)
+                before = first_two(pt)
+                cam2 = rs.scene(pt, rs.next_seed(rs.PLAIN_SEEDS, seed), w, h)[2]
+                scene.camera = cam2
+                pt.set_camera(cam2, depth)
+                pt.clear_image()
+                run2 = rs.plain_run(po, pt, seed, w, h, oflags, cam=cam2)
+                trace_sequence(pt, rep, seed, w, h, run2, depth, rays=run2.rays, what="camera of seed %d: " % rs.next_seed(rs.PLAIN_SEEDS, seed))
+                if fused:
+                    rep.equal(seed, "fused launches under the second camera > 0", first_two(pt) > before, True)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+# ---- sky + glossy -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("group", rs.groups(rs.GLOSSY_SEEDS))
+def test_sky_and_glossy_sessions(pt, po, launch_plan, group):
+    """PT_COMPACT | PT_GLOSSY with the seed's sky (or none) against glossy_model.Model: the GGX lobe at grazing hits, inside shells."""
+    rep = Report("sky + glossy", launch_plan)
+    for seed, w, h in frames(rs.GLOSSY_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        run, _, f = rs.glossy_run(po, pt, seed, w, h)
+        pt.pathtraceInit(pt.Scene(geoms, f.materials, cam, depth), flags=pt.PT_COMPACT | pt.PT_GLOSSY, max_batch=2)
+        try:
+            if f.sky is not None:
+                pt.set_environment(f.sky)
+            trace_sequence(pt, rep, seed, w, h, run, depth)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+# ---- textures + bumps + sky + glossy -----------------------------------------------------------------------------------------------
+def textured_session(pt, rep, seed, w, h, run, f, geoms, cam, depth, flags, counters, tris=None, meshes=None):
+    scene = pt.Scene(geoms, f.materials, cam, depth, triangles=tris, meshes=meshes) if tris is not None else pt.Scene(geoms, f.materials, cam, depth)
+    pt.pathtraceInit(scene, flags=flags | pt.PT_TEXTURES | pt.PT_GLOSSY, max_batch=2)
+    try:
+        for k, t in f.bump_maps.items():
+            pt.set_bump_map(k, t)
+        for k, t in f.textures.items():
+            pt.set_texture(k, t)
+        if f.sky is not None:
+            pt.set_environment(f.sky)
+        trace_sequence(pt, rep, seed, w, h, run, depth, counters=counters, last=3)
+        b, t = rs.dropped(f)
+        if b is not None:
+            pt.set_bump_map(b, None)
+        if t is not None:
+            pt.set_texture(t, None)
+        for it in (4, 5):
+            pt.trace_batch_async(it, 1)
+        pt.synchronize()
+        rep.image(seed, w, "after a bump map and a texture were removed", pt.get_image(w * h), run.images[5], run, (4, 5))
+    finally:
+        pt.pathtraceFree()
+
+
+TEXTURED = {"compact": lambda pt: pt.PT_COMPACT, "non-compacting": lambda pt: 0, "sorted": lambda pt: pt.PT_COMPACT | pt.PT_SORT_MATERIAL}
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.TEXTURED_SEEDS))
+@pytest.mark.parametrize("pipeline", list(TEXTURED))
+def test_textured_and_bumped_sessions(pt, po, launch_plan, pipeline, group):
+    """PT_TEXTURES | PT_GLOSSY with the seed's checker textures, bump maps (studs and noise, 1 to 8 texels a side, slopes up to 3),
+    sky and exponents against bump_model.Model: texel lookups on 100 : 1 primitives, the guard on slivers.  After iteration 3 one
+    bump map and one texture are removed; two more iterations follow on the lanes."""
+    rep = Report("textures + bumps " + pipeline, launch_plan)
+    for seed, w, h in frames(rs.TEXTURED_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        run, _, f = rs.textured_run(po, pt, seed, w, h)
+        textured_session(pt, rep, seed, w, h, run, f, geoms, cam, depth, TEXTURED[pipeline](pt), pipeline != "non-compacting")
+    rep.done()
+
+
+# ---- direct + sky + glossy ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("group", rs.groups(rs.DIRECT_SEEDS))
+def test_direct_light_sessions(pt, po, launch_plan, group):
+    """PT_COMPACT | PT_DIRECT_LIGHT | PT_GLOSSY against direct_model.Model: points inside an emitting sphere, degenerate elements
+    (zero-area ones are not in the table), D + 1 bounces counted."""
+    rep = Report("direct + sky + glossy", launch_plan)
+    for seed, w, h in frames(rs.DIRECT_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        elements = rs.light_table_size(po, pt, seed, w, h)
+        if elements == 0 or elements > 1024:                         # (decided from the model; no seed of the list is such a one:
+            pytest.skip("seed %d: %d light elements" % (seed, elements))     # tests/test_random_scenes_cpu.py asserts it)
+        run, _, f, _ = rs.direct_run(po, pt, seed, w, h)
+        pt.pathtraceInit(pt.Scene(geoms, f.materials, cam, f.direct_depth), flags=pt.PT_COMPACT | pt.PT_DIRECT_LIGHT | pt.PT_GLOSSY, max_batch=2)
+        try:
+            if f.sky is not None:
+                pt.set_environment(f.sky)
+            trace_sequence(pt, rep, seed, w, h, run, f.direct_depth + 1)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+# ---- with a mesh -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hierarchy", [False, True])
+@pytest.mark.parametrize("session", ["plain", "textured"])
+def test_sessions_with_a_mesh(pt, po, launch_plan, session, hierarchy):
+    """A soup of 300 triangles beside the random primitives, through the loop over every triangle and through PT_MESH_BVH; in the
+    textured session the mesh's material may carry a texture and a bump map, which hits on the mesh ignore."""
+    rep = Report("mesh, %s, %s" % (session, "hierarchy" if hierarchy else "loop"), launch_plan)
+    extra = pt.PT_MESH_BVH if hierarchy else 0
+    for seed in rs.MESH_SEEDS:
+        geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
+        geoms, tris, meshes = rs.mesh_of(pt, seed, geoms, len(mats))
+        if session == "plain":
+            run = rs.plain_run(po, pt, seed, W, H, po.F_COMPACT, mesh=True)
+            pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth, triangles=tris, meshes=meshes), flags=pt.PT_COMPACT | extra, max_batch=2)
+            try:
+                trace_sequence(pt, rep, seed, W, H, run, depth, rays=run.rays)
+            finally:
+                pt.pathtraceFree()
+        else:
+            run, _, f = rs.textured_run(po, pt, seed, W, H, mesh=True)
+            textured_session(pt, rep, seed, W, H, run, f, geoms, cam, depth, pt.PT_COMPACT | extra, True, tris, meshes)
+    rep.done()
+
+
+# ---- the filters -------------------------------------------------------------------------------------------------------------------
+def planes_equal(rep, seed, w, what, got, want):
+    diff = bits(got) != bits(want)
+    if diff.any():
+        p = int(np.nonzero(diff.reshape(len(got), -1).any(axis=1))[0][0])
+        rep.lines.append("seed %d, %s [%s], %s: %d of %d words differ; first pixel %d (x %d, y %d): got %r, want %r" %
+                         (seed, rep.session, rep.plan, what, int(diff.sum()), diff.size, p, p % w, p // w, got[p].tolist(), want[p].tolist()))
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.FILTER_SEEDS))
+def test_filters(pt, po, launch_plan, group):
+    """On the plain compacting session after two iterations: pt_gbuffer against the oracle's first hits (|position| up to hundreds,
+    a depth discontinuity at nearly every pixel), pt_denoise at 1 and 5 levels, and pt_denoise_temporal with pt_history under the
+    seed's camera, after a move of (0.3, 0.2, 0) and under the next seed's perturbed camera, which leaves positions behind the old
+    camera and off its frame -- every pixel against atrous_model and temporal_model."""
+    rep = Report("filters", launch_plan)
+    for seed, w, h in frames(rs.FILTER_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        fr = rs.filter_run(po, pt, seed, rs.next_seed(rs.FILTER_SEEDS, seed), w, h)
+        scene = pt.Scene(geoms, mats, cam, depth)
+        pt.pathtraceInit(scene, flags=pt.PT_COMPACT, max_batch=2)
+        try:
+            for k, c in enumerate(fr["cams"]):
+                if k:
+                    scene.camera = c
+                    pt.set_camera(c, depth)
+                    pt.clear_image()
+                pt.trace_batch(1, 2)
+                what = ("own camera", "moved camera", "camera of the next seed")[k]
+                if not rep.image(seed, w, what + ": running sum", pt.get_image(w * h), fr["images"][k]):
+                    continue
+                g = pt.gbuffer()
+                for key in ("t", "normal", "position", "materialId"):
+                    planes_equal(rep, seed, w, what + ": G-buffer " + key, g[key], fr["g"][k][key])
+                if k == 0:
+                    for levels in (1, 5):
+                        planes_equal(rep, seed, w, "pt_denoise, %d levels" % levels, pt.denoise(2, levels, *rs.SIGMAS), fr["denoise"][levels])
+                got = pt.denoise_temporal(2, pt.DenoiseParams(5, *rs.SIGMAS), pt.TemporalParams(64, 0.1, 0.1))
+                hc, hn = pt.history()
+                want, whc, whn = fr["temporal"][k]
+                planes_equal(rep, seed, w, what + ": history lengths", hn, whn)
+                planes_equal(rep, seed, w, what + ": history colours", hc, whc)
+                planes_equal(rep, seed, w, what + ": pt_denoise_temporal", got, want)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.TEXTURED_SEEDS))
+def test_albedo_and_the_demodulating_filter(pt, po, launch_plan, group):
+    """On the textured session after three iterations: pt_albedo against albedo_model (tinted first hits on stretched primitives,
+    the clamp) and pt_denoise with the switch on."""
+    rep = Report("albedo", launch_plan)
+    for seed, w, h in frames(rs.TEXTURED_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        run, _, f = rs.textured_run(po, pt, seed, w, h)
+        A, want = rs.albedo_run(po, pt, seed, w, h)
+        pt.pathtraceInit(pt.Scene(geoms, f.materials, cam, depth), flags=pt.PT_COMPACT | pt.PT_TEXTURES | pt.PT_GLOSSY, max_batch=3)
+        try:
+            for k, t in f.bump_maps.items():
+                pt.set_bump_map(k, t)
+            for k, t in f.textures.items():
+                pt.set_texture(k, t)
+            if f.sky is not None:
+                pt.set_environment(f.sky)
+            pt.trace_batch(1, 3)
+            if rep.image(seed, w, "running sum", pt.get_image(w * h), run.images[3], run, (1, 2, 3)):
+                planes_equal(rep, seed, w, "pt_albedo", pt.albedo(), A)
+                pt.set_denoise_albedo(True)
+                planes_equal(rep, seed, w, "pt_denoise on irradiance, 3 levels", pt.denoise(3, 3, *rs.SIGMAS), want)
+        finally:
+            pt.pathtraceFree()
+    rep.done()

@@ -1,0 +1,233 @@
+"""The random scenes of tests/random_scenes.py, from the models alone (no device): what tests/test_gpu_random_scenes.py compares
+the kernels with cannot be vacuous.  The generator is deterministic and builds, seed by seed, the scene the fuzz tool's inline code
+always built; every model image, G-buffer, albedo plane and filter output of the chosen seeds is finite (zero-scale primitives
+stay in, so the device's byte comparison is never one of NaN payloads); and, summed over each session's seed list, the scenes reach
+the branches the sessions are there for -- stated as floors, not as measurements."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import __graft_entry__ as ge  # noqa: E402
+import random_scenes as rs  # noqa: E402
+
+W, H = rs.W, rs.H
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def pt():
+    p = ge.load_package()
+    p.build_host()
+    return p
+
+
+def historical(pt, seed):
+    """The scene construction of tests/tools/fuzz_gpu.py's main() as it stood before it moved to random_scenes.draw, draw for draw
+    (its PTMI355_WHOLE_MAX coin is returned, not applied): (geoms, materials, camera, depth, coin, the next draw of the stream)."""
+    Hl = pt.host_binding.host_library()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "scenes.npz"))
+    rng = np.random.default_rng(seed)
+    nm = int(rng.integers(2, 12))
+    mats = np.zeros(nm, dtype=pt.MATERIAL_DT)
+    for m in mats:
+        m["color"] = rng.uniform(0.1, 1.0, 3)
+        m["spec_color"] = rng.uniform(0.5, 1.0, 3)
+        kind = rng.integers(4)
+        m["hasReflective"], m["hasRefractive"] = (1.0, 0.0) if kind == 1 else ((0.0, 1.0) if kind == 2 else (0.0, 0.0))
+        m["indexOfRefraction"] = rng.uniform(1.05, 2.5)
+        m["emittance"] = rng.uniform(1, 6) if kind == 3 else 0.0
+    mats[0]["emittance"] = 4.0
+    ng = int(rng.integers(1, 40))
+    geoms = np.zeros(ng, dtype=pt.GEOM_DT)
+    for k, g in enumerate(geoms):
+        g["type"] = rng.integers(2)
+        g["materialid"] = rng.integers(nm)
+        g["translation"] = rng.uniform(-5, 5, 3) + (0, 5, 0)
+        g["rotation"] = rng.uniform(-180, 180, 3) * (rng.random() < 0.6) + rng.choice([0.0, 90.0, 180.0, 45.0], 3) * (rng.random() < 0.3)
+        sc = rng.uniform(0.2, 4.0, 3)
+        r = rng.random()
+        if r < 0.2:
+            sc[rng.integers(3)] = rng.choice([0.02, 0.005, 0.001])
+        elif r < 0.25:
+            sc = np.full(3, rng.choice([30.0, 100.0]))
+        elif r < 0.3:
+            sc = np.full(3, rng.choice([1e-2, 1e-4]))
+        elif r < 0.33:
+            sc[rng.integers(3)] = 0.0
+        g["scale"] = sc
+        Hl.pth_build_geom_matrices(geoms.ctypes.data + k * pt.GEOM_DT.itemsize)
+    depth = int(rng.integers(1, 12))
+    cam = np.array(z["cornell_64__camera"], copy=True).reshape(1)
+    r = rng.random()
+    if r < 0.5:
+        cam["position"][0] += rng.uniform(-3, 3, 3).astype(np.float32)
+    elif r < 0.6:
+        cam["position"][0] += (rng.uniform(-1, 1, 3) * rng.choice([30.0, 300.0])).astype(np.float32)
+    if rng.random() < 0.2:
+        a = rng.uniform(-0.8, 0.8)
+        cam["view"][0] = np.float32([np.sin(a), 0.0, np.cos(a)]) * np.float32(np.sign(cam["view"][0][2]) or 1.0)
+    coin = bool(rng.random() < 0.5)
+    return geoms, mats, cam, depth, coin, rng.random()
+
+
+# ---- determinism -----------------------------------------------------------------------------------------------------------------
+def test_seed_lists_are_sixteen_literal_seeds():
+    for seeds in (rs.PLAIN_SEEDS, rs.GLOSSY_SEEDS, rs.TEXTURED_SEEDS, rs.DIRECT_SEEDS, rs.FILTER_SEEDS):
+        assert len(seeds) == 16 and len(set(seeds)) == 16 and len(rs.groups(seeds)) == 4
+    assert len(rs.MESH_SEEDS) == 4
+
+
+@pytest.mark.parametrize("seed", sorted(set(rs.PLAIN_SEEDS + rs.TEXTURED_SEEDS + rs.DIRECT_SEEDS + (1, 2, 3, 1000, 1049))))
+def test_a_seed_builds_the_scene_it_always_built(pt, seed):
+    """At the tool's 64 x 64 the new function's bytes are the old inline code's -- geoms, materials, camera, depth, the launch-plan
+    coin and the place the stream stands at afterwards; at 40 x 26 only the camera's resolution and pixel lengths differ."""
+    old = historical(pt, seed)
+    new = rs.draw(pt, seed, 64, 64)
+    for a, b in zip(old[:3], new[:3]):
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    assert old[3] == new[3] and old[4] == new[4] and old[5] == new[5].random()
+    again = rs.scene(pt, seed, 64, 64)
+    assert [a.tobytes() for a in again[:3]] == [a.tobytes() for a in new[:3]] and again[3] == new[3]
+    small = rs.scene(pt, seed, W, H)
+    assert small[0].tobytes() == new[0].tobytes() and small[1].tobytes() == new[1].tobytes() and small[3] == new[3]
+    for k in small[2].dtype.names:
+        if k not in ("resolution", "pixelLength"):
+            assert small[2][k].tobytes() == new[2][k].tobytes(), k
+    assert tuple(small[2]["resolution"][0]) == (W, H)
+
+
+def test_the_second_stream_is_deterministic_and_leaves_the_scene_alone(pt):
+    for seed in rs.TEXTURED_SEEDS[:4]:
+        geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
+        before = mats.tobytes()
+        a, b = rs.features(seed, mats, depth), rs.features(seed, mats, depth)
+        assert mats.tobytes() == before
+        assert a.materials.tobytes() == b.materials.tobytes() and sorted(a.textures) == sorted(b.textures)
+        assert all(a.textures[k].tobytes() == b.textures[k].tobytes() for k in a.textures)
+        assert all(a.bump_maps[k].tobytes() == b.bump_maps[k].tobytes() for k in a.bump_maps)
+        assert (a.sky is None) == (b.sky is None) and (a.sky is None or a.sky.tobytes() == b.sky.tobytes())
+        plain = a.materials.copy()
+        plain["spec_exponent"] = 0
+        assert plain.tobytes() == before and set(np.unique(a.materials["spec_exponent"])) <= {0.0, 2.0, 50.0, 1e4}
+        for t in list(a.textures.values()) + list(a.bump_maps.values()):
+            assert t.shape[1] in (1, 4, 8) and t.shape == (6, t.shape[1], t.shape[1], 3) and np.abs(t).max() < 16
+        assert 1 <= a.direct_depth <= min(depth, rs.MAX_DEPTH - 1)
+
+
+# ---- the scenes are the hostile ones ---------------------------------------------------------------------------------------------
+def test_geometry_floors(pt, po):
+    for seeds in (rs.PLAIN_SEEDS, rs.GLOSSY_SEEDS, rs.TEXTURED_SEEDS, rs.DIRECT_SEEDS, rs.FILTER_SEEDS):
+        scenes = [rs.scene(pt, s, W, H) for s in seeds]
+        assert sum(bool(rs.zero_scaled(g).any()) for g, _, _, _ in scenes) >= 2           # zero-scale primitives stay in
+        for g, _, _, _ in scenes:
+            z = rs.zero_scaled(g)
+            assert not np.isfinite(g["inverseTransform"][z]).any(axis=(1, 2)).any() or not z.any()
+        counts = [len(g) for g, _, _, _ in scenes]
+        assert max(counts) >= 17 and min(counts) <= 16                                   # either side of the own-surface form's 15 + 1
+        depths = {d for _, _, _, d in scenes}
+        assert 1 in depths and 2 in depths and max(depths) >= 8
+        facts = [rs.first_hit_facts(po, pt, s, W, H) for s in seeds]
+        assert max(f[0] for f in facts) > 0.25                                            # a frame with more than a quarter misses
+        assert any(f[1] for f in facts)                                                   # a camera inside a primitive
+        thin = np.concatenate([g["scale"].min(axis=1) for g, _, _, _ in scenes])
+        big = np.concatenate([g["scale"].max(axis=1) for g, _, _, _ in scenes])
+        assert (thin == np.float32(0.001)).any() and (big >= 100).any() and (big == np.float32(1e-4)).any()
+
+
+def finite(*arrays):
+    return all(np.isfinite(a).all() for a in arrays)
+
+
+# ---- the sessions' references: finite, and not vacuous ---------------------------------------------------------------------------
+def test_plain_session_images_are_finite(pt, po):
+    for seed in rs.PLAIN_SEEDS:
+        for oflags in (po.F_COMPACT, 0, po.F_COMPACT | po.F_SORT):
+            run = rs.plain_run(po, pt, seed, W, H, oflags)
+            assert finite(*run.images.values()), seed
+        assert finite(*rs.plain_run(po, pt, seed, W, H, po.F_COMPACT, cam=rs.scene(pt, rs.next_seed(rs.PLAIN_SEEDS, seed), W, H)[2]).images.values())
+    lit = sum(bool((rs.plain_run(po, pt, s, W, H, po.F_COMPACT).images[9] != 0).any()) for s in rs.PLAIN_SEEDS)
+    assert lit >= 8
+
+
+def total(dicts, key):
+    return sum(d.get(key, 0) for d in dicts)
+
+
+def test_glossy_session_floors(pt, po):
+    counts = []
+    for seed in rs.GLOSSY_SEEDS:
+        run, c, f = rs.glossy_run(po, pt, seed, W, H)
+        assert finite(*run.images.values()), seed
+        counts.append(c)
+    assert total(counts, "hits") >= 1000 and total(counts, "h fallback") > 0 and total(counts, "r fallback") > 0
+    skies = [rs.glossy_run(po, pt, s, W, H)[2].sky is not None for s in rs.GLOSSY_SEEDS]
+    assert any(skies) and not all(skies)
+
+
+def test_textured_session_floors(pt, po):
+    counts = []
+    for seed in rs.TEXTURED_SEEDS:
+        run, c, f = rs.textured_run(po, pt, seed, W, H)
+        assert finite(*run.images.values()), seed
+        A, out = rs.albedo_run(po, pt, seed, W, H)
+        assert finite(A, out), seed
+        counts.append(c)
+    assert total(counts, "tinted") >= 10000 and total(counts, "bumped") >= 5000 and total(counts, "guarded") >= 100
+    assert total(counts, "hits") >= 1000 and total(counts, "h fallback") > 0 and total(counts, "r fallback") > 0
+    assert sum(bool((rs.albedo_run(po, pt, s, W, H)[0] != 1).any()) for s in rs.TEXTURED_SEEDS) >= 8
+    # the removal after iteration 3 takes something away in most seeds
+    fs = [rs.textured_run(po, pt, s, W, H)[2] for s in rs.TEXTURED_SEEDS]
+    assert sum(rs.dropped(f)[0] is not None for f in fs) >= 8 and sum(rs.dropped(f)[1] is not None for f in fs) >= 8
+
+
+def test_direct_session_floors(pt, po):
+    counts = []
+    for seed in rs.DIRECT_SEEDS:
+        assert 0 < rs.light_table_size(po, pt, seed, W, H) <= 1024, seed               # no seed of the list is ever skipped
+        run, c, f, elements = rs.direct_run(po, pt, seed, W, H)
+        assert finite(*run.images.values()), seed
+        counts.append(c)
+    assert total(counts, "sampled") >= 1000 and total(counts, "sphere") > 0 and total(counts, "cube") > 0 and total(counts, "inside") >= 1
+    final, occluded = total(counts, "final rays"), total(counts, "occluded")
+    assert final >= 300 and 0 < occluded < final                                         # some are occluded, some score
+    assert total(counts, "hits") >= 1000 and total(counts, "h fallback") > 0 and total(counts, "r fallback") > 0
+
+
+def test_filter_session_floors(pt, po):
+    kept = []
+    for seed in rs.FILTER_SEEDS:
+        fr = rs.filter_run(po, pt, seed, rs.next_seed(rs.FILTER_SEEDS, seed), W, H)
+        for g in fr["g"]:
+            assert finite(g["t"], g["normal"], g["position"]), seed
+        assert finite(*fr["images"]) and finite(*fr["denoise"].values()), seed
+        for res, hc, hn in fr["temporal"]:
+            assert finite(res, hc, hn), seed
+        assert fr["kept"][0] == 0
+        kept += fr["kept"][1:]
+    assert max(kept) > 0.5 and min(kept) < 0.05                                           # history that survives a move, and history that does not
+    far = [np.abs(rs.filter_run(po, pt, s, rs.next_seed(rs.FILTER_SEEDS, s), W, H)["g"][0]["position"]).max() for s in rs.FILTER_SEEDS]
+    assert max(far) >= 50
+
+
+def test_mesh_session_images_are_finite(pt, po):
+    for seed in rs.MESH_SEEDS:
+        assert finite(*rs.plain_run(po, pt, seed, W, H, po.F_COMPACT, mesh=True).images.values()), seed
+        run, c, f = rs.textured_run(po, pt, seed, W, H, mesh=True)
+        assert finite(*run.images.values()), seed
+    assert sum(rs.textured_run(po, pt, s, W, H, mesh=True)[1]["tinted"] for s in rs.MESH_SEEDS) > 0
+
+
+def test_wide_frames_are_finite(pt, po):
+    w, h = rs.WIDE
+    assert finite(*rs.plain_run(po, pt, rs.PLAIN_SEEDS[0], w, h, po.F_COMPACT).images.values())
+    assert finite(*rs.glossy_run(po, pt, rs.GLOSSY_SEEDS[0], w, h)[0].images.values())
+    assert finite(*rs.textured_run(po, pt, rs.TEXTURED_SEEDS[0], w, h)[0].images.values())
+    assert finite(*rs.direct_run(po, pt, rs.DIRECT_SEEDS[0], w, h)[0].images.values())
+    fr = rs.filter_run(po, pt, rs.FILTER_SEEDS[0], rs.FILTER_SEEDS[1], w, h)
+    assert finite(*fr["images"]) and finite(*fr["denoise"].values()) and all(finite(*t) for t in fr["temporal"])
+    assert all(finite(g["t"], g["normal"], g["position"]) for g in fr["g"])
+    assert finite(*rs.albedo_run(po, pt, rs.TEXTURED_SEEDS[0], w, h))

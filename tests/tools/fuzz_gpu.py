@@ -2,7 +2,8 @@
 """Soak / fuzz run on a GPU box (not part of the pytest suites): random scenes (cubes and spheres with random
 rotations, thin slabs, enclosing shells, tiny and huge primitives, random materials) traced for a few iterations
 under every pipeline, and the cull-stress rays of tests/cull_model.py through pt_intersect_once -- all compared with
-the CPU oracle bit for bit.  `mesh` mode: PT_MESH_BVH on random soups and smooth meshes incl. grazing rays.
+the CPU oracle bit for bit.  The scenes are tests/random_scenes.py's (`draw`: seed N is the scene it always was), which the suite
+runs too (tests/test_gpu_random_scenes.py, with the shading features and the filters this tool knows nothing of).  `mesh` mode: PT_MESH_BVH on random soups and smooth meshes incl. grazing rays.
 Usage: python tests/tools/fuzz_gpu.py [first_seed] [count]   |   python tests/tools/fuzz_gpu.py mesh [first_seed] [count]"""
 import os
 import sys
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as ge  # noqa: E402
 import cull_model  # noqa: E402
 import mesh_cases  # noqa: E402
+import random_scenes  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 
 
@@ -84,57 +86,14 @@ def main():
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 50
     pt = ge.load_package()
     po.build()
-    H = pt.host_binding.host_library()
-    z = np.load(os.path.join(ROOT, "tests", "golden", "scenes.npz"))
-    cam = z["cornell_64__camera"]
     bad = 0
     t0 = time.time()
     for seed in range(first, first + count):
         if (seed - first) % 50 == 0:
             print("seed %d (%.0f s, %d mismatches so far)" % (seed, time.time() - t0, bad), flush=True)
-        rng = np.random.default_rng(seed)
-        nm = int(rng.integers(2, 12))
-        mats = np.zeros(nm, dtype=pt.MATERIAL_DT)
-        for m in mats:
-            m["color"] = rng.uniform(0.1, 1.0, 3)
-            m["spec_color"] = rng.uniform(0.5, 1.0, 3)
-            kind = rng.integers(4)
-            m["hasReflective"], m["hasRefractive"] = (1.0, 0.0) if kind == 1 else ((0.0, 1.0) if kind == 2 else (0.0, 0.0))
-            m["indexOfRefraction"] = rng.uniform(1.05, 2.5)
-            m["emittance"] = rng.uniform(1, 6) if kind == 3 else 0.0
-        mats[0]["emittance"] = 4.0
-        ng = int(rng.integers(1, 40))
-        geoms = np.zeros(ng, dtype=pt.GEOM_DT)
-        for k, g in enumerate(geoms):
-            g["type"] = rng.integers(2)
-            g["materialid"] = rng.integers(nm)
-            g["translation"] = rng.uniform(-5, 5, 3) + (0, 5, 0)
-            g["rotation"] = rng.uniform(-180, 180, 3) * (rng.random() < 0.6) + rng.choice([0.0, 90.0, 180.0, 45.0], 3) * (rng.random() < 0.3)
-            sc = rng.uniform(0.2, 4.0, 3)
-            r = rng.random()
-            if r < 0.2:
-                sc[rng.integers(3)] = rng.choice([0.02, 0.005, 0.001])
-            elif r < 0.25:
-                sc = np.full(3, rng.choice([30.0, 100.0]))
-            elif r < 0.3:
-                sc = np.full(3, rng.choice([1e-2, 1e-4]))
-            elif r < 0.33:
-                sc[rng.integers(3)] = 0.0
-            g["scale"] = sc
-            H.pth_build_geom_matrices(geoms.ctypes.data + k * pt.GEOM_DT.itemsize)
-        depth = int(rng.integers(1, 12))
-        # the camera moves too (the bounce-0 candidate masks and the cull boxes' reach follow it): near the scene, far
-        # outside it, sometimes looking elsewhere; and either launch plan (a kernel per bounce / one launch per batch)
-        cam = np.array(z["cornell_64__camera"], copy=True).reshape(1)
-        r = rng.random()
-        if r < 0.5:
-            cam["position"][0] += rng.uniform(-3, 3, 3).astype(np.float32)
-        elif r < 0.6:
-            cam["position"][0] += (rng.uniform(-1, 1, 3) * rng.choice([30.0, 300.0])).astype(np.float32)
-        if rng.random() < 0.2:
-            a = rng.uniform(-0.8, 0.8)
-            cam["view"][0] = np.float32([np.sin(a), 0.0, np.cos(a)]) * np.float32(np.sign(cam["view"][0][2]) or 1.0)
-        if rng.random() < 0.5:
+        # the scene, and the launch plan it drew (a kernel per bounce / one launch per batch); rng goes on to the stress rays
+        geoms, mats, cam, depth, per_bounce, rng = random_scenes.draw(pt, seed, 64, 64)
+        if per_bounce:
             os.environ["PTMI355_WHOLE_MAX"] = "0"
         else:
             os.environ.pop("PTMI355_WHOLE_MAX", None)
