@@ -214,8 +214,8 @@ enum pt_flags {
                                     scores only if its nearest hit is the primitive it was aimed at ("direct lighting"
                                     below).  Its expectation is that of a plain session of depth
                                     D + 1 in a scene without specular surfaces.  Bounces 0 .. D - 2, emitters, misses,
-                                    mirrors and dielectrics are untouched; mesh emitters and the environment map are not
-                                    sampled; a scene without an emissive cube or sphere renders as without the flag, bit for
+                                    mirrors and dielectrics are untouched; mesh emitters are not sampled, the environment map
+                                    only with PT_DIRECT_SKY; a scene without an emissive cube or sphere renders as without the flag, bit for
                                     bit.  pt_stats reports D + 1 bounces (live[D] = the final rays), pt_trace_bounce accepts
                                     depth D.  Honoured by the fused pipelines (with and without PT_COMPACT, the fused form of
                                     PT_SORT_MATERIAL, meshes with and without PT_MESH_BVH), which run such a session a kernel
@@ -238,6 +238,17 @@ enum pt_flags {
                                     with a PT_SORT_MATERIAL session that would take the two-kernel form (their intersection
                                     planes do not carry the winning primitive) and with PT_DIRECT_LIGHT (the textured form of
                                     the direct kernels is a later change).  PT_FAKE_SHADER ignores the flag. */
+    PT_DIRECT_SKY    = 1u << 15, /* opt-in, with PT_DIRECT_LIGHT: the environment map, while one is set, is one more light
+                                    element behind the lamps' -- the sampling bounce picks it with probability 1/2 (1 in a
+                                    scene without lamps), draws a direction from a table built over the map's texels and the
+                                    final ray scores the map's radiance where it leaves the scene ("direct lighting samples the
+                                    environment map" below).  Without a map, or with a map that yields
+                                    no element (no texel with a finite luminance > 0), the session is the PT_DIRECT_LIGHT
+                                    session bit for bit.  The light count, and with it the number of bounces (pt_stats, live[D],
+                                    pt_trace_bounce), follows pt_set_environment.  The sampler ignores the cosine and
+                                    visibility: on a featureless sky it is noisier than the ordinary bounce, under a small
+                                    bright region far quieter.  Refused by pt_init (PT_ERR_INVALID) without PT_DIRECT_LIGHT;
+                                    PT_FAKE_SHADER ignores both. */
     PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after
@@ -447,7 +458,7 @@ int pt_glossy_alpha2(const float *exponents, int count, float *alpha2);
  * Final ray (bounce D): its target is the primitive of element e, recomputed from the same engine's first draw.  It scores
  *   colour *= material.color * emittance when t > 0 and the winning primitive (strict less, lowest index on ties) is the
  *   target; everything else -- another primitive in front, another emitter, a miss, with or without an environment map -- ends
- *   with colour 0.  Nothing draws at bounce D; the camera's engine slot stays D.
+ *   with colour 0 (PT_DIRECT_SKY, below, adds the sky's element and its rule).  Nothing draws at bounce D; the camera's engine slot stays D.
  * pt_light_elements: host only (no GPU), pt_init's own function.  Returns E, or the required count when `capacity` is too
  * small, in which case nothing is written; out may be NULL with capacity 0.  PT_ERR_INVALID: a negative count, a null array
  * with a positive count, an emitting candidate's materialid outside the table. */
@@ -458,6 +469,37 @@ typedef struct pt_light_element {
 } pt_light_element;
 int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials,
                       pt_light_element *out, int capacity);
+
+/* ---- direct lighting samples the environment map (PT_DIRECT_SKY, with PT_DIRECT_LIGHT) ------------------------------------------
+ * The device side is binary32, one rounding per operation in the order written, no FMA; the host tables are binary64 on the
+ * binary32 texels, every stored value rounded once; tests/sky_model.py is the numpy form and the device equals it bit for bit.
+ * Sampling tables, built on the host by pt_set_environment in a flagged session from the 6 n n texels.  Row r = face * n + j
+ * (6 n rows), texel k = r * n + i.
+ *   lum_k = (0.2126 r + 0.7152 g) + 0.0722 b of the texel, 0 where that is not a finite number > 0.
+ *   J_k = 1 / (q sqrt(q)), q = (1 + ac ac) + bc bc, at the texel centre ac = (2 i + 1) / n - 1, bc likewise from j.
+ *   m_k = lum_k J_k;  T = the sum of m_k in index order; T not a finite number > 0: there is no sky element.
+ *   rows:    M_r = (sum over i of m_k, in order) + T / (16 * 6 n);  rowcdf[r] = (float)(running sum of M / its last value), the
+ *            last forced to 1.0f;  rowinv[r] = (float)(1 / ((double)rowcdf[r] - (double)rowcdf[r - 1])), rowcdf[-1] = 0: the
+ *            probability the ROUNDED table selects with.
+ *   columns: within row r, c_k = m_k + (the row's sum) / (16 n), c_k = 1 when the row's sum is 0;  colcdf and colinv built
+ *            from c as rowcdf and rowinv are from M, row by row.  The two 1/17 mixtures keep every row and column reachable.
+ * Light table: with E lamp elements and a sky element a lamp's cdf is halved and its inv_p doubled; element E is the sky -- kind
+ *   2, geom -1, cdf 1.0f, inv_p 2 (1 when E = 0) -- with K = (float)(4 / (pi n n)), s = (float)(2.0 / n) and n.  Up to 1024 lamp
+ *   elements plus the sky.  pt_light_elements is unchanged.
+ * Sampling at bounce D - 1: u0, u1, u2 as above; e = the smallest index with u0 < cdf[e].  A lamp proceeds as above.  The sky
+ *   draws u3, u4:  r = the smallest index with u1 < rowcdf[r] (6 n - 1 if none);  i = the smallest with u2 < colcdf[r n + i]
+ *   (n - 1 if none);  face = r / n, j = r % n, axis = face >> 1;  a = ((float)i + u3) * s - 1, b = ((float)j + u4) * s - 1;
+ *   v[axis] = (face & 1) ? -1 : 1, the other two axes in x, y, z order get a, b (pt_environment_texel's mapping inverted);
+ *   l2 = (1 + a a) + b b;  rl = 1 / sqrt(l2);  dir = v * rl;  Jd = (rl * rl) * rl;  cs = dot(n, dir).  cs > 0 false (NaN
+ *   included): the path ends with colour 0.  Otherwise w = ((cs * Jd) * (rowinv[r] * colinv[r n + i])) * (K * inv_p[e]),
+ *   colour = (colour * material.color) * w, origin P, direction dir, one more bounce.  No inside test, no cl.
+ * Final ray (bounce D): the target of a sky-aimed ray is -1.  It scores when t > 0 is false: colour = the session's ordinary
+ *   miss lookup on the direction as traced (whichever texel that reads) times colour.  Any hit ends it with 0; a lamp-aimed ray
+ *   that misses still ends with 0.  Nothing draws at bounce D.
+ * pt_sky_table: host only (no GPU), pt_set_environment's own function.  1: the map yields a sky element and row (6 n pairs
+ * {cdf, inv}) and col (6 n n pairs, row by row) are written -- each may be NULL; 0: no element (n == 0 or texels == NULL
+ * included), nothing written.  PT_ERR_INVALID: n outside [0, 1024], texels == NULL with n > 0. */
+int pt_sky_table(const float *texels, int n, float *row, float *col);
 
 /* pathtrace (pathtrace.cu:284-393): one iteration `iter` (1-based; RNG key and
  * tonemap divisor).  pbo_rgba: optional DEVICE pointer to W*H RGBA8 (the mapped
@@ -752,6 +794,22 @@ int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_materia
 int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
                                   int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
                                   const uint8_t *outside, const int32_t *hit_geom, int n);
+/* pt_probe_sky_sample: PT_DIRECT_SKY's branch of the sampler on the device through the function the kernels call, one lane per
+ * (normal, engine seed) record (normals: count x 3 floats; seeded like pt_probe_hemisphere), on a table whose only element is
+ * the sky of the map (texels, n): the direction (count x 3), the weight and the texel r * n + i drawn.  weight = 0 and dir = 0
+ * where the path would end (cs > 0 false; the texel is still reported).  A map without an element (n == 0 included): weight 0,
+ * dir 0, texel -1, nothing launched.  PT_ERR_INVALID: n outside [0, 1024], texels == NULL with n > 0, count < 0 or above 2^26,
+ * a null array with count > 0.
+ * pt_probe_shade_scatter_direct_sky: pt_probe_shade_scatter_direct on the light table of a PT_DIRECT_SKY session under the map
+ * (texels, env_n; env_n == 0: no map, pt_probe_shade_scatter_direct itself).  At depth == trace_depth a ray aimed at the sky scores
+ * the map where isects[i].t > 0 is false and ends with 0 on any hit.  (As in pt_probe_shade_scatter_direct a miss at an earlier
+ * depth ends with colour 0: the pipelines' miss exit is pt_probe_environment's.)  Refusals as pt_probe_shade_scatter_direct's,
+ * and env_n outside [0, 1024] or texels == NULL with env_n > 0. */
+int pt_probe_sky_sample(const float *texels, int n, const float *normals, const uint32_t *seeds, int count, float *dir, float *weight,
+                        int32_t *texel);
+int pt_probe_shade_scatter_direct_sky(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                      int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                      const uint8_t *outside, const int32_t *hit_geom, int n, const float *texels, int env_n);
 /* pt_probe_tri_form: the every-triangle loop's first stage on the device, through the kernel's own code (csrc/pt_k_trisweep.hpp:
  * tri_ray_operands, tri_group_form), for ONE mesh of `count` triangles (records and frame as pt_tri_records makes them) and n rays
  * (origins, directions: n x 3 floats each; rays with |origin|_1 > origin_bound are `wild` as in the kernels).  Per ray (each output

@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     set_environment, get_environment, gradient_cubemap, environment_texel, probe_environment,
     glossy_alpha2, probe_glossy_lobe, probe_shade_scatter_glossy,
     PT_DIRECT_LIGHT, LIGHT_DT, light_elements, probe_direct_sample, probe_shade_scatter_direct,
+    PT_DIRECT_SKY, sun_on_cubemap, sky_table, probe_sky_sample, probe_shade_scatter_direct_sky,
     PT_TEXTURES, set_texture, get_texture, checker_cubemap, texture_texel, probe_texture, probe_shade_scatter_textured,
     set_bump_map, get_bump_map, studs_bumpmap, bump_normal, probe_bump_normal, probe_shade_scatter_bumped,
 )

@@ -41,6 +41,7 @@ PT_SHARED_IMAGE = 512
 PT_LOOKAHEAD = 2048         # pt_trace traces ahead of its caller (include/ptmi355.h)
 PT_GLOSSY = 4096            # SPECEX gives mirrors and dielectrics a GGX lobe (include/ptmi355.h)
 PT_DIRECT_LIGHT = 8192      # the last bounce aims a final ray at a sampled light (include/ptmi355.h)
+PT_DIRECT_SKY = 32768       # ... and the environment map is one more light element (with PT_DIRECT_LIGHT; include/ptmi355.h)
 PT_TEXTURES = 16384         # a cube texture per material tints spheres and cubes (include/ptmi355.h)
 BVH_NODE_WORDS = 16
 
@@ -191,6 +192,10 @@ def library():
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
             L.pt_probe_shade_scatter_direct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.pt_sky_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_probe_sky_sample.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_probe_shade_scatter_direct_sky.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
             L.pt_set_texture.argtypes = [C.c_int, C.c_void_p, C.c_int]
             L.pt_get_texture.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
             L.pt_texture_texel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -351,6 +356,73 @@ def gradient_cubemap(n, zenith, horizon, ground):
         up, down = np.maximum(y, 0.0)[..., None], np.maximum(-y, 0.0)[..., None]
         out[face] = (h + (z - h) * up + (g - h) * down).astype(np.float32)
     return out
+
+
+def sun_on_cubemap(texels, direction, cos_half_angle, rgb):
+    """A copy of the cube map `texels` ([6, n, n, 3]) in which every texel whose centre direction c has dot(c, direction / |direction|)
+    >= cos_half_angle is replaced by `rgb`: a sun for PT_DIRECT_SKY to find.  Host arithmetic in float64, the centres as in
+    gradient_cubemap; the texels are input to the specification, not part of it."""
+    t, n = _cube_texels(texels)
+    out = np.array(t, dtype=np.float32, copy=True).reshape(6, n, n, 3)
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    d = d / np.sqrt((d * d).sum())
+    col = np.asarray(rgb, dtype=np.float64).reshape(3).astype(np.float32)
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n * 2.0 - 1.0
+    b, a = np.meshgrid(c, c, indexing="ij")
+    for face in range(6):
+        axis, major = face >> 1, (-1.0 if face & 1 else 1.0)
+        comp = [None, None, None]
+        comp[axis] = np.full_like(a, major)
+        rest = [k for k in range(3) if k != axis]
+        comp[rest[0]], comp[rest[1]] = a, b
+        ln = np.sqrt(comp[0] * comp[0] + comp[1] * comp[1] + comp[2] * comp[2])
+        cosine = (comp[0] * d[0] + comp[1] * d[1] + comp[2] * d[2]) / ln
+        out[face][cosine >= float(cos_half_angle)] = col
+    return out
+
+
+def sky_table(texels):
+    """Host-only: the sampling tables a PT_DIRECT_SKY session builds from a cube map (include/ptmi355.h: pt_sky_table): (row [6 n, 2],
+    col [6 n, n, 2]) float32 pairs {cdf, inv}, or None when the map yields no sky element."""
+    t, n = (None, 0) if texels is None else _cube_texels(texels)
+    row = np.zeros((6 * n, 2), dtype=np.float32)
+    col = np.zeros((6 * n, n, 2), dtype=np.float32)
+    if _chk(library().pt_sky_table(_p(t), n, _p(row), _p(col))) == 0:
+        return None
+    return row, col
+
+
+def probe_sky_sample(texels, normals, seeds):
+    """PT_DIRECT_SKY's branch of the sampler on the device for (normal, engine seed) pairs on the table of the cube map `texels`
+    alone (include/ptmi355.h: pt_probe_sky_sample): (dir [n, 3] float32, weight [n] float32, texel [n] int32); weight 0 and dir
+    0 where the path would end, texel -1 where the map yields no element."""
+    t, n = (None, 0) if texels is None else _cube_texels(texels)
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    if len(nr) != len(sd):
+        raise PtError("probe_sky_sample: %d normals, %d seeds" % (len(nr), len(sd)))
+    d = np.zeros((len(sd), 3), dtype=np.float32)
+    w = np.zeros(len(sd), dtype=np.float32)
+    k = np.zeros(len(sd), dtype=np.int32)
+    _chk(library().pt_probe_sky_sample(_p(t), n, _p(nr), _p(sd), len(sd), _p(d), _p(w), _p(k)))
+    return d, w, k
+
+
+def probe_shade_scatter_direct_sky(iter, depth, trace_depth, geoms, materials, paths, isects, texels, outside=None, hit_geom=None):
+    """probe_shade_scatter_direct on the light table of a PT_DIRECT_SKY session under the cube map `texels` (None: no map)
+    (include/ptmi355.h: pt_probe_shade_scatter_direct_sky)."""
+    g = np.ascontiguousarray(geoms, dtype=GEOM_DT).reshape(-1)
+    m = np.ascontiguousarray(materials, dtype=MATERIAL_DT).reshape(-1)
+    p = np.array(paths, dtype=PATH_DT, copy=True, order="C").reshape(-1)
+    x = np.ascontiguousarray(isects, dtype=ISECT_DT).reshape(-1)
+    o = None if outside is None else np.ascontiguousarray(outside, dtype=np.uint8).reshape(-1)
+    h = None if hit_geom is None else np.ascontiguousarray(hit_geom, dtype=np.int32).reshape(-1)
+    t, n = (None, 0) if texels is None else _cube_texels(texels)
+    if len(x) != len(p) or (o is not None and len(o) != len(p)) or (h is not None and len(h) != len(p)):
+        raise PtError("probe_shade_scatter_direct_sky: %d paths, %d intersections" % (len(p), len(x)))
+    _chk(library().pt_probe_shade_scatter_direct_sky(int(iter), int(depth), int(trace_depth), _p(g), len(g), _p(m), len(m), _p(p), _p(x),
+                                                     _p(o), _p(h), len(p), _p(t), n))
+    return p
 
 
 def environment_texel(dirs, n):

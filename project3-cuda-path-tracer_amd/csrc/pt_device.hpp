@@ -628,6 +628,7 @@ template <typename P> PTD f3 texture_bump_mcol(const float *mats, int matId, uin
 constexpr int LIGHT_WORDS = 56;
 constexpr int L_KIND = 0, L_GEOM = 1, L_AREA = 2, L_CDF = 3, L_INVP = 4, L_DETPI = 5, L_C0 = 6, L_EA = 9, L_EB = 12, L_NRM = 15,
               L_INV = 18, L_FWD = 30, L_INVT = 42;
+constexpr int L_SKY_K = 5, L_SKY_S = 6, L_SKY_N = 7;          // the sky's record (kind 2, PT_DIRECT_SKY: sky_sample below)
 
 // the smallest e with u0 < cdf[e]; count - 1 if none (cdf is non-decreasing and ends with 1.0f, u0 < 1)
 PTD int light_pick(const float *lights, int count, float u0) {
@@ -642,7 +643,50 @@ PTD int light_pick(const float *lights, int count, float u0) {
 // steps 1 (the draws) to 7 of section 6.18 at the point P with normal n: the engine's first three draws pick the element and
 // the point y on it.  true: `dir` = the unit direction to y and `w` = the sample's weight cos cos A inv_p / (pi r^2); false
 // (y is not in front of P, or P not in front of the element): dir = 0, w = 0.  elem = the element picked either way.
-PTD bool direct_sample(const float *lights, int count, f3 P, f3 n, uint32_t &rng, f3 &dir, float &w, int &elem) {
+// PT_DIRECT_SKY: the element of kind 2, the last of the table, is the environment map -- word 5 K =
+// (float)(4 / (pi n n)), word 6 s = (float)(2.0 / n), word 7 n; behind the `count` records sit the row table (6 n pairs {cdf,
+// inv}) and the column table (6 n n pairs, row by row).  Two more draws place the direction inside the texel picked by u1
+// (row) and u2 (column); there is no point y, no cl and no inside test.  `sky_texel` (the probe): the texel drawn.  The two
+// searches are divergent loads: only the lanes that picked the sky come here.
+PTD int cdf_pick(const float *pairs, int count, float u) {
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u < pairs[2 * (size_t)mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+PTD bool sky_sample(const float *lights, int count, const float *L, f3 n, float u1, float u2, uint32_t &rng, f3 &dir, float &w, int *sky_texel) {
+    const int nn = __float_as_int(L[L_SKY_N]);
+    const float *rows = lights + (size_t)count * LIGHT_WORDS;
+    const int r = cdf_pick(rows, 6 * nn, u1);
+    const float *cols = rows + 2 * (size_t)(6 * nn) + 2 * (size_t)r * (size_t)nn;
+    const int i = cdf_pick(cols, nn, u2);
+    if (sky_texel) *sky_texel = r * nn + i;
+    const float u3 = u01(rng);
+    const float u4 = u01(rng);
+    const int face = r / nn, j = r - face * nn, axis = face >> 1;
+    const float s = L[L_SKY_S];
+    const float a = ((float)i + u3) * s - 1.0f;
+    const float b = ((float)j + u4) * s - 1.0f;
+    const float sg = (face & 1) ? -1.0f : 1.0f;
+    const f3 v = axis == 0 ? mk(sg, a, b) : (axis == 1 ? mk(a, sg, b) : mk(a, b, sg));
+    const float l2 = (1.0f + a * a) + b * b;
+    const float rl = 1.0f / __builtin_sqrtf(l2);
+    const f3 d = scale(v, rl);
+    const float Jd = (rl * rl) * rl;
+    const float cs = dot(n, d);
+    if (!(cs > 0.0f)) {                                               // NaN: false
+        dir = mk(0.0f, 0.0f, 0.0f);
+        w = 0.0f;
+        return false;
+    }
+    dir = d;
+    w = ((cs * Jd) * (rows[2 * (size_t)r + 1] * cols[2 * (size_t)i + 1])) * (L[L_SKY_K] * L[L_INVP]);
+    return true;
+}
+
+PTD bool direct_sample(const float *lights, int count, f3 P, f3 n, uint32_t &rng, f3 &dir, float &w, int &elem, int *sky_texel = nullptr) {
     const float TWO_PI = 6.2831853071795864769252867665590057683943f;
     const float PI = 3.14159265358979323846264338327950288f;
     const float u0 = u01(rng);
@@ -651,7 +695,9 @@ PTD bool direct_sample(const float *lights, int count, f3 P, f3 n, uint32_t &rng
     const int e = light_pick(lights, count, u0);
     elem = e;
     const float *L = lights + (size_t)e * LIGHT_WORDS;
-    const bool sphere = __float_as_int(L[L_KIND]) == 0;
+    const int kind = __float_as_int(L[L_KIND]);
+    if (kind == 2) return sky_sample(lights, count, L, n, u1, u2, rng, dir, w, sky_texel);
+    const bool sphere = kind == 0;
     f3 y, nl;
     float A;
     if (sphere) {
@@ -694,6 +740,7 @@ PTD bool direct_sample(const float *lights, int count, f3 P, f3 n, uint32_t &rng
 }
 
 // the primitive the final ray of (iter, pixel) was aimed at: the first draw of the engine of the bounce that aimed it
+// (-1: the sky, PT_DIRECT_SKY -- its record says so)
 PTD int direct_target(const float *lights, int count, int iter, int pixel, int depth) {
     uint32_t rng = seeded_engine(iter, pixel, depth);
     const int e = light_pick(lights, count, u01(rng));

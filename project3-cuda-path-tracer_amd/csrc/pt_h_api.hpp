@@ -167,6 +167,8 @@ static int init_impl(const pt_scene_desc *d) {
     // PT_DIRECT_LIGHT: the pipelines that keep intersection planes do not carry the winning primitive
     // (the two-kernel sort is refused further down, once the form of the sort is known); PT_FAKE_SHADER ignores the flag
     std::vector<pt_light_element> light_el;
+    if ((d->flags & PT_DIRECT_SKY) && !(d->flags & PT_DIRECT_LIGHT) && !(d->flags & PT_FAKE_SHADER))
+        return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_SKY needs PT_DIRECT_LIGHT (the sky is one more light element of its sampler)");
     if ((d->flags & PT_DIRECT_LIGHT) && !(d->flags & PT_FAKE_SHADER)) {
         if (d->flags & PT_UNFUSED)
             return fail(PT_ERR_INVALID, "pt_init: PT_DIRECT_LIGHT cannot be combined with PT_UNFUSED (its intersection planes do not carry the winning primitive)");
@@ -418,6 +420,7 @@ static int init_impl(const pt_scene_desc *d) {
         HIPCHK(hipMalloc((void **)&R.d_lights, lrec.size() * 4));
         HIPCHK(hipMemcpy(R.d_lights, lrec.data(), lrec.size() * 4, hipMemcpyHostToDevice));
         R.nlights = (int)light_el.size();
+        if (sky_session()) R.lamp_rec = lrec;                  // pt_set_environment rebuilds the table from the lamps' records
     }
     // pools, intersections, final colours, image, control
     const size_t capz = R.cap;
@@ -454,7 +457,7 @@ static int init_impl(const pt_scene_desc *d) {
     R.max_tiles = (R.cap + TILE - 1) / TILE;
     // only the election buckets of the bounces this scene can run are cleared per batch
     R.ctl_bytes = offsetof(Control, bucket) - offsetof(Control, stamp) +
-                  (size_t)session_bounces() * sizeof(((Control *)nullptr)->bucket[0]);
+                  (size_t)session_bounces_max(R.trace_depth) * sizeof(((Control *)nullptr)->bucket[0]);
     HIPCHK(hipMalloc((void **)&R.ctl, sizeof(Control)));
     HIPCHK(hipMemsetAsync(R.ctl, 0, sizeof(Control), R.stream));      // incl. Control::ticket, which no batch clears
     HIPCHK(hipMalloc((void **)&R.persist, sizeof(Persist)));
@@ -495,7 +498,8 @@ static int init_impl(const pt_scene_desc *d) {
             return PT_OK;
         };
         int rc = size_for(std::integral_constant<int, 0>{});
-        if (rc == PT_OK && R.nlights > 0) rc = size_for(std::integral_constant<int, SH_DIRECT>{});
+        // (a PT_DIRECT_SKY session gains its light when a map arrives: pt_set_environment comes after this)
+        if (rc == PT_OK && (R.nlights > 0 || sky_session())) rc = size_for(std::integral_constant<int, SH_DIRECT>{});
         // (a PT_TEXTURES session launches the TEX forms whenever a texture is set: pt_set_texture comes after this)
         if (rc == PT_OK && (R.flags & PT_TEXTURES) && !(R.flags & PT_FAKE_SHADER)) rc = size_for(std::integral_constant<int, SH_TEX>{});
         if (rc != PT_OK) return rc;
@@ -628,7 +632,7 @@ int pt_set_camera(const pt_camera *camera, int trace_depth) {
     if (trace_depth != R.trace_depth) {
         // the per-batch clear covers the election buckets of the bounces that can run
         R.ctl_bytes = offsetof(Control, bucket) - offsetof(Control, stamp) +
-                      (size_t)(trace_depth + (R.nlights > 0 ? 1 : 0)) * sizeof(((Control *)nullptr)->bucket[0]);
+                      (size_t)session_bounces_max(trace_depth) * sizeof(((Control *)nullptr)->bucket[0]);
     }
     const bool moved = memcmp(&R.cam, camera, sizeof R.cam) != 0;
     R.cam = *camera;
@@ -668,6 +672,30 @@ int pt_set_lens(float lens_radius, float focal_distance) {
 // Environment lighting (include/ptmi355.h).  The map is scene state the launches in flight read:
 // the host waits for everything the session has enqueued -- windows traced ahead are void, as after a camera change --
 // before the old texels are released.  The accumulation buffer stays as it is.
+// PT_DIRECT_SKY: the device's light table of a flagged session -- the lamps' records alone (texels ==
+// nullptr, or a map that yields no element), or the lamps at half their probability, the sky's record and its two tables.
+// The caller has synchronised the session: nothing in flight reads the old table.  The light count, and with it the number
+// of bounces a batch runs, follows.
+static int upload_sky_lights(const float *texels, int n) {
+    std::vector<float> rows, cols, rec;
+    int count = (int)(R.lamp_rec.size() / (size_t)ptlight::RECORD_WORDS);
+    const std::vector<float> *src = &R.lamp_rec;
+    if (texels && n > 0 && ptlight::sky_table(texels, n, rows, cols)) {
+        count = ptlight::sky_records(R.lamp_rec, n, rows, cols, rec);
+        src = &rec;
+    }
+    if (R.d_lights) { (void)hipFree(R.d_lights); R.d_lights = nullptr; }
+    R.nlights = 0;
+    if (count == 0) return PT_OK;
+    if (hipMalloc((void **)&R.d_lights, src->size() * 4) != hipSuccess) {
+        (void)hipGetLastError(); R.d_lights = nullptr;
+        return fail(PT_ERR_NOMEM, "pt_set_environment: %zu bytes of device memory for the light table", src->size() * 4);
+    }
+    HIPCHK(hipMemcpy(R.d_lights, src->data(), src->size() * 4, hipMemcpyHostToDevice));
+    R.nlights = count;
+    return PT_OK;
+}
+
 int pt_set_environment(const float *texels, int n) {
     if (!R.live) return fail(PT_ERR_INVALID, "pt_set_environment: not initialised");
     if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_environment: n = %d outside [0, 1024]", n);
@@ -686,6 +714,10 @@ int pt_set_environment(const float *texels, int n) {
     R.env_n = 0;
     if (R.d_env) { (void)hipFree(R.d_env); R.d_env = nullptr; }
     R.env_keep.clear();
+    if (sky_session()) {                                        // the element disappears with the map
+        const int rc2 = upload_sky_lights(nullptr, 0);
+        if (rc2) return rc2;
+    }
     if (n == 0) return PT_OK;
     const size_t count = (size_t)6 * (size_t)n * (size_t)n;
     std::vector<float> quad(count * 4);
@@ -699,6 +731,7 @@ int pt_set_environment(const float *texels, int n) {
     HIPCHK(hipMemcpy(R.d_env, quad.data(), count * 16, hipMemcpyHostToDevice));
     R.env_keep.assign(texels, texels + count * 3);
     R.env_n = n;
+    if (sky_session()) return upload_sky_lights(texels, n);
     return PT_OK;
 }
 
@@ -910,7 +943,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex + R.nbump == 0 && R.epi_enabled &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && !sky_session() && R.ntex + R.nbump == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 
@@ -1464,6 +1497,18 @@ int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *ma
     if (ne < 0) return fail(PT_ERR_INVALID, "pt_light_elements: a cube or sphere names a material outside [0, %d)", num_materials);
     if (ne <= capacity && ne > 0) memcpy(out, el.data(), (size_t)ne * sizeof(pt_light_element));
     return ne;
+}
+
+// PT_DIRECT_SKY's sampling tables (include/ptmi355.h; pt_lights.hpp): what pt_set_environment builds in a flagged session, host only
+int pt_sky_table(const float *texels, int n, float *row, float *col) {
+    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_sky_table: n = %d outside [0, 1024]", n);
+    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_sky_table: null texels with n = %d", n);
+    if (!texels || n == 0) return 0;
+    std::vector<float> rows, cols;
+    if (!ptlight::sky_table(texels, n, rows, cols)) return 0;
+    if (row) memcpy(row, rows.data(), rows.size() * 4);
+    if (col) memcpy(col, cols.data(), cols.size() * 4);
+    return 1;
 }
 
 int pt_get_stats(pt_stats *stats) {

@@ -81,6 +81,9 @@ struct Renderer {
     // scene has a cube or sphere that emits: such a session runs trace_depth + 1 bounces (session_bounces), a kernel each.
     float *d_lights = nullptr;
     int nlights = 0;
+    // PT_DIRECT_SKY: the lamps' records as pt_init made them.  In a flagged session nlights CHANGES
+    // when a map arrives or goes (pt_set_environment: + 1 for the sky's element, and the two tables behind the records)
+    std::vector<float> lamp_rec;
     // PT_TEXTURES: at most one cube texture per material.  tex_keep[m] / tex_n[m]: as the caller gave
     // them (pt_get_texture); d_tex: every texture's texels {r, g, b, 0} back to back, d_tex_tab: per material {offset in texels,
     // n}, both rebuilt by pt_set_texture.  ntex = textures set; > 0: the session launches the TEX forms of k_bounce, a kernel
@@ -357,6 +360,10 @@ int ensure_scratch(size_t bytes) {
 
 // bounces a batch of this session runs: traceDepth, and the final ray of PT_DIRECT_LIGHT behind them
 int session_bounces(void) { return R.trace_depth + (R.nlights > 0 ? 1 : 0); }
+// a session whose light count follows the environment map: PT_DIRECT_SKY (with PT_DIRECT_LIGHT, pt_init sees to that)
+bool sky_session(void) { return (R.flags & PT_DIRECT_SKY) && (R.flags & PT_DIRECT_LIGHT) && !(R.flags & PT_FAKE_SHADER); }
+// ... and the most bounces a batch of depth `trace_depth` can run in this session, whatever map comes later
+int session_bounces_max(int trace_depth) { return trace_depth + ((R.nlights > 0 || sky_session()) ? 1 : 0); }
 
 RangeDir tile_dir(int depth) {
     const uint32_t W = (uint32_t)R.grid * WAVES * (uint32_t)(R.sort_keys > 0 ? R.sort_runs : 1);     // runs of tiles

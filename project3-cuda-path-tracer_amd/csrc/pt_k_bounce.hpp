@@ -201,7 +201,8 @@ __device__ __forceinline__ bool mesh_root_candidate(const SceneDev &sc, f3 ro, f
 // DIRECT: bounces D - 1 and D of a PT_DIRECT_LIGHT session with traceDepth D (k_bounce only).  At
 // D - 1 the last-bounce exit of a diffuse hit aims a final ray at a sampled light (ptd::shade_scatter<.., true>); at D every
 // path ends: with the emitter's colour when its nearest hit is the primitive `geom` it was aimed at, with 0 otherwise -- a
-// miss included, whatever the environment.  The table's pointer and size are read where they are used, like the map's.
+// miss included, whatever the environment -- except, in a PT_DIRECT_SKY session (section 6.24), a ray aimed at the sky, which
+// scores on a miss and on nothing else.  The table's pointer and size are read where they are used, like the map's.
 // TEX: a PT_TEXTURES session while a texture is set (k_bounce only) -- a hit on a sphere or cube whose
 // material has a cube texture shades with material.color * texel (ptd::texture_mcol, shade_scatter<.., TEX>).  The gather runs on
 // those lanes only; the two pointers are read from the argument block where a lane hit, like the map's.
@@ -251,7 +252,13 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
             const int nlights = c.kargs ? karg_field<int>(offsetof(BounceArgs, nlights)) : a.nlights;
             if (depth == a.trace_depth) {                      // the final ray (wave-uniform: the whole launch)
                 const int target = ptd::direct_target(lights, nlights, c.iter0 + (int)tr.smp, tr.pixel, depth - 1);
-                if (t > 0.0f && geom == target) {
+                // PT_DIRECT_SKY: a ray aimed at the sky (target -1) scores when it leaves the scene --
+                // the session's ordinary lookup on the direction as traced, through end_path -- and ends with 0 on any hit.
+                // Only where the session has a map: a sky element never exists without one.
+                if (ENV && target < 0) {
+                    if (!(t > 0.0f)) missed = true;
+                    else ps.c = ptd::mk(0.0f, 0.0f, 0.0f);
+                } else if (t > 0.0f && geom == target) {
                     const float *m = c.acc.mats + mat * ptd::MAT_WORDS;
                     ps.c = ptd::mul(ps.c, ptd::scale(ptd::mk(m[0], m[1], m[2]), m[9]));
                 } else {

@@ -101,4 +101,89 @@ inline void records(const pt_geom *geoms, const std::vector<pt_light_element> &e
     }
 }
 
+// ---- PT_DIRECT_SKY: the sampling tables of an environment map -----------------------------------
+// Binary64 on the binary32 texels (6 n n RGB triples, pt_set_environment's layout), in the order written, every stored value
+// rounded once; tests/sky_model.py restates it in numpy.  Row r = face * n + j, texel k = r * n + i.  `rows`: 6 n pairs
+// {cdf, inv}, `cols`: 6 n n pairs, each row's own cdf.  false: the map yields no sky element (nothing is written then).
+inline bool sky_table(const float *texels, int n, std::vector<float> &rows, std::vector<float> &cols) {
+    if (!texels || n < 1) return false;
+    const size_t nn = (size_t)n, R = 6 * nn, count = R * nn;
+    std::vector<double> m(count), rowsum(R);
+    std::vector<double> jac(nn * nn);
+    for (size_t j = 0; j < nn; ++j)
+        for (size_t i = 0; i < nn; ++i) {
+            const double ac = (double)(2 * i + 1) / (double)n - 1.0, bc = (double)(2 * j + 1) / (double)n - 1.0;
+            const double q = (1.0 + ac * ac) + bc * bc;
+            jac[j * nn + i] = 1.0 / (q * std::sqrt(q));
+        }
+    double T = 0.0;
+    for (size_t r = 0; r < R; ++r) {
+        const size_t j = r % nn;
+        double s = 0.0;
+        for (size_t i = 0; i < nn; ++i) {
+            const size_t k = r * nn + i;
+            double lum = (0.2126 * (double)texels[3 * k] + 0.7152 * (double)texels[3 * k + 1]) + 0.0722 * (double)texels[3 * k + 2];
+            if (!(std::isfinite(lum) && lum > 0.0)) lum = 0.0;
+            m[k] = lum * jac[j * nn + i];
+            s += m[k];
+            T += m[k];
+        }
+        rowsum[r] = s;
+    }
+    if (!(std::isfinite(T) && T > 0.0)) return false;
+    rows.assign(2 * R, 0.0f);
+    cols.assign(2 * count, 0.0f);
+    // a running sum over its total as binary32, the last forced to 1.0f; inv = the reciprocal of the probability the ROUNDED
+    // table selects with
+    auto emit = [](const double *mass, size_t len, float *out) {
+        double total = 0.0;
+        for (size_t k = 0; k < len; ++k) total += mass[k];
+        double run = 0.0;
+        for (size_t k = 0; k < len; ++k) {
+            run += mass[k];
+            out[2 * k] = (float)(run / total);
+        }
+        out[2 * (len - 1)] = 1.0f;
+        double prev = 0.0;
+        for (size_t k = 0; k < len; ++k) {
+            out[2 * k + 1] = (float)(1.0 / ((double)out[2 * k] - prev));
+            prev = (double)out[2 * k];
+        }
+    };
+    std::vector<double> mass(R > nn ? R : nn);
+    const double row_mix = T / (double)(16 * R);
+    for (size_t r = 0; r < R; ++r) mass[r] = rowsum[r] + row_mix;
+    emit(mass.data(), R, rows.data());
+    for (size_t r = 0; r < R; ++r) {
+        const double mix = rowsum[r] / (double)(16 * nn);
+        for (size_t i = 0; i < nn; ++i) mass[i] = rowsum[r] == 0.0 ? 1.0 : m[r * nn + i] + mix;
+        emit(mass.data(), nn, cols.data() + 2 * r * nn);
+    }
+    return true;
+}
+
+// The device's light table of a PT_DIRECT_SKY session: the lamps' records `lamps` (ptlight::records, E = lamps.size() /
+// RECORD_WORDS) with cdf halved and inv_p doubled (exact), the sky's record -- kind 2, geom -1, cdf 1, inv_p 2 (1 when it is the
+// only element), K = (float)(4 / (pi n n)) in word 5, s = (float)(2.0 / n) in word 6, n in word 7 -- and behind the E + 1
+// records the row table and the column table.  Returns the element count, E + 1.
+inline int sky_records(const std::vector<float> &lamps, int n, const std::vector<float> &rows, const std::vector<float> &cols, std::vector<float> &rec) {
+    const size_t E = lamps.size() / (size_t)RECORD_WORDS;
+    rec.assign((E + 1) * (size_t)RECORD_WORDS + rows.size() + cols.size(), 0.0f);
+    if (!lamps.empty()) memcpy(rec.data(), lamps.data(), lamps.size() * 4);
+    for (size_t e = 0; e < E; ++e) {
+        rec[e * RECORD_WORDS + 3] *= 0.5f;
+        rec[e * RECORD_WORDS + 4] *= 2.0f;
+    }
+    float *r = rec.data() + E * (size_t)RECORD_WORDS;
+    const int32_t kind = 2, geom = -1, nn = n;
+    memcpy(&r[0], &kind, 4); memcpy(&r[1], &geom, 4);
+    r[3] = 1.0f; r[4] = E > 0 ? 2.0f : 1.0f;
+    r[5] = (float)(4.0 / (PI * (double)n * (double)n));
+    r[6] = (float)(2.0 / (double)n);
+    memcpy(&r[7], &nn, 4);
+    memcpy(r + RECORD_WORDS, rows.data(), rows.size() * 4);
+    memcpy(r + RECORD_WORDS + rows.size(), cols.data(), cols.size() * 4);
+    return (int)E + 1;
+}
+
 }  // namespace ptlight

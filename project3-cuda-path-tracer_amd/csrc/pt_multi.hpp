@@ -1099,6 +1099,17 @@ int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt
     return one::pt_probe_shade_scatter_direct(iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
                                               hit_geom, n);
 }
+int pt_probe_shade_scatter_direct_sky(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                      int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                      const uint8_t *outside, const int32_t *hit_geom, int n, const float *texels, int env_n) {
+    return one::pt_probe_shade_scatter_direct_sky(iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
+                                                  hit_geom, n, texels, env_n);
+}
+int pt_probe_sky_sample(const float *texels, int n, const float *normals, const uint32_t *seeds, int count, float *dir, float *weight,
+                        int32_t *texel) {
+    return one::pt_probe_sky_sample(texels, n, normals, seeds, count, dir, weight, texel);
+}
+int pt_sky_table(const float *texels, int n, float *row, float *col) { return one::pt_sky_table(texels, n, row, col); }
 int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const float *alpha2, int n, float *dirs) {
     return one::pt_probe_glossy_lobe(normals, seeds, alpha2, n, dirs);
 }

@@ -225,13 +225,32 @@ __global__ __launch_bounds__(64) void k_probe_direct_sample(const float *__restr
     element[i] = e;
 }
 
+// PT_DIRECT_SKY's branch of the sampler through ptd::direct_sample on a table whose only element is the
+// sky: one lane per (normal, engine seed) record, P = 0 (the sky's branch does not read it)
+__global__ __launch_bounds__(64) void k_probe_sky_sample(const float *__restrict__ lights, int nlights, const float *__restrict__ nrm,
+                                                          const uint32_t *__restrict__ seeds, int count, float *__restrict__ dir,
+                                                          float *__restrict__ weight, int32_t *__restrict__ texel) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    uint32_t st = ptd::lcg_seed(seeds[i]);
+    f3 d;
+    float w;
+    int e, k = -1;
+    (void)ptd::direct_sample(lights, nlights, ptd::mk(0.0f, 0.0f, 0.0f), ptd::mk(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), st, d, w, e, &k);
+    dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+    weight[i] = w;
+    texel[i] = k;
+}
+
 // k_probe_shade_scatter through the direct form of the shader, as tile_shade<.., SH_DIRECT> calls it at bounce `depth` of a session of
 // traceDepth `trace_depth`: the scatter with last_bounce = (depth == trace_depth - 1), or -- depth == trace_depth -- the final ray's
-// scoring rule on the winning primitive hit_geom[i]
+// scoring rule on the winning primitive hit_geom[i].  env_n > 0 (pt_probe_shade_scatter_direct_sky): the table may end with the
+// sky's element, and a final ray aimed at it reads the map `env` where it misses
 __global__ __launch_bounds__(64) void k_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const float *__restrict__ mats,
                                                                     const float *__restrict__ lights, int nlights, pt_path_segment *paths,
                                                                     const pt_shadeable_intersection *__restrict__ isects,
-                                                                    const uint8_t *__restrict__ outside, const int32_t *__restrict__ hit_geom, int n) {
+                                                                    const uint8_t *__restrict__ outside, const int32_t *__restrict__ hit_geom, int n,
+                                                                    const float4 *__restrict__ env, int env_n) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     pt_path_segment p = paths[i];
@@ -244,7 +263,10 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_direct(int iter, int
     bool alive = false;
     if (depth == trace_depth) {
         const int target = nlights > 0 ? ptd::direct_target(lights, nlights, iter, p.pixelIndex, depth - 1) : -2;
-        if (x.t > 0.0f && hit_geom[i] == target) {
+        if (env_n > 0 && target == -1) {                   // PT_DIRECT_SKY: a sky-aimed ray scores on a miss only (tile_shade)
+            if (!(x.t > 0.0f)) ps.c = ptd::miss_colour(ps.c, ps.d, env, env_n);
+            else ps.c = ptd::mk(0.0f, 0.0f, 0.0f);
+        } else if (x.t > 0.0f && hit_geom[i] == target) {
             const float *m = mats + x.materialId * ptd::MAT_WORDS;
             ps.c = ptd::mul(ps.c, ptd::scale(ptd::mk(m[0], m[1], m[2]), m[9]));
         } else {
@@ -525,10 +547,12 @@ int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_materia
     return PT_OK;
 }
 
-int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
-                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
-                                  const uint8_t *outside, const int32_t *hit_geom, int n) {
-    const char *who = "pt_probe_shade_scatter_direct";
+// both direct forms of the shader probe: texels == nullptr -- the lamps' table; otherwise the table of a PT_DIRECT_SKY session
+// under the map (texels, env_n), as pt_set_environment makes it
+static int probe_shade_scatter_direct(const char *who, int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms,
+                                      const pt_material *materials, int num_materials, pt_path_segment *paths,
+                                      const pt_shadeable_intersection *isects, const uint8_t *outside, const int32_t *hit_geom, int n,
+                                      const float *texels, int env_n) {
     if (n < 0 || n > (1 << 26) || num_materials < 1 || trace_depth < 1 || trace_depth > MAX_DEPTH - 1 || depth < 0 || depth > trace_depth ||
         (n > 0 && (!paths || !isects || !materials)) || (n > 0 && depth == trace_depth && !hit_geom))
         return fail(PT_ERR_INVALID, "%s: bad argument", who);
@@ -536,26 +560,87 @@ int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt
         if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
             return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
     std::vector<float> rec;
-    const int ne = probe_light_records(who, geoms, num_geoms, materials, num_materials, rec);
+    int ne = probe_light_records(who, geoms, num_geoms, materials, num_materials, rec);
     if (ne < 0) return ne;
     if (n == 0) return PT_OK;
+    std::vector<float> quad;
+    if (texels && env_n > 0) {
+        std::vector<float> rows, cols, all;
+        if (ptlight::sky_table(texels, env_n, rows, cols)) {
+            ne = ptlight::sky_records(rec, env_n, rows, cols, all);
+            rec.swap(all);
+        }
+        const size_t count = (size_t)6 * (size_t)env_n * (size_t)env_n;
+        quad.assign(count * 4, 0.0f);
+        for (size_t k = 0; k < count; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    } else {
+        env_n = 0;
+    }
     std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
     pack_materials(materials, num_materials, mrec.data(), false);
     ProbeBufs b;
     const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
     const float *d_l = ne > 0 ? (const float *)b.get(rec.size() * 4, rec.data()) : nullptr;
+    const float4 *d_env = env_n > 0 ? (const float4 *)b.get(quad.size() * 4, quad.data()) : nullptr;
     pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
     const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
     const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
     const int32_t *d_hit = hit_geom ? (const int32_t *)b.get((size_t)n * 4, hit_geom) : nullptr;
-    if (!d_mats || (ne > 0 && !d_l) || !d_paths || !d_isects || (outside && !d_outside) || (hit_geom && !d_hit)) {
+    if (!d_mats || (ne > 0 && !d_l) || (env_n > 0 && !d_env) || !d_paths || !d_isects || (outside && !d_outside) || (hit_geom && !d_hit)) {
         (void)hipGetLastError();
         return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
     }
     hipLaunchKernelGGL(k_probe_shade_scatter_direct, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, trace_depth, d_mats, d_l, ne,
-                       d_paths, d_isects, d_outside, d_hit, n);
+                       d_paths, d_isects, d_outside, d_hit, n, d_env, env_n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                  const uint8_t *outside, const int32_t *hit_geom, int n) {
+    return probe_shade_scatter_direct("pt_probe_shade_scatter_direct", iter, depth, trace_depth, geoms, num_geoms, materials, num_materials,
+                                      paths, isects, outside, hit_geom, n, nullptr, 0);
+}
+
+int pt_probe_shade_scatter_direct_sky(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
+                                      int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                                      const uint8_t *outside, const int32_t *hit_geom, int n, const float *texels, int env_n) {
+    const char *who = "pt_probe_shade_scatter_direct_sky";
+    if (env_n < 0 || env_n > 1024 || (env_n > 0 && !texels)) return fail(PT_ERR_INVALID, "%s: bad map (n = %d)", who, env_n);
+    return probe_shade_scatter_direct(who, iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
+                                      hit_geom, n, texels, env_n);
+}
+
+int pt_probe_sky_sample(const float *texels, int n, const float *normals, const uint32_t *seeds, int count, float *dir, float *weight,
+                        int32_t *texel) {
+    if (n < 0 || n > 1024 || (n > 0 && !texels) || count < 0 || count > (1 << 26) || (count > 0 && (!normals || !seeds || !dir || !weight || !texel)))
+        return fail(PT_ERR_INVALID, "pt_probe_sky_sample: bad argument (n = %d, count = %d)", n, count);
+    if (count == 0) return PT_OK;
+    std::vector<float> rows, cols, rec;
+    if (!texels || n == 0 || !ptlight::sky_table(texels, n, rows, cols)) {
+        for (int i = 0; i < count; ++i) { dir[3 * i] = dir[3 * i + 1] = dir[3 * i + 2] = 0.0f; weight[i] = 0.0f; texel[i] = -1; }
+        return PT_OK;
+    }
+    const int ne = ptlight::sky_records(std::vector<float>(), n, rows, cols, rec);
+    ProbeBufs b;
+    const float *d_l = (const float *)b.get(rec.size() * 4, rec.data());
+    const float *d_n = (const float *)b.get((size_t)count * 12, normals);
+    const uint32_t *d_s = (const uint32_t *)b.get((size_t)count * 4, seeds);
+    float *d_d = (float *)b.get((size_t)count * 12, nullptr);
+    float *d_w = (float *)b.get((size_t)count * 4, nullptr);
+    int32_t *d_t = (int32_t *)b.get((size_t)count * 4, nullptr);
+    if (!d_l || !d_n || !d_s || !d_d || !d_w || !d_t) {
+        (void)hipGetLastError();
+        return fail(PT_ERR_DEVICE, "pt_probe_sky_sample: no HIP device / out of memory (this library has no CPU fallback)");
+    }
+    hipLaunchKernelGGL(k_probe_sky_sample, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_l, ne, d_n, d_s, count, d_d, d_w, d_t);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(dir, d_d, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(weight, d_w, (size_t)count * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(texel, d_t, (size_t)count * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }

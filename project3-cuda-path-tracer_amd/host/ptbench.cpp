@@ -6,7 +6,7 @@
 //           [--cache-first] [--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S]
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
-//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures] [--albedo]
+//           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]
 //
 // --albedo (needs --denoise): pt_set_denoise_albedo(1) before the first filtered picture -- every one of them, the --move /
 // --temporal ones included, is filtered as colour / first-hit albedo and multiplied back (include/ptmi355.h, DESIGN.md section
@@ -19,6 +19,11 @@
 //
 // --direct: PT_DIRECT_LIGHT -- the last bounce of a path that hits a diffuse surface aims a final ray at a sampled point of an
 // emissive cube or sphere (DEPTH + 1 bounces; include/ptmi355.h).  scenes/cornell_two_lamps.txt.
+//
+// --direct-sky: PT_DIRECT_LIGHT | PT_DIRECT_SKY -- the environment map (--sky) is one more light element of that sampler, and a
+// final ray aimed at it scores where it leaves the scene.  scenes/open_sky_sun.txt.
+// --sun X,Y,Z,COS,R,G,B (needs --sky): every texel of the baked map whose centre direction c has dot(c, (X,Y,Z) / |(X,Y,Z)|) >= COS
+// is replaced by (R, G, B) -- float64, operation for operation what binding.sun_on_cubemap does (the same texels bit for bit).
 //
 // --glossy: PT_GLOSSY -- a mirror or dielectric whose material has SPECEX > 0 scatters about a sampled microfacet normal (a GGX
 // lobe of alpha^2 = 2 / (SPECEX + 2); include/ptmi355.h).  Without it SPECEX is ignored (scenes/cornell_glossy.txt then renders
@@ -81,7 +86,7 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--glossy] [--direct] [--textures] [--albedo]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -96,6 +101,8 @@ int main(int argc, char **argv) {
     pt_temporal_params tp = {64, 0.1f, 0.1f};
     int sky_n = 0;
     double sky[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};          // zenith, horizon, ground
+    bool sun = false;
+    double sun_v[7] = {0, 0, 0, 0, 0, 0, 0};              // direction, cosine of the half angle, colour
     std::string resume;
     int start = -1;
     float lens_radius = 0.0f, focal_distance = 0.0f;
@@ -114,6 +121,14 @@ int main(int argc, char **argv) {
         else if (a == "--aa") flags |= PT_AA_JITTER;
         else if (a == "--glossy") flags |= PT_GLOSSY;
         else if (a == "--direct") flags |= PT_DIRECT_LIGHT;
+        else if (a == "--direct-sky") flags |= PT_DIRECT_LIGHT | PT_DIRECT_SKY;
+        else if (a == "--sun" && i + 1 < argc) {
+            if (sscanf(argv[++i], "%lf,%lf,%lf,%lf,%lf,%lf,%lf", &sun_v[0], &sun_v[1], &sun_v[2], &sun_v[3], &sun_v[4], &sun_v[5], &sun_v[6]) != 7) {
+                fprintf(stderr, "--sun wants X,Y,Z,COS,R,G,B\n");
+                return 1;
+            }
+            sun = true;
+        }
         else if (a == "--textures") flags |= PT_TEXTURES;
         else if (a == "--albedo") albedo = true;
         else if (a == "--lens" && i + 2 < argc) { lens_radius = (float)atof(argv[++i]); focal_distance = (float)atof(argv[++i]); }
@@ -171,6 +186,7 @@ int main(int argc, char **argv) {
     pth_scene *sc = pth_load_scene(argv[1]);
     if (!sc) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
     if (iters < 0) iters = sc->iterations;
+    if (sun && sky_n < 1) { fprintf(stderr, "--sun needs --sky (the map it is painted on)\n"); return 1; }
     if (albedo && !denoise) { fprintf(stderr, "--albedo needs --denoise (the filter it switches to irradiance)\n"); return 1; }
     if (move && !denoise) { fprintf(stderr, "--move needs --denoise (the filter its pictures go through)\n"); return 1; }
     if (per_call) {
@@ -219,6 +235,12 @@ int main(int argc, char **argv) {
                     for (int k = 0; k < 3; ++k) {
                         const double z = sky[k], h = sky[3 + k], g = sky[6 + k];
                         t[k] = (float)(h + (z - h) * up + (g - h) * down);
+                    }
+                    if (sun) {
+                        const double sl = std::sqrt(sun_v[0] * sun_v[0] + sun_v[1] * sun_v[1] + sun_v[2] * sun_v[2]);
+                        const double ln = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+                        const double cosine = (v[0] * (sun_v[0] / sl) + v[1] * (sun_v[1] / sl) + v[2] * (sun_v[2] / sl)) / ln;
+                        if (cosine >= sun_v[3]) for (int k = 0; k < 3; ++k) t[k] = (float)sun_v[4 + k];
                     }
                 }
         if (pt_set_environment(tex.data(), n) != PT_OK) { fprintf(stderr, "pt_set_environment: %s\n", pt_last_error()); return 1; }
