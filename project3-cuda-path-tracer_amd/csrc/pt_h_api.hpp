@@ -5,7 +5,8 @@
 // ===========================================================================
 // the entry points of ONE context (the C-ABI of include/ptmi355.h, applied to the calling thread's context `R`);
 // the exported symbols are defined in pt_multi.hpp, which forwards to these directly (one device) or through the
-// per-device worker threads (several)
+// per-device worker threads (several).  The host-only builders at the end of this file read no context and are the
+// exported symbols themselves
 // ===========================================================================
 namespace one {
 
@@ -1400,6 +1401,51 @@ int pt_get_bvh_info(pt_bvh_info *out) {
     return PT_OK;
 }
 
+int pt_get_counters(int64_t *rays, int64_t *first_bounce_rays, int64_t *iterations) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_counters: not initialised");
+    Persist p;
+    HIPCHK(hipMemcpyAsync(&p, R.persist, sizeof p, hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    if (rays) *rays = (int64_t)p.rays;
+    if (first_bounce_rays) *first_bounce_rays = (int64_t)p.first_rays;
+    if (iterations) *iterations = (int64_t)p.iterations;
+    return PT_OK;
+}
+
+int pt_set_profiling(int enable) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_profiling: not initialised");
+    int rc = drain_events();
+    if (rc) return rc;
+    if (enable && R.ev.empty()) {
+        R.ev.resize(2 * EV_PAIRS);
+        R.ev_stage.assign(EV_PAIRS, 0);
+        for (auto &e : R.ev) HIPCHK(hipEventCreate(&e));
+    }
+    R.profiling = enable != 0;
+    R.prof = pt_profile{};
+    return PT_OK;
+}
+
+int pt_get_profile(pt_profile *out) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_profile: not initialised");
+    if (!out) return fail(PT_ERR_INVALID, "pt_get_profile: null");
+    int rc = drain_events();
+    if (rc) return rc;
+    *out = R.prof;
+    return PT_OK;
+}
+
+int pt_get_stats(pt_stats *stats) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_stats: not initialised");
+    if (!stats) return fail(PT_ERR_INVALID, "pt_get_stats: null");
+    *stats = R.stats;
+    return PT_OK;
+}
+
+}  // namespace one
+
+// ---- host-only builders: what pt_init makes of meshes, primitives, lamps and the sky, on caller data.  No context is read, so
+// these are the exported symbols themselves (include/ptmi355.h has declared them extern "C") ----
 int pt_bvh_build(const pt_triangle *triangles, int count, float *nodes, int node_capacity, int32_t *order, float *grid) {
     if (count < 0 || (count > 0 && !triangles)) return fail(PT_ERR_INVALID, "pt_bvh_build: bad triangle list");
     ptbvh::Tree tree;
@@ -1454,40 +1500,6 @@ int pt_cull_boxes(const pt_geom *geoms, int count, const float *eye, float *boxe
     return PT_OK;
 }
 
-int pt_get_counters(int64_t *rays, int64_t *first_bounce_rays, int64_t *iterations) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_counters: not initialised");
-    Persist p;
-    HIPCHK(hipMemcpyAsync(&p, R.persist, sizeof p, hipMemcpyDeviceToHost, R.stream));
-    HIPCHK(hipStreamSynchronize(R.stream));
-    if (rays) *rays = (int64_t)p.rays;
-    if (first_bounce_rays) *first_bounce_rays = (int64_t)p.first_rays;
-    if (iterations) *iterations = (int64_t)p.iterations;
-    return PT_OK;
-}
-
-int pt_set_profiling(int enable) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_profiling: not initialised");
-    int rc = drain_events();
-    if (rc) return rc;
-    if (enable && R.ev.empty()) {
-        R.ev.resize(2 * EV_PAIRS);
-        R.ev_stage.assign(EV_PAIRS, 0);
-        for (auto &e : R.ev) HIPCHK(hipEventCreate(&e));
-    }
-    R.profiling = enable != 0;
-    R.prof = pt_profile{};
-    return PT_OK;
-}
-
-int pt_get_profile(pt_profile *out) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_profile: not initialised");
-    if (!out) return fail(PT_ERR_INVALID, "pt_get_profile: null");
-    int rc = drain_events();
-    if (rc) return rc;
-    *out = R.prof;
-    return PT_OK;
-}
-
 // PT_DIRECT_LIGHT's light element table (include/ptmi355.h; pt_lights.hpp): what pt_init builds, host only
 int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, pt_light_element *out, int capacity) {
     if (num_geoms < 0 || num_materials < 0 || capacity < 0 || (num_geoms > 0 && !geoms) || (num_materials > 0 && !materials) || (capacity > 0 && !out))
@@ -1510,12 +1522,3 @@ int pt_sky_table(const float *texels, int n, float *row, float *col) {
     if (col) memcpy(col, cols.data(), cols.size() * 4);
     return 1;
 }
-
-int pt_get_stats(pt_stats *stats) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_stats: not initialised");
-    if (!stats) return fail(PT_ERR_INVALID, "pt_get_stats: null");
-    *stats = R.stats;
-    return PT_OK;
-}
-
-}  // namespace one

@@ -1,5 +1,7 @@
-// pt_multi.hpp -- the exported C-ABI of libptmi355.so (include/ptmi355.h) and, behind it, the frame tiled over
-// several GPUs of one node INSIDE the library (included by ptmi355.hip only).
+// pt_multi.hpp -- the exported C-ABI of libptmi355.so (include/ptmi355.h) where a call depends on the session and, behind it,
+// the frame tiled over several GPUs of one node INSIDE the library (included by ptmi355.hip only, last of the headers).  The
+// entry points that touch no session -- the probes of pt_probe.hpp and the host-only builders at the end of pt_h_api.hpp --
+// are exported where they are defined: there is nothing to dispatch.
 //
 // The reference renders on one device chosen by the host (cudaGLSetGLDevice(0), preview.cpp:107) and keeps its
 // renderer state in file-static globals (pathtrace.cu:70-75).  Here a session owns one CONTEXT per device
@@ -1058,101 +1060,6 @@ int pt_get_profile(pt_profile *out) {
 int pt_get_bvh_info(pt_bvh_info *out) {
     if (!G.live) return one::pt_get_bvh_info(out);
     return on_one(0, [&](Worker &) -> int { return one::pt_get_bvh_info(out); });
-}
-
-int pt_bvh_build(const pt_triangle *triangles, int count, float *nodes, int node_capacity, int32_t *order, float *grid) {
-    return one::pt_bvh_build(triangles, count, nodes, node_capacity, order, grid);
-}
-int pt_tri_bounds(const pt_triangle *triangles, int count, float origin_bound, float *bounds) {
-    return one::pt_tri_bounds(triangles, count, origin_bound, bounds);
-}
-int pt_tri_records(const pt_triangle *triangles, int count, float origin_bound, uint16_t *records, float frame[4]) {
-    return one::pt_tri_records(triangles, count, origin_bound, records, frame);
-}
-int pt_cull_boxes(const pt_geom *geoms, int count, const float *eye, float *boxes, float *origin_bound, float *reject) {
-    return one::pt_cull_boxes(geoms, count, eye, boxes, origin_bound, reject);
-}
-int pt_probe_rng(const uint32_t *seeds, int n, int draws, uint32_t *state, float *u) { return one::pt_probe_rng(seeds, n, draws, state, u); }
-int pt_probe_sincos(const float *x, uint32_t first_bits, uint32_t n, float *s, float *c, uint64_t sum[2]) {
-    return one::pt_probe_sincos(x, first_bits, n, s, c, sum);
-}
-int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, float *dirs) { return one::pt_probe_hemisphere(normals, seeds, n, dirs); }
-int pt_probe_shade_scatter(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
-                           const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
-    return one::pt_probe_shade_scatter(iter, depth, materials, num_materials, paths, isects, outside, n, deferred);
-}
-int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
-                                  const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
-    return one::pt_probe_shade_scatter_glossy(iter, depth, materials, num_materials, paths, isects, outside, n, deferred);
-}
-int pt_glossy_alpha2(const float *exponents, int count, float *alpha2) { return one::pt_glossy_alpha2(exponents, count, alpha2); }
-int pt_light_elements(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, pt_light_element *out, int capacity) {
-    return one::pt_light_elements(geoms, num_geoms, materials, num_materials, out, capacity);
-}
-int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, const float *P,
-                           const float *n, const uint32_t *seeds, int count, float *dir, float *weight, int32_t *element) {
-    return one::pt_probe_direct_sample(geoms, num_geoms, materials, num_materials, P, n, seeds, count, dir, weight, element);
-}
-int pt_probe_shade_scatter_direct(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
-                                  int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
-                                  const uint8_t *outside, const int32_t *hit_geom, int n) {
-    return one::pt_probe_shade_scatter_direct(iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
-                                              hit_geom, n);
-}
-int pt_probe_shade_scatter_direct_sky(int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms, const pt_material *materials,
-                                      int num_materials, pt_path_segment *paths, const pt_shadeable_intersection *isects,
-                                      const uint8_t *outside, const int32_t *hit_geom, int n, const float *texels, int env_n) {
-    return one::pt_probe_shade_scatter_direct_sky(iter, depth, trace_depth, geoms, num_geoms, materials, num_materials, paths, isects, outside,
-                                                  hit_geom, n, texels, env_n);
-}
-int pt_probe_sky_sample(const float *texels, int n, const float *normals, const uint32_t *seeds, int count, float *dir, float *weight,
-                        int32_t *texel) {
-    return one::pt_probe_sky_sample(texels, n, normals, seeds, count, dir, weight, texel);
-}
-int pt_sky_table(const float *texels, int n, float *row, float *col) { return one::pt_sky_table(texels, n, row, col); }
-int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const float *alpha2, int n, float *dirs) {
-    return one::pt_probe_glossy_lobe(normals, seeds, alpha2, n, dirs);
-}
-int pt_environment_texel(const float *dirs, int count, int n, int32_t *index) { return one::pt_environment_texel(dirs, count, n, index); }
-int pt_probe_environment(const float *texels, int n, const float *dirs, const float *throughput, int count, float *colour) {
-    return one::pt_probe_environment(texels, n, dirs, throughput, count, colour);
-}
-int pt_texture_texel(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n, int32_t *index) {
-    return one::pt_texture_texel(geoms, num_geoms, hit_geom, points, count, n, index);
-}
-int pt_probe_texture(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, const float *texels, int n,
-                     const float *colour_in, float *colour_out) {
-    return one::pt_probe_texture(geoms, num_geoms, hit_geom, points, count, texels, n, colour_in, colour_out);
-}
-int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
-                                    const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
-                                    const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
-                                    const int32_t *tex_n, const int32_t *tex_offset) {
-    return one::pt_probe_shade_scatter_textured(iter, depth, materials, num_materials, paths, isects, outside, n, deferred, geoms, num_geoms,
-                                                hit_geom, tex_texels, tex_n, tex_offset);
-}
-int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
-                   int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
-    return one::pt_bump_normal(geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
-}
-int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
-                         int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
-    return one::pt_probe_bump_normal(geoms, num_geoms, hit_geom, points, normals, dirs, count, texels, n, out_normals, perturbed);
-}
-int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materials, int num_materials, pt_path_segment *paths,
-                                  const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred,
-                                  const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
-                                  const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
-                                  const int32_t *bump_offset) {
-    return one::pt_probe_shade_scatter_bumped(iter, depth, materials, num_materials, paths, isects, outside, n, deferred, geoms, num_geoms,
-                                              hit_geom, tex_texels, tex_n, tex_offset, bump_texels, bump_n, bump_offset);
-}
-int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) { return one::pt_probe_sqrt(first_bits, n, mismatch); }
-int pt_probe_clock(int microseconds, double *ghz) { return one::pt_probe_clock(microseconds, ghz); }
-int pt_probe_own_surface_plan(uint64_t paths, int ngeoms, int plain_fused) { return one::pt_probe_own_surface_plan(paths, ngeoms, plain_fused); }
-int pt_probe_tri_form(const pt_triangle *triangles, int count, float origin_bound, const float *origins, const float *directions, int n,
-                      uint16_t *ray_slots, int32_t *ray_class, float *form) {
-    return one::pt_probe_tri_form(triangles, count, origin_bound, origins, directions, n, ray_slots, ray_class, form);
 }
 
 }  // extern "C"

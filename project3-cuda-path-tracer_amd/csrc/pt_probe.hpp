@@ -1,10 +1,11 @@
-// pt_probe.hpp -- known-answer probes of libptmi355.so (included by ptmi355.hip only): the device functions of
+// pt_probe.hpp -- known-answer probes of libptmi355.so (included by ptmi355.hip only, before pt_multi.hpp): the device functions of
 // pt_device.hpp that restate third-party arithmetic the reference merely calls -- thrust's minstd_rand + u01
 // (pathtrace.cu:41-45, interactions.h:12-13), the sin / cos binding of interactions.h:40-41 and
 // calculateRandomDirectionInHemisphere (interactions.h:10-42) -- and this project's own completion of the empty scatterRay
 // (interactions.h:69-79: ptd::shade_scatter) run on caller data, so that a test can hold them against published constants,
 // the reference's glm vectors and the oracle one function at a time instead of through whole images.
-// No session needed: the probes run on the calling thread's current HIP device.
+// No session needed: the probes run on the calling thread's current HIP device, and their entry points are the exported symbols
+// themselves (global scope; include/ptmi355.h has declared them extern "C") -- pt_multi.hpp has nothing to dispatch for them.
 #pragma once
 
 namespace {
@@ -67,40 +68,57 @@ __global__ void k_probe_glossy_lobe(const float *normals, const uint32_t *seeds,
     dirs[3 * i] = d.x; dirs[3 * i + 1] = d.y; dirs[3 * i + 2] = d.z;
 }
 
-// one pass of the loop body's shader (pathtrace.cu:224-266 with scatterRay completed, DESIGN.md section 3) through the kernels'
-// own ptd::shade_scatter: one lane per (path, intersection) pair, host structs as they are.  A path that ends keeps the ray it
-// came with.  defer != 0: the deferring kernels' call -- a diffuse survivor comes back with the hit normal for a direction and
-// draws it afterwards, as the next bounce's load does.  GLOSSY: the form a PT_GLOSSY session's kernels call
-template <bool GLOSSY>
-__global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
-                                                             const pt_shadeable_intersection *__restrict__ isects,
-                                                             const uint8_t *__restrict__ outside, int n, int defer) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    pt_path_segment p = paths[i];
-    if (p.remainingBounces <= 0) return;                            // (the oracle's compaction-off mode: untouched)
-    const pt_shadeable_intersection x = isects[i];
-    ptd::PathState ps;
+// ---- what the shade-scatter probes share: one lane per (path, intersection) record, host structs as they are.  Each kernel is
+// probe_load, its own call of the shader, probe_resolve_pending where that call can defer, probe_store ----
+// record i into locals; false for a lane past the records and for a path that has ended (the oracle's compaction-off mode:
+// untouched).  outside == nullptr: every hit is from outside
+__device__ __forceinline__ bool probe_load(const pt_path_segment *paths, const pt_shadeable_intersection *isects, const uint8_t *outside, int n,
+                                           int i, pt_path_segment &p, pt_shadeable_intersection &x, ptd::PathState &ps, int &out) {
+    if (i >= n) return false;
+    p = paths[i];
+    if (p.remainingBounces <= 0) return false;
+    x = isects[i];
     ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
     ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
     ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
-    bool deferred = false;
-    const bool alive = ptd::shade_scatter<GLOSSY>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
-                                          outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
-                                          defer != 0, &deferred);
-    if (deferred) {
-        // what the next bounce's load does with a pending direction (pt_k_bounce.hpp: tile_load<RESOLVE>, whose `depth - 1`
-        // is this bounce's depth): the same engine, the same sampler, on the normal the scatter left in the direction
-        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
-        ps.d = ptd::hemisphere(ps.d, rng);
-    }
-    pt_path_segment *q = paths + i;
+    out = outside ? (outside[i] ? 1 : 0) : 1;
+    return true;
+}
+// what the next bounce's load does with a pending direction (pt_k_bounce.hpp: tile_load<RESOLVE>, whose `depth - 1`
+// is this bounce's depth): the same engine, the same sampler, on the normal the scatter left in the direction
+__device__ __forceinline__ void probe_resolve_pending(ptd::PathState &ps, int iter, int pixel, int depth) {
+    uint32_t rng = ptd::seeded_engine(iter, pixel, depth);
+    ps.d = ptd::hemisphere(ps.d, rng);
+}
+// a path that ends keeps the ray it came with
+__device__ __forceinline__ void probe_store(pt_path_segment *q, const ptd::PathState &ps, bool alive, int remaining) {
     if (alive) {
         q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
         q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
     }
     q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
-    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
+    q->remainingBounces = remaining;
+}
+
+// one pass of the loop body's shader (pathtrace.cu:224-266 with scatterRay completed, DESIGN.md section 3) through the kernels'
+// own ptd::shade_scatter.  defer != 0: the deferring kernels' call -- a diffuse survivor comes back with the hit normal for a
+// direction and draws it afterwards, as the next bounce's load does.  GLOSSY: the form a PT_GLOSSY session's kernels call
+template <bool GLOSSY>
+__global__ __launch_bounds__(64) void k_probe_shade_scatter(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
+                                                             const pt_shadeable_intersection *__restrict__ isects,
+                                                             const uint8_t *__restrict__ outside, int n, int defer) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    pt_path_segment p;
+    pt_shadeable_intersection x;
+    ptd::PathState ps;
+    int out;
+    if (!probe_load(paths, isects, outside, n, i, p, x, ps, out)) return;
+    bool deferred = false;
+    const bool alive = ptd::shade_scatter<GLOSSY>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
+                                          out, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                          defer != 0, &deferred);
+    if (deferred) probe_resolve_pending(ps, iter, p.pixelIndex, depth);
+    probe_store(paths + i, ps, alive, alive ? p.remainingBounces - 1 : 0);
 }
 
 // PT_TEXTURES' lookup and multiply through the kernels' own ptd::texture_tint: one lane per (primitive,
@@ -126,14 +144,11 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_textured(int iter, i
                                                                       const int32_t *__restrict__ hit_geom, const float4 *__restrict__ texels,
                                                                       const int2 *__restrict__ tab) {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    pt_path_segment p = paths[i];
-    if (p.remainingBounces <= 0) return;
-    const pt_shadeable_intersection x = isects[i];
+    pt_path_segment p;
+    pt_shadeable_intersection x;
     ptd::PathState ps;
-    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
-    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
-    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    int out;
+    if (!probe_load(paths, isects, outside, n, i, p, x, ps, out)) return;
     bool deferred = false;
     f3 mcol = ptd::mk(0.0f, 0.0f, 0.0f);
     if (x.t > 0.0f) {
@@ -141,19 +156,10 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_textured(int iter, i
         mcol = ptd::texture_mcol(mats, x.materialId, (uint32_t)type[g], inv + (size_t)g * 12, ps.o, ps.d, x.t, tab, texels);
     }
     const bool alive = ptd::shade_scatter<false, false, true>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
-                                                              outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                                              out, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
                                                               defer != 0, &deferred, nullptr, nullptr, 0, &mcol);
-    if (deferred) {
-        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
-        ps.d = ptd::hemisphere(ps.d, rng);
-    }
-    pt_path_segment *q = paths + i;
-    if (alive) {
-        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
-        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
-    }
-    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
-    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
+    if (deferred) probe_resolve_pending(ps, iter, p.pixelIndex, depth);
+    probe_store(paths + i, ps, alive, alive ? p.remainingBounces - 1 : 0);
 }
 
 // bump mapping through the kernels' own ptd::bump_normal: one lane per (primitive, world point, reported
@@ -183,30 +189,18 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_bumped(int iter, int
                                                                     const int2 *__restrict__ tab, const ptd::bump_texel *__restrict__ bumps,
                                                                     const int2 *__restrict__ btab) {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    pt_path_segment p = paths[i];
-    if (p.remainingBounces <= 0) return;
-    const pt_shadeable_intersection x = isects[i];
+    pt_path_segment p;
+    pt_shadeable_intersection x;
     ptd::PathState ps;
-    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
-    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
-    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    int out;
+    if (!probe_load(paths, isects, outside, n, i, p, x, ps, out)) return;
     bool deferred = false;
     const int g = x.t > 0.0f ? hit_geom[i] : 0;
     const bool alive = ptd::shade_scatter_tex<false>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
-                                                     outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
+                                                     out, mats, iter, p.pixelIndex, depth, p.remainingBounces == 1,
                                                      defer != 0, &deferred, nullptr, (uint32_t)type[g], rec + (size_t)g * 36, tab, texels, btab, bumps);
-    if (deferred) {
-        uint32_t rng = ptd::seeded_engine(iter, p.pixelIndex, depth);
-        ps.d = ptd::hemisphere(ps.d, rng);
-    }
-    pt_path_segment *q = paths + i;
-    if (alive) {
-        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
-        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
-    }
-    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
-    q->remainingBounces = alive ? p.remainingBounces - 1 : 0;
+    if (deferred) probe_resolve_pending(ps, iter, p.pixelIndex, depth);
+    probe_store(paths + i, ps, alive, alive ? p.remainingBounces - 1 : 0);
 }
 
 // PT_DIRECT_LIGHT's sampler through the kernels' own ptd::direct_sample, seeded like k_probe_hemisphere
@@ -252,14 +246,11 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_direct(int iter, int
                                                                     const uint8_t *__restrict__ outside, const int32_t *__restrict__ hit_geom, int n,
                                                                     const float4 *__restrict__ env, int env_n) {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    pt_path_segment p = paths[i];
-    if (p.remainingBounces <= 0) return;
-    const pt_shadeable_intersection x = isects[i];
+    pt_path_segment p;
+    pt_shadeable_intersection x;
     ptd::PathState ps;
-    ps.o = ptd::mk(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z);
-    ps.d = ptd::mk(p.ray.direction.x, p.ray.direction.y, p.ray.direction.z);
-    ps.c = ptd::mk(p.color.x, p.color.y, p.color.z);
+    int out;
+    if (!probe_load(paths, isects, outside, n, i, p, x, ps, out)) return;
     bool alive = false;
     if (depth == trace_depth) {
         const int target = nlights > 0 ? ptd::direct_target(lights, nlights, iter, p.pixelIndex, depth - 1) : -2;
@@ -274,16 +265,10 @@ __global__ __launch_bounds__(64) void k_probe_shade_scatter_direct(int iter, int
         }
     } else {
         alive = ptd::shade_scatter<false, true>(ps, x.t, ptd::mk(x.surfaceNormal.x, x.surfaceNormal.y, x.surfaceNormal.z), x.materialId,
-                                                outside ? (outside[i] ? 1 : 0) : 1, mats, iter, p.pixelIndex, depth, depth == trace_depth - 1,
+                                                out, mats, iter, p.pixelIndex, depth, depth == trace_depth - 1,
                                                 false, nullptr, nullptr, lights, nlights);
     }
-    pt_path_segment *q = paths + i;
-    if (alive) {
-        q->ray.origin.x = ps.o.x; q->ray.origin.y = ps.o.y; q->ray.origin.z = ps.o.z;
-        q->ray.direction.x = ps.d.x; q->ray.direction.y = ps.d.y; q->ray.direction.z = ps.d.z;
-    }
-    q->color.x = ps.c.x; q->color.y = ps.c.y; q->color.z = ps.c.z;
-    q->remainingBounces = alive ? trace_depth - depth : 0;
+    probe_store(paths + i, ps, alive, alive ? trace_depth - depth : 0);
 }
 
 // the miss exit's colour through the kernels' own ptd::miss_colour: one lane per (direction, throughput) pair
@@ -344,35 +329,229 @@ __global__ __launch_bounds__(64) void k_probe_tri_form(const pt_half8 *__restric
     }
 }
 
-// device scratch of one probe call: freed on every exit path
+// device scratch of one probe call: freed on every exit path.  A failed allocation or upload sticks: the call site asks ok() once,
+// after its last buffer
 struct ProbeBufs {
     std::vector<void *> mem;
+    bool failed = false;
     ~ProbeBufs() { for (void *p : mem) if (p) (void)hipFree(p); }
     void *get(size_t bytes, const void *init) {
         void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
+        if (failed || hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) { failed = true; return nullptr; }
         mem.push_back(p);
-        if (init ? hipMemcpy(p, init, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, bytes ? bytes : 4) != hipSuccess) return nullptr;
-        return p;
+        if (init ? hipMemcpy(p, init, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, bytes ? bytes : 4) != hipSuccess) failed = true;
+        return failed ? nullptr : p;
+    }
+    // `count` elements of the caller's array on the device; an array the caller left out (nullptr) stays nullptr
+    template <typename T> T *in(const T *host, size_t count) { return host ? (T *)get(count * sizeof(T), host) : nullptr; }
+    // `count` zeroed elements for the kernel to write
+    template <typename T> T *out(size_t count) { return (T *)get(count * sizeof(T), nullptr); }
+    bool ok() const { return !failed; }
+    // ... and back (a result the caller did not ask for, host == nullptr, is skipped)
+    template <typename T> hipError_t fetch(T *host, const T *dev, size_t count) {
+        return host ? hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
     }
 };
 
+// what entry point `who` answers when its buffers could not be made
+int probe_no_device(const char *who) {
+    (void)hipGetLastError();
+    return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
+}
+
+// every record that hits (t > 0) names a material of the table
+int probe_check_materials(const char *who, const pt_shadeable_intersection *isects, int n, int num_materials) {
+    for (int i = 0; i < n; ++i)
+        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
+            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
+    return PT_OK;
+}
+// ... and a primitive of the scene; isects == nullptr: the records are primitives and points, and every one is looked at
+int probe_check_geoms(const char *who, const pt_shadeable_intersection *isects, const int32_t *hit_geom, int n, int num_geoms) {
+    for (int i = 0; i < n; ++i)
+        if ((!isects || isects[i].t > 0.0f) && (hit_geom[i] < 0 || hit_geom[i] >= num_geoms))
+            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
+    return PT_OK;
+}
+
+// `count` RGB texels in the session's device layout: {r, g, b, 0}
+std::vector<float> rgb_quads(const float *texels, size_t count) {
+    std::vector<float> quad(std::max<size_t>(count, 1) * 4, 0.0f);
+    for (size_t k = 0; k < count; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    return quad;
+}
+// {da, db} of `count` RGB texels
+std::vector<float> bump_pairs(const float *texels, size_t count) {
+    std::vector<float> pair(std::max<size_t>(count, 1) * 2, 0.0f);
+    for (size_t k = 0; k < count; ++k) { pair[2 * k] = texels[3 * k]; pair[2 * k + 1] = texels[3 * k + 1]; }
+    return pair;
+}
+
+// a per-material table of cube maps (`what`: "texture" / "bump map"; material m: n[m] x n[m] texels per face from texel offset[m],
+// n[m] == 0: none) as the kernels read it, {offset, n} per material, and the texels it reaches
+int probe_cube_table(const char *who, const char *what, int num_materials, const int32_t *n, const int32_t *offset, std::vector<int2> &tab,
+                     size_t &reach) {
+    tab.resize((size_t)num_materials);
+    reach = 0;
+    for (int m = 0; m < num_materials; ++m) {
+        if (n[m] < 0 || n[m] > 1024 || (n[m] > 0 && offset[m] < 0))
+            return fail(PT_ERR_INVALID, "%s: material %d has a %s of n = %d at offset %d", who, m, what, n[m], offset[m]);
+        if (n[m] > 0) reach = std::max(reach, (size_t)offset[m] + (size_t)6 * (size_t)n[m] * (size_t)n[m]);
+        tab[(size_t)m] = make_int2(n[m] > 0 ? offset[m] : 0, n[m]);
+    }
+    return PT_OK;
+}
+
+// the arguments every shade-scatter probe takes (deferred: 0 where the probe has none); true: refuse.  Everything is refused
+// before anything is launched: the kernels never index past the material table
+bool probe_shade_args_bad(int n, int num_materials, int deferred, const pt_path_segment *paths, const pt_shadeable_intersection *isects,
+                          const pt_material *materials) {
+    return n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials));
+}
+
+// the records of a shade-scatter probe on the device -- pt_init's own material records, the paths, the intersections, `outside`
+// where the caller gave it -- with room for the probe's own inputs; after the launch, finish() brings the paths back
+struct ShadeRecords : ProbeBufs {
+    const float *mats;
+    pt_path_segment *paths, *host_paths;
+    const pt_shadeable_intersection *isects;
+    const uint8_t *outside;
+    size_t n;
+    ShadeRecords(const pt_material *materials, int num_materials, bool glossy, pt_path_segment *paths_, const pt_shadeable_intersection *isects_,
+                 const uint8_t *outside_, int n_) : host_paths(paths_), n((size_t)n_) {
+        std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
+        one::pack_materials(materials, num_materials, mrec.data(), glossy);
+        mats = in(mrec.data(), mrec.size());
+        paths = in(paths_, n);
+        isects = in(isects_, n);
+        outside = in(outside_, n);
+    }
+    dim3 grid() const { return dim3((unsigned)((n + 63) / 64)); }
+    int finish() {
+        HIPCHK(hipGetLastError());
+        HIPCHK(fetch(host_paths, paths, n));
+        HIPCHK(hipDeviceSynchronize());
+        return PT_OK;
+    }
+};
+
+// pt_probe_shade_scatter (glossy = false) and pt_probe_shade_scatter_glossy (true): `who` names the entry point in messages
+int probe_shade_scatter(const char *who, bool glossy, int iter, int depth, const pt_material *materials, int num_materials,
+                        pt_path_segment *paths, const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
+    if (probe_shade_args_bad(n, num_materials, deferred, paths, isects, materials)) return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    const int rc = probe_check_materials(who, isects, n, num_materials);
+    if (rc) return rc;
+    if (n == 0) return PT_OK;
+    ShadeRecords r(materials, num_materials, glossy, paths, isects, outside, n);
+    if (!r.ok()) return probe_no_device(who);
+    if (glossy) hipLaunchKernelGGL(k_probe_shade_scatter<true>, r.grid(), dim3(64), 0, 0, iter, depth, r.mats, r.paths, r.isects, r.outside, n, deferred);
+    else hipLaunchKernelGGL(k_probe_shade_scatter<false>, r.grid(), dim3(64), 0, 0, iter, depth, r.mats, r.paths, r.isects, r.outside, n, deferred);
+    return r.finish();
+}
+
+// the light table of a probe call: pt_init's own functions; -1 with the message set
+int probe_light_records(const char *who, const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials,
+                        std::vector<float> &rec) {
+    if (num_geoms < 0 || num_materials < 1 || !materials || (num_geoms > 0 && !geoms)) return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    std::vector<pt_light_element> el;
+    const int ne = ptlight::elements(geoms, num_geoms, materials, num_materials, el);
+    if (ne < 0) return fail(PT_ERR_INVALID, "%s: a cube or sphere names a material outside [0, %d)", who, num_materials);
+    if (ne > ptlight::MAX_ELEMENTS) return fail(PT_ERR_INVALID, "%s: %d light elements (at most %d)", who, ne, ptlight::MAX_ELEMENTS);
+    ptlight::records(geoms, el, rec);
+    return ne;
+}
+
+// both direct forms of the shader probe: texels == nullptr -- the lamps' table; otherwise the table of a PT_DIRECT_SKY session
+// under the map (texels, env_n), as pt_set_environment makes it
+int probe_shade_scatter_direct(const char *who, int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms,
+                               const pt_material *materials, int num_materials, pt_path_segment *paths,
+                               const pt_shadeable_intersection *isects, const uint8_t *outside, const int32_t *hit_geom, int n,
+                               const float *texels, int env_n) {
+    if (probe_shade_args_bad(n, num_materials, 0, paths, isects, materials) || trace_depth < 1 || trace_depth > MAX_DEPTH - 1 || depth < 0 ||
+        depth > trace_depth || (n > 0 && depth == trace_depth && !hit_geom))
+        return fail(PT_ERR_INVALID, "%s: bad argument", who);
+    const int rc = probe_check_materials(who, isects, n, num_materials);
+    if (rc) return rc;
+    std::vector<float> rec;
+    int ne = probe_light_records(who, geoms, num_geoms, materials, num_materials, rec);
+    if (ne < 0) return ne;
+    if (n == 0) return PT_OK;
+    std::vector<float> quad;
+    if (texels && env_n > 0) {
+        std::vector<float> rows, cols, all;
+        if (ptlight::sky_table(texels, env_n, rows, cols)) {
+            ne = ptlight::sky_records(rec, env_n, rows, cols, all);
+            rec.swap(all);
+        }
+        quad = rgb_quads(texels, (size_t)6 * (size_t)env_n * (size_t)env_n);
+    } else {
+        env_n = 0;
+    }
+    ShadeRecords r(materials, num_materials, false, paths, isects, outside, n);
+    const float *d_l = ne > 0 ? r.in(rec.data(), rec.size()) : nullptr;
+    const float4 *d_env = env_n > 0 ? (const float4 *)r.in(quad.data(), quad.size()) : nullptr;
+    const int32_t *d_hit = r.in(hit_geom, (size_t)n);
+    if (!r.ok()) return probe_no_device(who);
+    hipLaunchKernelGGL(k_probe_shade_scatter_direct, r.grid(), dim3(64), 0, 0, iter, depth, trace_depth, r.mats, d_l, ne, r.paths, r.isects, r.outside,
+                       d_hit, n, d_env, env_n);
+    return r.finish();
+}
+
+// ---- texture mapping (PT_TEXTURES; DESIGN.md section 6.19) ----
+// the primitives of a probe call as the lookups read them: inverseTransform as 12 words (4 columns x 3 rows) and the type
+void texture_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &inv, std::vector<int32_t> &type) {
+    inv.assign((size_t)std::max(1, num_geoms) * 12, 0.0f);
+    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
+    for (int g = 0; g < num_geoms; ++g) {
+        for (int c = 0; c < 4; ++c)
+            for (int r = 0; r < 3; ++r) inv[(size_t)g * 12 + c * 3 + r] = geoms[g].inverseTransform.m[c][r];
+        type[(size_t)g] = (int32_t)geoms[g].type;
+    }
+}
+// the refusals pt_texture_texel and pt_probe_texture share; 0 when the arguments are sound
+int texture_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n) {
+    if (count < 0 || num_geoms < 0 || n < 1 || n > 1024 || (num_geoms > 0 && !geoms) || (count > 0 && (!hit_geom || !points)))
+        return fail(PT_ERR_INVALID, "%s: bad argument (count %d, %d geoms, n %d)", who, count, num_geoms, n);
+    return probe_check_geoms(who, nullptr, hit_geom, count, num_geoms);
+}
+
+// ---- bump mapping (PT_TEXTURES; DESIGN.md section 6.22) ----
+// the primitives as ptd::bump_normal reads them: inverseTransform, transform, invTranspose, 12 words each, and the type
+void bump_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &rec, std::vector<int32_t> &type) {
+    rec.assign((size_t)std::max(1, num_geoms) * 36, 0.0f);
+    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
+    for (int g = 0; g < num_geoms; ++g) {
+        const pt_mat4 *ms[3] = {&geoms[g].inverseTransform, &geoms[g].transform, &geoms[g].invTranspose};
+        for (int m = 0; m < 3; ++m)
+            for (int c = 0; c < 4; ++c)
+                for (int r = 0; r < 3; ++r) rec[(size_t)g * 36 + m * 12 + c * 3 + r] = ms[m]->m[c][r];
+        type[(size_t)g] = (int32_t)geoms[g].type;
+    }
+}
+int bump_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals,
+              const float *dirs, int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
+    const int rc = texture_args(who, geoms, num_geoms, hit_geom, points, count, n);
+    if (rc) return rc;
+    if (!texels || (count > 0 && (!normals || !dirs || !out_normals || !perturbed)))
+        return fail(PT_ERR_INVALID, "%s: null array (count %d)", who, count);
+    return PT_OK;
+}
+
 }  // namespace
 
-namespace one {
-
+// ---- the entry points (include/ptmi355.h) ----
 int pt_probe_rng(const uint32_t *seeds, int n, int draws, uint32_t *state, float *u) {
     if (n < 0 || draws < 0 || (n > 0 && !seeds)) return fail(PT_ERR_INVALID, "pt_probe_rng: bad argument");
     if (n == 0) return PT_OK;
     ProbeBufs b;
-    uint32_t *d_seeds = (uint32_t *)b.get((size_t)n * 4, seeds);
-    uint32_t *d_state = (uint32_t *)b.get((size_t)n * 4, nullptr);
-    float *d_u = (float *)b.get((size_t)n * 4, nullptr);
-    if (!d_seeds || !d_state || !d_u) { (void)hipGetLastError(); return fail(PT_ERR_DEVICE, "pt_probe_rng: no HIP device / out of memory (this library has no CPU fallback)"); }
+    const uint32_t *d_seeds = b.in(seeds, (size_t)n);
+    uint32_t *d_state = b.out<uint32_t>((size_t)n);
+    float *d_u = b.out<float>((size_t)n);
+    if (!b.ok()) return probe_no_device("pt_probe_rng");
     hipLaunchKernelGGL(k_probe_rng, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_seeds, n, draws, d_state, d_u);
     HIPCHK(hipGetLastError());
-    if (state) HIPCHK(hipMemcpy(state, d_state, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (u) HIPCHK(hipMemcpy(u, d_u, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(state, d_state, (size_t)n));
+    HIPCHK(b.fetch(u, d_u, (size_t)n));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -383,17 +562,17 @@ int pt_probe_sincos(const float *x, uint32_t first_bits, uint32_t n, float *s, f
     // may sweep every binary32 value
     if ((x || s || c) && n > (1u << 28)) return fail(PT_ERR_INVALID, "pt_probe_sincos: %u elements with arrays (at most 2^28)", n);
     ProbeBufs b;
-    float *d_x = x ? (float *)b.get((size_t)n * 4, x) : nullptr;
-    float *d_s = s ? (float *)b.get((size_t)n * 4, nullptr) : nullptr;
-    float *d_c = c ? (float *)b.get((size_t)n * 4, nullptr) : nullptr;
-    unsigned long long *d_sum = (unsigned long long *)b.get(16, nullptr);
-    if ((x && !d_x) || (s && !d_s) || (c && !d_c) || !d_sum) { (void)hipGetLastError(); return fail(PT_ERR_DEVICE, "pt_probe_sincos: no HIP device / out of memory (this library has no CPU fallback)"); }
+    const float *d_x = b.in(x, (size_t)n);
+    float *d_s = s ? b.out<float>((size_t)n) : nullptr;
+    float *d_c = c ? b.out<float>((size_t)n) : nullptr;
+    unsigned long long *d_sum = b.out<unsigned long long>(2);
+    if (!b.ok()) return probe_no_device("pt_probe_sincos");
     const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_probe_sincos, dim3(blocks), dim3(256), 0, 0, d_x, first_bits, n, d_s, d_c, d_sum);
     HIPCHK(hipGetLastError());
-    if (s) HIPCHK(hipMemcpy(s, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (c) HIPCHK(hipMemcpy(c, d_c, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (sum) HIPCHK(hipMemcpy(sum, d_sum, 16, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(s, d_s, (size_t)n));
+    HIPCHK(b.fetch(c, d_c, (size_t)n));
+    HIPCHK(b.fetch((unsigned long long *)sum, d_sum, 2));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -403,12 +582,12 @@ int pt_probe_sqrt(uint32_t first_bits, uint32_t n, uint64_t mismatch[2]) {
     mismatch[0] = mismatch[1] = 0;
     if (n == 0) return PT_OK;
     ProbeBufs b;
-    unsigned long long *d_bad = (unsigned long long *)b.get(16, nullptr);
-    if (!d_bad) { (void)hipGetLastError(); return fail(PT_ERR_DEVICE, "pt_probe_sqrt: no HIP device / out of memory (this library has no CPU fallback)"); }
+    unsigned long long *d_bad = b.out<unsigned long long>(2);
+    if (!b.ok()) return probe_no_device("pt_probe_sqrt");
     const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 8192);
     hipLaunchKernelGGL(k_probe_sqrt, dim3(blocks), dim3(256), 0, 0, first_bits, n, d_bad);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(mismatch, d_bad, 16, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch((unsigned long long *)mismatch, d_bad, 2));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -449,44 +628,35 @@ int pt_probe_hemisphere(const float *normals, const uint32_t *seeds, int n, floa
     if (n < 0 || (n > 0 && (!normals || !seeds || !dirs))) return fail(PT_ERR_INVALID, "pt_probe_hemisphere: bad argument");
     if (n == 0) return PT_OK;
     ProbeBufs b;
-    float *d_n = (float *)b.get((size_t)n * 12, normals);
-    uint32_t *d_seeds = (uint32_t *)b.get((size_t)n * 4, seeds);
-    float *d_d = (float *)b.get((size_t)n * 12, nullptr);
-    if (!d_n || !d_seeds || !d_d) { (void)hipGetLastError(); return fail(PT_ERR_DEVICE, "pt_probe_hemisphere: no HIP device / out of memory (this library has no CPU fallback)"); }
+    const float *d_n = b.in(normals, 3 * (size_t)n);
+    const uint32_t *d_seeds = b.in(seeds, (size_t)n);
+    float *d_d = b.out<float>(3 * (size_t)n);
+    if (!b.ok()) return probe_no_device("pt_probe_hemisphere");
     hipLaunchKernelGGL(k_probe_hemisphere, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_n, d_seeds, n, d_d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dirs, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(dirs, d_d, 3 * (size_t)n));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
 
-// pt_probe_shade_scatter (glossy = false) and pt_probe_shade_scatter_glossy (true): `who` names the entry point in messages
-static int probe_shade_scatter(const char *who, bool glossy, int iter, int depth, const pt_material *materials, int num_materials,
-                               pt_path_segment *paths, const pt_shadeable_intersection *isects, const uint8_t *outside, int n, int deferred) {
-    // everything is refused here, before anything is launched: the kernel never indexes past the material table
-    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)))
-        return fail(PT_ERR_INVALID, "%s: bad argument", who);
-    for (int i = 0; i < n; ++i)
-        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
-            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
+int pt_glossy_alpha2(const float *exponents, int count, float *alpha2) {
+    if (count < 0 || (count > 0 && (!exponents || !alpha2))) return fail(PT_ERR_INVALID, "pt_glossy_alpha2: bad argument (count %d)", count);
+    for (int i = 0; i < count; ++i) alpha2[i] = one::glossy_alpha2(exponents[i]);      // pt_init's own function
+    return PT_OK;
+}
+
+int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const float *alpha2, int n, float *dirs) {
+    if (n < 0 || (n > 0 && (!normals || !seeds || !alpha2 || !dirs))) return fail(PT_ERR_INVALID, "pt_probe_glossy_lobe: bad argument");
     if (n == 0) return PT_OK;
-    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
-    pack_materials(materials, num_materials, mrec.data(), glossy);  // pt_init's own records
     ProbeBufs b;
-    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
-    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
-    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
-    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
-    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside)) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
-    }
-    if (glossy) hipLaunchKernelGGL(k_probe_shade_scatter<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths,
-                                   d_isects, d_outside, n, deferred);
-    else hipLaunchKernelGGL(k_probe_shade_scatter<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths,
-                            d_isects, d_outside, n, deferred);
+    const float *d_n = b.in(normals, 3 * (size_t)n);
+    const uint32_t *d_seeds = b.in(seeds, (size_t)n);
+    const float *d_a = b.in(alpha2, (size_t)n);
+    float *d_d = b.out<float>(3 * (size_t)n);
+    if (!b.ok()) return probe_no_device("pt_probe_glossy_lobe");
+    hipLaunchKernelGGL(k_probe_glossy_lobe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_n, d_seeds, d_a, n, d_d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(dirs, d_d, 3 * (size_t)n));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -502,18 +672,6 @@ int pt_probe_shade_scatter_glossy(int iter, int depth, const pt_material *materi
                                deferred);
 }
 
-// the light table of a probe call: pt_init's own functions; -1 with the message set
-static int probe_light_records(const char *who, const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials,
-                               std::vector<float> &rec) {
-    if (num_geoms < 0 || num_materials < 1 || !materials || (num_geoms > 0 && !geoms)) return fail(PT_ERR_INVALID, "%s: bad argument", who);
-    std::vector<pt_light_element> el;
-    const int ne = ptlight::elements(geoms, num_geoms, materials, num_materials, el);
-    if (ne < 0) return fail(PT_ERR_INVALID, "%s: a cube or sphere names a material outside [0, %d)", who, num_materials);
-    if (ne > ptlight::MAX_ELEMENTS) return fail(PT_ERR_INVALID, "%s: %d light elements (at most %d)", who, ne, ptlight::MAX_ELEMENTS);
-    ptlight::records(geoms, el, rec);
-    return ne;
-}
-
 int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_material *materials, int num_materials, const float *P,
                            const float *n, const uint32_t *seeds, int count, float *dir, float *weight, int32_t *element) {
     if (count < 0 || count > (1 << 26) || (count > 0 && (!P || !n || !seeds || !dir || !weight || !element)))
@@ -527,73 +685,19 @@ int pt_probe_direct_sample(const pt_geom *geoms, int num_geoms, const pt_materia
         return PT_OK;
     }
     ProbeBufs b;
-    const float *d_l = (const float *)b.get(rec.size() * 4, rec.data());
-    const float *d_p = (const float *)b.get((size_t)count * 12, P);
-    const float *d_n = (const float *)b.get((size_t)count * 12, n);
-    const uint32_t *d_s = (const uint32_t *)b.get((size_t)count * 4, seeds);
-    float *d_d = (float *)b.get((size_t)count * 12, nullptr);
-    float *d_w = (float *)b.get((size_t)count * 4, nullptr);
-    int32_t *d_e = (int32_t *)b.get((size_t)count * 4, nullptr);
-    if (!d_l || !d_p || !d_n || !d_s || !d_d || !d_w || !d_e) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_direct_sample: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const float *d_l = b.in(rec.data(), rec.size());
+    const float *d_p = b.in(P, 3 * (size_t)count);
+    const float *d_n = b.in(n, 3 * (size_t)count);
+    const uint32_t *d_s = b.in(seeds, (size_t)count);
+    float *d_d = b.out<float>(3 * (size_t)count);
+    float *d_w = b.out<float>((size_t)count);
+    int32_t *d_e = b.out<int32_t>((size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_direct_sample");
     hipLaunchKernelGGL(k_probe_direct_sample, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_l, ne, d_p, d_n, d_s, count, d_d, d_w, d_e);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dir, d_d, (size_t)count * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(weight, d_w, (size_t)count * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(element, d_e, (size_t)count * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipDeviceSynchronize());
-    return PT_OK;
-}
-
-// both direct forms of the shader probe: texels == nullptr -- the lamps' table; otherwise the table of a PT_DIRECT_SKY session
-// under the map (texels, env_n), as pt_set_environment makes it
-static int probe_shade_scatter_direct(const char *who, int iter, int depth, int trace_depth, const pt_geom *geoms, int num_geoms,
-                                      const pt_material *materials, int num_materials, pt_path_segment *paths,
-                                      const pt_shadeable_intersection *isects, const uint8_t *outside, const int32_t *hit_geom, int n,
-                                      const float *texels, int env_n) {
-    if (n < 0 || n > (1 << 26) || num_materials < 1 || trace_depth < 1 || trace_depth > MAX_DEPTH - 1 || depth < 0 || depth > trace_depth ||
-        (n > 0 && (!paths || !isects || !materials)) || (n > 0 && depth == trace_depth && !hit_geom))
-        return fail(PT_ERR_INVALID, "%s: bad argument", who);
-    for (int i = 0; i < n; ++i)
-        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
-            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
-    std::vector<float> rec;
-    int ne = probe_light_records(who, geoms, num_geoms, materials, num_materials, rec);
-    if (ne < 0) return ne;
-    if (n == 0) return PT_OK;
-    std::vector<float> quad;
-    if (texels && env_n > 0) {
-        std::vector<float> rows, cols, all;
-        if (ptlight::sky_table(texels, env_n, rows, cols)) {
-            ne = ptlight::sky_records(rec, env_n, rows, cols, all);
-            rec.swap(all);
-        }
-        const size_t count = (size_t)6 * (size_t)env_n * (size_t)env_n;
-        quad.assign(count * 4, 0.0f);
-        for (size_t k = 0; k < count; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
-    } else {
-        env_n = 0;
-    }
-    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
-    pack_materials(materials, num_materials, mrec.data(), false);
-    ProbeBufs b;
-    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
-    const float *d_l = ne > 0 ? (const float *)b.get(rec.size() * 4, rec.data()) : nullptr;
-    const float4 *d_env = env_n > 0 ? (const float4 *)b.get(quad.size() * 4, quad.data()) : nullptr;
-    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
-    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
-    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
-    const int32_t *d_hit = hit_geom ? (const int32_t *)b.get((size_t)n * 4, hit_geom) : nullptr;
-    if (!d_mats || (ne > 0 && !d_l) || (env_n > 0 && !d_env) || !d_paths || !d_isects || (outside && !d_outside) || (hit_geom && !d_hit)) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
-    }
-    hipLaunchKernelGGL(k_probe_shade_scatter_direct, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, trace_depth, d_mats, d_l, ne,
-                       d_paths, d_isects, d_outside, d_hit, n, d_env, env_n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(dir, d_d, 3 * (size_t)count));
+    HIPCHK(b.fetch(weight, d_w, (size_t)count));
+    HIPCHK(b.fetch(element, d_e, (size_t)count));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -626,43 +730,19 @@ int pt_probe_sky_sample(const float *texels, int n, const float *normals, const 
     }
     const int ne = ptlight::sky_records(std::vector<float>(), n, rows, cols, rec);
     ProbeBufs b;
-    const float *d_l = (const float *)b.get(rec.size() * 4, rec.data());
-    const float *d_n = (const float *)b.get((size_t)count * 12, normals);
-    const uint32_t *d_s = (const uint32_t *)b.get((size_t)count * 4, seeds);
-    float *d_d = (float *)b.get((size_t)count * 12, nullptr);
-    float *d_w = (float *)b.get((size_t)count * 4, nullptr);
-    int32_t *d_t = (int32_t *)b.get((size_t)count * 4, nullptr);
-    if (!d_l || !d_n || !d_s || !d_d || !d_w || !d_t) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_sky_sample: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const float *d_l = b.in(rec.data(), rec.size());
+    const float *d_n = b.in(normals, 3 * (size_t)count);
+    const uint32_t *d_s = b.in(seeds, (size_t)count);
+    float *d_d = b.out<float>(3 * (size_t)count);
+    float *d_w = b.out<float>((size_t)count);
+    int32_t *d_t = b.out<int32_t>((size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_sky_sample");
     hipLaunchKernelGGL(k_probe_sky_sample, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_l, ne, d_n, d_s, count, d_d, d_w, d_t);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dir, d_d, (size_t)count * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(weight, d_w, (size_t)count * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(texel, d_t, (size_t)count * 4, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(dir, d_d, 3 * (size_t)count));
+    HIPCHK(b.fetch(weight, d_w, (size_t)count));
+    HIPCHK(b.fetch(texel, d_t, (size_t)count));
     HIPCHK(hipDeviceSynchronize());
-    return PT_OK;
-}
-
-// ---- texture mapping (PT_TEXTURES; DESIGN.md section 6.19) ----
-// the primitives of a probe call as the lookups read them: inverseTransform as 12 words (4 columns x 3 rows) and the type
-static void texture_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &inv, std::vector<int32_t> &type) {
-    inv.assign((size_t)std::max(1, num_geoms) * 12, 0.0f);
-    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
-    for (int g = 0; g < num_geoms; ++g) {
-        for (int c = 0; c < 4; ++c)
-            for (int r = 0; r < 3; ++r) inv[(size_t)g * 12 + c * 3 + r] = geoms[g].inverseTransform.m[c][r];
-        type[(size_t)g] = (int32_t)geoms[g].type;
-    }
-}
-// the refusals pt_texture_texel and pt_probe_texture share; 0 when the arguments are sound
-static int texture_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, int count, int n) {
-    if (count < 0 || num_geoms < 0 || n < 1 || n > 1024 || (num_geoms > 0 && !geoms) || (count > 0 && (!hit_geom || !points)))
-        return fail(PT_ERR_INVALID, "%s: bad argument (count %d, %d geoms, n %d)", who, count, num_geoms, n);
-    for (int i = 0; i < count; ++i)
-        if (hit_geom[i] < 0 || hit_geom[i] >= num_geoms)
-            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
     return PT_OK;
 }
 
@@ -691,24 +771,19 @@ int pt_probe_texture(const pt_geom *geoms, int num_geoms, const int32_t *hit_geo
     std::vector<float> inv;
     std::vector<int32_t> type;
     texture_geoms(geoms, num_geoms, inv, type);
-    const size_t nt = (size_t)6 * (size_t)n * (size_t)n;
-    std::vector<float> quad(nt * 4, 0.0f);                         // the session's device layout: {r, g, b, 0}
-    for (size_t k = 0; k < nt; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    const std::vector<float> quad = rgb_quads(texels, (size_t)6 * (size_t)n * (size_t)n);
     ProbeBufs b;
-    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
-    const float *d_inv = (const float *)b.get(inv.size() * 4, inv.data());
-    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
-    const int32_t *d_hit = (const int32_t *)b.get((size_t)count * 4, hit_geom);
-    const float *d_pts = (const float *)b.get((size_t)count * 12, points);
-    const float *d_in = (const float *)b.get((size_t)count * 12, colour_in);
-    float *d_out = (float *)b.get((size_t)count * 12, nullptr);
-    if (!d_tex || !d_inv || !d_type || !d_hit || !d_pts || !d_in || !d_out) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_texture: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const float4 *d_tex = (const float4 *)b.in(quad.data(), quad.size());
+    const float *d_inv = b.in(inv.data(), inv.size());
+    const int32_t *d_type = b.in(type.data(), type.size());
+    const int32_t *d_hit = b.in(hit_geom, (size_t)count);
+    const float *d_pts = b.in(points, 3 * (size_t)count);
+    const float *d_in = b.in(colour_in, 3 * (size_t)count);
+    float *d_out = b.out<float>(3 * (size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_texture");
     hipLaunchKernelGGL(k_probe_texture, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_inv, d_type, d_hit, d_pts, count, d_tex, n, d_in, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(colour_out, d_out, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(colour_out, d_out, 3 * (size_t)count));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -718,81 +793,32 @@ int pt_probe_shade_scatter_textured(int iter, int depth, const pt_material *mate
                                     const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
                                     const int32_t *tex_n, const int32_t *tex_offset) {
     const char *who = "pt_probe_shade_scatter_textured";
-    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)) ||
-        num_geoms < 0 || (num_geoms > 0 && !geoms) || (n > 0 && !hit_geom) || !tex_n || !tex_offset)
+    if (probe_shade_args_bad(n, num_materials, deferred, paths, isects, materials) || num_geoms < 0 || (num_geoms > 0 && !geoms) ||
+        (n > 0 && !hit_geom) || !tex_n || !tex_offset)
         return fail(PT_ERR_INVALID, "%s: bad argument", who);
-    for (int i = 0; i < n; ++i) {
-        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
-            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
-        if (isects[i].t > 0.0f && (hit_geom[i] < 0 || hit_geom[i] >= num_geoms))
-            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
-    }
+    std::vector<int2> tab;
     size_t total = 0;                                              // texels the table reaches
-    for (int m = 0; m < num_materials; ++m) {
-        if (tex_n[m] < 0 || tex_n[m] > 1024 || (tex_n[m] > 0 && tex_offset[m] < 0))
-            return fail(PT_ERR_INVALID, "%s: material %d has a texture of n = %d at offset %d", who, m, tex_n[m], tex_offset[m]);
-        if (tex_n[m] > 0) total = std::max(total, (size_t)tex_offset[m] + (size_t)6 * (size_t)tex_n[m] * (size_t)tex_n[m]);
-    }
+    int rc = probe_check_materials(who, isects, n, num_materials);
+    if (!rc) rc = probe_check_geoms(who, isects, hit_geom, n, num_geoms);
+    if (!rc) rc = probe_cube_table(who, "texture", num_materials, tex_n, tex_offset, tab, total);
+    if (rc) return rc;
     if (total > 0 && !tex_texels) return fail(PT_ERR_INVALID, "%s: null tex_texels", who);
     if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "%s: %zu texels in all (at most 2^31 - 1)", who, total);
     if (n == 0) return PT_OK;
-    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
-    pack_materials(materials, num_materials, mrec.data(), false);
     std::vector<float> inv;
     std::vector<int32_t> type;
     texture_geoms(geoms, num_geoms, inv, type);
-    std::vector<float> quad(std::max<size_t>(total, 1) * 4, 0.0f);
-    for (size_t k = 0; k < total; ++k) { quad[4 * k] = tex_texels[3 * k]; quad[4 * k + 1] = tex_texels[3 * k + 1]; quad[4 * k + 2] = tex_texels[3 * k + 2]; }
-    std::vector<int2> tab((size_t)num_materials);
-    for (int m = 0; m < num_materials; ++m) tab[(size_t)m] = make_int2(tex_n[m] > 0 ? tex_offset[m] : 0, tex_n[m]);
-    ProbeBufs b;
-    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
-    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
-    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
-    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
-    const float *d_inv = (const float *)b.get(inv.size() * 4, inv.data());
-    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
-    const int32_t *d_hit = (const int32_t *)b.get((size_t)n * 4, hit_geom);
-    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
-    const int2 *d_tab = (const int2 *)b.get(tab.size() * sizeof(int2), tab.data());
-    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside) || !d_inv || !d_type || !d_hit || !d_tex || !d_tab) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
-    }
-    hipLaunchKernelGGL(k_probe_shade_scatter_textured, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
-                       d_outside, n, deferred, d_inv, d_type, d_hit, d_tex, d_tab);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
-    HIPCHK(hipDeviceSynchronize());
-    return PT_OK;
-}
-
-// ---- bump mapping (PT_TEXTURES; DESIGN.md section 6.22) ----
-// the primitives as ptd::bump_normal reads them: inverseTransform, transform, invTranspose, 12 words each, and the type
-static void bump_geoms(const pt_geom *geoms, int num_geoms, std::vector<float> &rec, std::vector<int32_t> &type) {
-    rec.assign((size_t)std::max(1, num_geoms) * 36, 0.0f);
-    type.assign((size_t)std::max(1, num_geoms), (int32_t)PT_TRIANGLE_MESH);
-    for (int g = 0; g < num_geoms; ++g) {
-        const pt_mat4 *ms[3] = {&geoms[g].inverseTransform, &geoms[g].transform, &geoms[g].invTranspose};
-        for (int m = 0; m < 3; ++m)
-            for (int c = 0; c < 4; ++c)
-                for (int r = 0; r < 3; ++r) rec[(size_t)g * 36 + m * 12 + c * 3 + r] = ms[m]->m[c][r];
-        type[(size_t)g] = (int32_t)geoms[g].type;
-    }
-}
-// {da, db} of `count` RGB texels
-static std::vector<float> bump_pairs(const float *texels, size_t count) {
-    std::vector<float> pair(std::max<size_t>(count, 1) * 2, 0.0f);
-    for (size_t k = 0; k < count; ++k) { pair[2 * k] = texels[3 * k]; pair[2 * k + 1] = texels[3 * k + 1]; }
-    return pair;
-}
-static int bump_args(const char *who, const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals,
-                     const float *dirs, int count, const float *texels, int n, float *out_normals, uint8_t *perturbed) {
-    const int rc = texture_args(who, geoms, num_geoms, hit_geom, points, count, n);
-    if (rc) return rc;
-    if (!texels || (count > 0 && (!normals || !dirs || !out_normals || !perturbed)))
-        return fail(PT_ERR_INVALID, "%s: null array (count %d)", who, count);
-    return PT_OK;
+    const std::vector<float> quad = rgb_quads(tex_texels, total);
+    ShadeRecords r(materials, num_materials, false, paths, isects, outside, n);
+    const float *d_inv = r.in(inv.data(), inv.size());
+    const int32_t *d_type = r.in(type.data(), type.size());
+    const int32_t *d_hit = r.in(hit_geom, (size_t)n);
+    const float4 *d_tex = (const float4 *)r.in(quad.data(), quad.size());
+    const int2 *d_tab = r.in(tab.data(), tab.size());
+    if (!r.ok()) return probe_no_device(who);
+    hipLaunchKernelGGL(k_probe_shade_scatter_textured, r.grid(), dim3(64), 0, 0, iter, depth, r.mats, r.paths, r.isects, r.outside, n, deferred,
+                       d_inv, d_type, d_hit, d_tex, d_tab);
+    return r.finish();
 }
 
 int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
@@ -827,24 +853,21 @@ int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit
     bump_geoms(geoms, num_geoms, rec, type);
     const std::vector<float> pair = bump_pairs(texels, (size_t)6 * (size_t)n * (size_t)n);
     ProbeBufs b;
-    const ptd::bump_texel *d_tex = (const ptd::bump_texel *)b.get(pair.size() * 4, pair.data());
-    const float *d_rec = (const float *)b.get(rec.size() * 4, rec.data());
-    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
-    const int32_t *d_hit = (const int32_t *)b.get((size_t)count * 4, hit_geom);
-    const float *d_pts = (const float *)b.get((size_t)count * 12, points);
-    const float *d_nrm = (const float *)b.get((size_t)count * 12, normals);
-    const float *d_dir = (const float *)b.get((size_t)count * 12, dirs);
-    float *d_out = (float *)b.get((size_t)count * 12, nullptr);
-    uint8_t *d_flag = (uint8_t *)b.get((size_t)count, nullptr);
-    if (!d_tex || !d_rec || !d_type || !d_hit || !d_pts || !d_nrm || !d_dir || !d_out || !d_flag) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_bump_normal: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const ptd::bump_texel *d_tex = (const ptd::bump_texel *)b.in(pair.data(), pair.size());
+    const float *d_rec = b.in(rec.data(), rec.size());
+    const int32_t *d_type = b.in(type.data(), type.size());
+    const int32_t *d_hit = b.in(hit_geom, (size_t)count);
+    const float *d_pts = b.in(points, 3 * (size_t)count);
+    const float *d_nrm = b.in(normals, 3 * (size_t)count);
+    const float *d_dir = b.in(dirs, 3 * (size_t)count);
+    float *d_out = b.out<float>(3 * (size_t)count);
+    uint8_t *d_flag = b.out<uint8_t>((size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_bump_normal");
     hipLaunchKernelGGL(k_probe_bump_normal, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_rec, d_type, d_hit, d_pts, d_nrm, d_dir, count,
                        d_tex, n, d_out, d_flag);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out_normals, d_out, (size_t)count * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(perturbed, d_flag, (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(out_normals, d_out, 3 * (size_t)count));
+    HIPCHK(b.fetch(perturbed, d_flag, (size_t)count));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -855,84 +878,35 @@ int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materi
                                   const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
                                   const int32_t *bump_offset) {
     const char *who = "pt_probe_shade_scatter_bumped";
-    if (n < 0 || n > (1 << 26) || num_materials < 1 || (deferred != 0 && deferred != 1) || (n > 0 && (!paths || !isects || !materials)) ||
-        num_geoms < 0 || (num_geoms > 0 && !geoms) || (n > 0 && !hit_geom) || !tex_n || !tex_offset || !bump_n || !bump_offset)
+    if (probe_shade_args_bad(n, num_materials, deferred, paths, isects, materials) || num_geoms < 0 || (num_geoms > 0 && !geoms) ||
+        (n > 0 && !hit_geom) || !tex_n || !tex_offset || !bump_n || !bump_offset)
         return fail(PT_ERR_INVALID, "%s: bad argument", who);
-    for (int i = 0; i < n; ++i) {
-        if (isects[i].t > 0.0f && (isects[i].materialId < 0 || isects[i].materialId >= num_materials))
-            return fail(PT_ERR_INVALID, "%s: record %d hits material %d of %d", who, i, isects[i].materialId, num_materials);
-        if (isects[i].t > 0.0f && (hit_geom[i] < 0 || hit_geom[i] >= num_geoms))
-            return fail(PT_ERR_INVALID, "%s: record %d names primitive %d of %d", who, i, hit_geom[i], num_geoms);
-    }
+    std::vector<int2> tab, btab;
     size_t total = 0, btotal = 0;                                  // texels the two tables reach
-    for (int m = 0; m < num_materials; ++m) {
-        if (tex_n[m] < 0 || tex_n[m] > 1024 || (tex_n[m] > 0 && tex_offset[m] < 0))
-            return fail(PT_ERR_INVALID, "%s: material %d has a texture of n = %d at offset %d", who, m, tex_n[m], tex_offset[m]);
-        if (bump_n[m] < 0 || bump_n[m] > 1024 || (bump_n[m] > 0 && bump_offset[m] < 0))
-            return fail(PT_ERR_INVALID, "%s: material %d has a bump map of n = %d at offset %d", who, m, bump_n[m], bump_offset[m]);
-        if (tex_n[m] > 0) total = std::max(total, (size_t)tex_offset[m] + (size_t)6 * (size_t)tex_n[m] * (size_t)tex_n[m]);
-        if (bump_n[m] > 0) btotal = std::max(btotal, (size_t)bump_offset[m] + (size_t)6 * (size_t)bump_n[m] * (size_t)bump_n[m]);
-    }
+    int rc = probe_check_materials(who, isects, n, num_materials);
+    if (!rc) rc = probe_check_geoms(who, isects, hit_geom, n, num_geoms);
+    if (!rc) rc = probe_cube_table(who, "texture", num_materials, tex_n, tex_offset, tab, total);
+    if (!rc) rc = probe_cube_table(who, "bump map", num_materials, bump_n, bump_offset, btab, btotal);
+    if (rc) return rc;
     if ((total > 0 && !tex_texels) || (btotal > 0 && !bump_texels)) return fail(PT_ERR_INVALID, "%s: null texels", who);
     if (total > (size_t)0x7fffffff || btotal > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "%s: %zu texels in all (at most 2^31 - 1)", who, std::max(total, btotal));
     if (n == 0) return PT_OK;
-    std::vector<float> mrec((size_t)num_materials * ptd::MAT_WORDS, 0.0f);
-    pack_materials(materials, num_materials, mrec.data(), false);
     std::vector<float> rec;
     std::vector<int32_t> type;
     bump_geoms(geoms, num_geoms, rec, type);
-    std::vector<float> quad(std::max<size_t>(total, 1) * 4, 0.0f);
-    for (size_t k = 0; k < total; ++k) { quad[4 * k] = tex_texels[3 * k]; quad[4 * k + 1] = tex_texels[3 * k + 1]; quad[4 * k + 2] = tex_texels[3 * k + 2]; }
-    const std::vector<float> pair = bump_pairs(bump_texels, btotal);
-    std::vector<int2> tab((size_t)num_materials), btab((size_t)num_materials);
-    for (int m = 0; m < num_materials; ++m) {
-        tab[(size_t)m] = make_int2(tex_n[m] > 0 ? tex_offset[m] : 0, tex_n[m]);
-        btab[(size_t)m] = make_int2(bump_n[m] > 0 ? bump_offset[m] : 0, bump_n[m]);
-    }
-    ProbeBufs b;
-    const float *d_mats = (const float *)b.get(mrec.size() * 4, mrec.data());
-    pt_path_segment *d_paths = (pt_path_segment *)b.get((size_t)n * sizeof(pt_path_segment), paths);
-    const pt_shadeable_intersection *d_isects = (const pt_shadeable_intersection *)b.get((size_t)n * sizeof(pt_shadeable_intersection), isects);
-    const uint8_t *d_outside = outside ? (const uint8_t *)b.get((size_t)n, outside) : nullptr;
-    const float *d_rec = (const float *)b.get(rec.size() * 4, rec.data());
-    const int32_t *d_type = (const int32_t *)b.get(type.size() * 4, type.data());
-    const int32_t *d_hit = (const int32_t *)b.get((size_t)n * 4, hit_geom);
-    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
-    const int2 *d_tab = (const int2 *)b.get(tab.size() * sizeof(int2), tab.data());
-    const ptd::bump_texel *d_bump = (const ptd::bump_texel *)b.get(pair.size() * 4, pair.data());
-    const int2 *d_btab = (const int2 *)b.get(btab.size() * sizeof(int2), btab.data());
-    if (!d_mats || !d_paths || !d_isects || (outside && !d_outside) || !d_rec || !d_type || !d_hit || !d_tex || !d_tab || !d_bump || !d_btab) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "%s: no HIP device / out of memory (this library has no CPU fallback)", who);
-    }
-    hipLaunchKernelGGL(k_probe_shade_scatter_bumped, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, iter, depth, d_mats, d_paths, d_isects,
-                       d_outside, n, deferred, d_rec, d_type, d_hit, d_tex, d_tab, d_bump, d_btab);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(paths, d_paths, (size_t)n * sizeof(pt_path_segment), hipMemcpyDeviceToHost));
-    HIPCHK(hipDeviceSynchronize());
-    return PT_OK;
-}
-
-int pt_glossy_alpha2(const float *exponents, int count, float *alpha2) {
-    if (count < 0 || (count > 0 && (!exponents || !alpha2))) return fail(PT_ERR_INVALID, "pt_glossy_alpha2: bad argument (count %d)", count);
-    for (int i = 0; i < count; ++i) alpha2[i] = glossy_alpha2(exponents[i]);      // pt_init's own function
-    return PT_OK;
-}
-
-int pt_probe_glossy_lobe(const float *normals, const uint32_t *seeds, const float *alpha2, int n, float *dirs) {
-    if (n < 0 || (n > 0 && (!normals || !seeds || !alpha2 || !dirs))) return fail(PT_ERR_INVALID, "pt_probe_glossy_lobe: bad argument");
-    if (n == 0) return PT_OK;
-    ProbeBufs b;
-    float *d_n = (float *)b.get((size_t)n * 12, normals);
-    uint32_t *d_seeds = (uint32_t *)b.get((size_t)n * 4, seeds);
-    float *d_a = (float *)b.get((size_t)n * 4, alpha2);
-    float *d_d = (float *)b.get((size_t)n * 12, nullptr);
-    if (!d_n || !d_seeds || !d_a || !d_d) { (void)hipGetLastError(); return fail(PT_ERR_DEVICE, "pt_probe_glossy_lobe: no HIP device / out of memory (this library has no CPU fallback)"); }
-    hipLaunchKernelGGL(k_probe_glossy_lobe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_n, d_seeds, d_a, n, d_d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dirs, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipDeviceSynchronize());
-    return PT_OK;
+    const std::vector<float> quad = rgb_quads(tex_texels, total), pair = bump_pairs(bump_texels, btotal);
+    ShadeRecords r(materials, num_materials, false, paths, isects, outside, n);
+    const float *d_rec = r.in(rec.data(), rec.size());
+    const int32_t *d_type = r.in(type.data(), type.size());
+    const int32_t *d_hit = r.in(hit_geom, (size_t)n);
+    const float4 *d_tex = (const float4 *)r.in(quad.data(), quad.size());
+    const int2 *d_tab = r.in(tab.data(), tab.size());
+    const ptd::bump_texel *d_bump = (const ptd::bump_texel *)r.in(pair.data(), pair.size());
+    const int2 *d_btab = r.in(btab.data(), btab.size());
+    if (!r.ok()) return probe_no_device(who);
+    hipLaunchKernelGGL(k_probe_shade_scatter_bumped, r.grid(), dim3(64), 0, 0, iter, depth, r.mats, r.paths, r.isects, r.outside, n, deferred,
+                       d_rec, d_type, d_hit, d_tex, d_tab, d_bump, d_btab);
+    return r.finish();
 }
 
 int pt_environment_texel(const float *dirs, int count, int n, int32_t *index) {
@@ -946,21 +920,16 @@ int pt_probe_environment(const float *texels, int n, const float *dirs, const fl
     if (count < 0 || n < 0 || n > 1024 || (n > 0 && !texels) || (count > 0 && (!dirs || !throughput || !colour)))
         return fail(PT_ERR_INVALID, "pt_probe_environment: bad argument (count %d, n %d)", count, n);
     if (count == 0) return PT_OK;
-    const size_t nt = (size_t)6 * (size_t)n * (size_t)n;
-    std::vector<float> quad(std::max<size_t>(nt, 1) * 4, 0.0f);          // the session's device layout: {r, g, b, 0}
-    for (size_t k = 0; k < nt; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
+    const std::vector<float> quad = rgb_quads(texels, (size_t)6 * (size_t)n * (size_t)n);
     ProbeBufs b;
-    const float4 *d_tex = (const float4 *)b.get(quad.size() * 4, quad.data());
-    const float *d_dirs = (const float *)b.get((size_t)count * 12, dirs);
-    const float *d_thr = (const float *)b.get((size_t)count * 12, throughput);
-    float *d_col = (float *)b.get((size_t)count * 12, nullptr);
-    if (!d_tex || !d_dirs || !d_thr || !d_col) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_environment: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const float4 *d_tex = (const float4 *)b.in(quad.data(), quad.size());
+    const float *d_dirs = b.in(dirs, 3 * (size_t)count);
+    const float *d_thr = b.in(throughput, 3 * (size_t)count);
+    float *d_col = b.out<float>(3 * (size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_environment");
     hipLaunchKernelGGL(k_probe_environment, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_tex, n, d_dirs, d_thr, count, d_col);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(colour, d_col, (size_t)count * 12, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch(colour, d_col, 3 * (size_t)count));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }
@@ -974,27 +943,22 @@ int pt_probe_tri_form(const pt_triangle *triangles, int count, float origin_boun
     if (count == 0 || n == 0) return n64;
     std::vector<uint16_t> recs((size_t)n64 * 32);
     float frame[4];
-    const int got = one::pt_tri_records(triangles, count, origin_bound, recs.data(), frame);   // upload_tri_bounds' own calls
+    const int got = pt_tri_records(triangles, count, origin_bound, recs.data(), frame);   // upload_tri_bounds' own calls
     if (got != n64) return got < 0 ? got : fail(PT_ERR_INTERNAL, "pt_probe_tri_form: %d records, expected %d", got, n64);
     ProbeBufs b;
-    const pt_half8 *d_rec = (const pt_half8 *)b.get(recs.size() * 2, recs.data());
-    const float *d_o = (const float *)b.get((size_t)n * 12, origins);
-    const float *d_d = (const float *)b.get((size_t)n * 12, directions);
-    _Float16 *d_slots = ray_slots ? (_Float16 *)b.get((size_t)n * 64, nullptr) : nullptr;
-    int32_t *d_cls = ray_class ? (int32_t *)b.get((size_t)n * 4, nullptr) : nullptr;
-    float *d_form = form ? (float *)b.get((size_t)n * n64 * 4, nullptr) : nullptr;
-    if (!d_rec || !d_o || !d_d || (ray_slots && !d_slots) || (ray_class && !d_cls) || (form && !d_form)) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_DEVICE, "pt_probe_tri_form: no HIP device / out of memory (this library has no CPU fallback)");
-    }
+    const pt_half8 *d_rec = (const pt_half8 *)b.in(recs.data(), recs.size());
+    const float *d_o = b.in(origins, 3 * (size_t)n);
+    const float *d_d = b.in(directions, 3 * (size_t)n);
+    _Float16 *d_slots = ray_slots ? b.out<_Float16>(32 * (size_t)n) : nullptr;
+    int32_t *d_cls = ray_class ? b.out<int32_t>((size_t)n) : nullptr;
+    float *d_form = form ? b.out<float>((size_t)n * n64) : nullptr;
+    if (!b.ok()) return probe_no_device("pt_probe_tri_form");
     hipLaunchKernelGGL(k_probe_tri_form, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, d_rec, n64, frame[0], frame[1], frame[2], frame[3],
                        origin_bound, d_o, d_d, n, d_slots, d_cls, d_form);
     HIPCHK(hipGetLastError());
-    if (ray_slots) HIPCHK(hipMemcpy(ray_slots, d_slots, (size_t)n * 64, hipMemcpyDeviceToHost));
-    if (ray_class) HIPCHK(hipMemcpy(ray_class, d_cls, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (form) HIPCHK(hipMemcpy(form, d_form, (size_t)n * n64 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(b.fetch((_Float16 *)ray_slots, d_slots, 32 * (size_t)n));
+    HIPCHK(b.fetch(ray_class, d_cls, (size_t)n));
+    HIPCHK(b.fetch(form, d_form, (size_t)n * n64));
     HIPCHK(hipDeviceSynchronize());
     return n64;
 }
-
-}  // namespace one
