@@ -32,6 +32,8 @@ void pt_free(void) {
     if (R.isect_mem) (void)hipFree(R.isect_mem);
     if (R.sort_table) (void)hipFree(R.sort_table);
     if (R.cache_mem) (void)hipFree(R.cache_mem);
+    if (R.state_mem) (void)hipFree(R.state_mem);
+    if (R.state_ended) (void)hipFree(R.state_ended);
     if (R.final_mem) (void)hipFree(R.final_mem);
     if (R.image && R.own_image) (void)hipFree(R.image);
     if (R.d_geoms) (void)hipFree(R.d_geoms);
@@ -224,6 +226,8 @@ static int init_impl(const pt_scene_desc *d) {
     if (const char *e = pt_experiment("PTMI355_FIRST_HIT")) R.first_hit_enabled = atoi(e) != 0;
     R.first_two_enabled = true;
     if (const char *e = pt_experiment("PTMI355_FIRST_TWO")) R.first_two_enabled = atoi(e) != 0;
+    R.first_state_enabled = true;
+    if (const char *e = pt_experiment("PTMI355_FIRST_STATE")) R.first_state_enabled = atoi(e) != 0;
     R.host_sparse_enabled = (d->flags & (PT_HOST_SPARSE | PT_SHARED_IMAGE)) != 0;
     if (const char *e = pt_experiment("PTMI355_ASYNC_DIRECT")) R.async_direct_enabled = atoi(e) != 0;
     R.pin_enabled = true;
@@ -491,7 +495,11 @@ static int init_impl(const pt_scene_desc *d) {
             // (... and the launch that does bounces 0 and 1, with and without the own-surface form)
             const void *fns_two[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true, true) : fns[0],
                                       own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true, true) : fns[0]};
-            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3], fns_two[0], fns_two[1]}) {
+            // (... and its first-state form)
+            const void *fns_state[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true, true, true) : fns[0],
+                                        own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true, true, true) : fns[0]};
+            for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3], fns_two[0], fns_two[1],
+                                  fns_state[0], fns_state[1]}) {
                 int n = 0;
                 HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BLOCK, R.lds_bytes));
                 per_cu = std::min(per_cu, n);
@@ -559,6 +567,16 @@ static int init_impl(const pt_scene_desc *d) {
         // the plain fused pipeline reads bounce 0 from the first-hit table whenever its camera rays repeat (enqueue_bounce).
         // The table is an optimisation: a session that cannot have one traces bounce 0 as before.
         if (hipMalloc(&R.cache_mem, (size_t)R.map.tile_pixels * Isect::FIRST_HIT_BYTES) != hipSuccess) { (void)hipGetLastError(); R.cache_mem = nullptr; }
+        // ... and, where bounce 0's shading is fixed per pixel up to the diffuse draw, the first-state table beside it (DESIGN.md
+        // section 6.25): no lobes and no dielectric, whose Fresnel choice draws from the sample's engine (the shader's own test
+        // on the record's word).  An optimisation too: without it the launch of bounces 0 and 1 shades per sample as before.
+        bool fixed0 = R.cache_mem != nullptr && R.first_state_enabled && !(R.flags & PT_GLOSSY);
+        for (int m = 0; m < d->num_materials; ++m) fixed0 = fixed0 && !(d->materials[m].hasRefractive > 0.0f);
+        if (fixed0) {
+            if (hipMalloc(&R.state_mem, first_state_bytes((size_t)R.map.tile_pixels)) != hipSuccess) { (void)hipGetLastError(); R.state_mem = nullptr; }
+            if (R.state_mem && R.map.tile_pixels % TILE == 0 &&
+                hipMalloc((void **)&R.state_ended, (size_t)(R.map.tile_pixels / TILE) * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); R.state_ended = nullptr; }
+        }
     }
     if ((R.flags & PT_SORT_MATERIAL) && !R.sort_keys) {
         if (d->num_materials + 1 > SORT_MAX_BINS)

@@ -131,11 +131,16 @@ void launch_intersect(const Pool &in, const uint32_t *n_ptr, uint32_t n_fixed, c
 // `table`: the table form of bounce 0 (MODE_CACHE0; enqueue_bounce) of a session without mesh or material keys -- it has the
 // ENV and GLOSSY variants only, so SH's other bits do not apply
 // `first2` (with `table`): the launch that does bounces 0 and 1 (MODE_FIRST2; enqueue_bounce) -- it always generates its paths
+// `state2` (with `first2`): its first-state form (MODE_STATE2), which has the one variant SH == 0
 template <int MESH, int SH = 0>
-const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool table = false, bool first2 = false) {
+const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool table = false, bool first2 = false, bool state2 = false) {
     if constexpr (MESH == MESH_NONE) {
         if (table && !sorted) {
             constexpr int SH0 = SH & (SH_ENV | SH_GLOSSY);
+            if (first2 && state2) {
+                if (own) return slds ? (const void *)k_bounce<MODE_STATE2, true, MESH, true, true, false, true, 0> : (const void *)k_bounce<MODE_STATE2, true, MESH, false, true, false, true, 0>;
+                return slds ? (const void *)k_bounce<MODE_STATE2, true, MESH, true, true, false, false, 0> : (const void *)k_bounce<MODE_STATE2, true, MESH, false, true, false, false, 0>;
+            }
             if (first2) {
                 if (own) return slds ? (const void *)k_bounce<MODE_FIRST2, true, MESH, true, true, false, true, SH0> : (const void *)k_bounce<MODE_FIRST2, true, MESH, false, true, false, true, SH0>;
                 return slds ? (const void *)k_bounce<MODE_FIRST2, true, MESH, true, true, false, false, SH0> : (const void *)k_bounce<MODE_FIRST2, true, MESH, false, true, false, false, SH0>;
@@ -181,19 +186,24 @@ const void *bounce_fn(bool slds, bool gen, bool sorted, bool own = false, bool t
 // with the same arguments (last_bounce is false there and the camera's engine slot is D either way).
 template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN, bool SORT = false, bool OWN = false>
 void launch_k_bounce(const BounceArgs &a) {
-    if constexpr (MODE == MODE_FUSED) {
-        if (a.nlights > 0 && a.depth >= a.trace_depth - 1) {
-            PT_SHADE_DISPATCH_WITH(SH_DIRECT, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
-            return;
+    if constexpr (MODE == MODE_STATE2) {                        // one shading variant: enqueue_bounce takes it for SH == 0 only
+        hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, 0>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a);
+        return;
+    } else {
+        if constexpr (MODE == MODE_FUSED) {
+            if (a.nlights > 0 && a.depth >= a.trace_depth - 1) {
+                PT_SHADE_DISPATCH_WITH(SH_DIRECT, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
+                return;
+            }
+            // PT_TEXTURES: while the session has a texture set, every bounce launches the TEX forms;
+            // a flagged session without one launches what a session without the flag does (bounce_args leaves tex_tab null)
+            if (a.tex_tab != nullptr) {
+                PT_SHADE_DISPATCH_WITH(SH_TEX, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
+                return;
+            }
         }
-        // PT_TEXTURES: while the session has a texture set, every bounce launches the TEX forms;
-        // a flagged session without one launches what a session without the flag does (bounce_args leaves tex_tab null)
-        if (a.tex_tab != nullptr) {
-            PT_SHADE_DISPATCH_WITH(SH_TEX, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
-            return;
-        }
+        PT_SHADE_DISPATCH(hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
     }
-    PT_SHADE_DISPATCH(hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
 }
 template <int MODE, bool COMPACT, int MESH, bool GEN>
 void launch_bounce_at(const BounceArgs &a) {
@@ -204,7 +214,7 @@ void launch_bounce_at(const BounceArgs &a) {
             return;
         }
     }
-    if constexpr ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE) {
+    if constexpr ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || mode_first2(MODE)) && COMPACT && MESH == MESH_NONE) {
         if (R.own_form) {                                     // the own-surface form of the cull (enqueue_bounce); MODE_CACHE0 writes its bits
             if (R.scene_lds) launch_k_bounce<MODE, COMPACT, MESH, true, GEN, false, true>(a);
             else launch_k_bounce<MODE, COMPACT, MESH, false, GEN, false, true>(a);
@@ -220,8 +230,8 @@ void launch_bounce(const BounceArgs &a) {
         launch_bounce_at<MODE, COMPACT, MESH_NONE, false>(a);
     } else if constexpr (MODE == MODE_CACHE0) {                  // bounce 0 by definition: batches generate their rays here too
         if (a.gen_rays) launch_bounce_at<MODE, COMPACT, MESH_NONE, true>(a); else launch_bounce_at<MODE, COMPACT, MESH_NONE, false>(a);
-    } else if constexpr (MODE == MODE_FIRST2) {                  // bounces 0 and 1 of a compacting batch: the paths are generated
-        static_assert(COMPACT, "MODE_FIRST2 compacts");
+    } else if constexpr (mode_first2(MODE)) {                    // bounces 0 and 1 of a compacting batch: the paths are generated
+        static_assert(COMPACT, "MODE_FIRST2 / MODE_STATE2 compact");
         launch_bounce_at<MODE, COMPACT, MESH_NONE, true>(a);
     } else {
         const bool gen = a.gen_rays != 0;
@@ -305,6 +315,9 @@ int enqueue_bounce(int depth, bool may_fuse = false) {
     // generates its paths and counts bounce 0's rays too.
     const bool first2 = may_fuse && auto0 && !(R.flags & PT_CACHE_FIRST) && compact && R.gen_fused && R.first_two_enabled &&
                         R.trace_depth >= 2 && !(a.nlights > 0 && 1 >= a.trace_depth - 1);
+    // ... and its bounce 0 from the first-state table where the session has one (pt_init: no PT_GLOSSY, no
+    // refractive material) and no environment map is set: every pixel is then one of the table's four kinds by construction.
+    const bool state2 = first2 && R.state_mem != nullptr && a.env_n == 0;
     if (first2) {
         depth = 1;
         a.depth = 1;
@@ -343,7 +356,7 @@ int enqueue_bounce(int depth, bool may_fuse = false) {
         const int blocks = std::min(R.grid, (R.map.tile_pixels + BLOCK - 1) / BLOCK);
         const hipStream_t fs = R.lane_cur ? R.lane_main : R.stream;
         PT_MESH_DISPATCH(hipLaunchKernelGGL((k_cache_first<MESH, SLDS>), dim3(blocks), dim3(BLOCK), R.lds_bytes, fs,
-                                            cache, R.scene, R.cam, R.map));
+                                            cache, R.scene, R.cam, R.map, R.state_mem, R.state_ended));
         HIPCHK(hipGetLastError());
         if (R.lane_cur) {
             HIPCHK(hipEventRecord(R.ov_enter, fs));
@@ -363,7 +376,11 @@ int enqueue_bounce(int depth, bool may_fuse = false) {
     if (cached0) {
         a.isect = Isect{R.cache_mem, (uint32_t)R.map.tile_pixels};
         R.first_hit_launches++;
-        if (first2) { R.first_two_launches++; tm.two_bounces(); launch_bounce<MODE_FIRST2, true>(a); }
+        if (state2) {
+            a.first_state = R.state_mem; a.first_ended = R.state_ended; a.first_ended_tiles = (uint32_t)(R.map.tile_pixels / TILE);
+            R.first_two_launches++; R.first_state_launches++; tm.two_bounces(); launch_bounce<MODE_STATE2, true>(a);
+        }
+        else if (first2) { R.first_two_launches++; tm.two_bounces(); launch_bounce<MODE_FIRST2, true>(a); }
         else if (compact) launch_bounce<MODE_CACHE0, true>(a); else launch_bounce<MODE_CACHE0, false>(a);
     } else if (unfused) {
         if (compact) launch_bounce<MODE_ISECT, true>(a); else launch_bounce<MODE_ISECT, false>(a);

@@ -54,7 +54,14 @@ struct Renderer {
     bool first_hit_refence = false;   // the batch being enqueued on a lane filled the table: the next one starts from enter_lanes' event
     bool first_two_enabled = true;    // PTMI355_FIRST_TWO=0: bounce 0 of the table form stays a launch of its own (the A/B control)
     uint64_t first_two_launches = 0;  // launches that did bounces 0 and 1 (k_bounce<MODE_FIRST2>) since pt_init (ptdbg_first_two)
-    uint64_t first_hit_fills = 0, first_hit_launches = 0;   // k_cache_first launches / bounce-0 launches of the table form since pt_init (ptdbg_first_hit)
+    // the first-state table (pt_types.hpp: the FS_ kinds): filled with the first-hit table by the same
+    // kernel, valid when it is (cache_valid).  Only sessions whose bounce 0 is fixed per pixel up to the diffuse draw have one:
+    // no PT_GLOSSY, no refractive material (pt_init)
+    float *state_mem = nullptr;       // first_state_bytes(tile_pixels)
+    uint32_t *state_ended = nullptr;  // one word per 64 local pixels (tile_pixels % 64 == 0 only)
+    bool first_state_enabled = true;  // PTMI355_FIRST_STATE=0: the launch of bounces 0 and 1 shades bounce 0 per sample (the A/B control)
+    uint64_t first_state_launches = 0;   // launches of k_bounce<MODE_STATE2> since pt_init (ptdbg_first_state); each is also a first_two launch
+    uint64_t first_hit_fills = 0, first_hit_launches = 0;  // k_cache_first launches / bounce-0 launches of the table form since pt_init (ptdbg_first_hit)
     Isect isect{};
     float *final_mem = nullptr;   // float4[cap]: {r, g, b, stamp} of the paths that ended with a non-zero colour, index = pid
     uint32_t fin_serial = 0;      // stamp of the current batch's entries (never 0; a wrap clears the buffer)

@@ -15,7 +15,12 @@ namespace {
 // MODE_FIRST2  : the first launch of a batch does bounces 0 AND 1: every tile shades bounce 0 from the
 //                first-hit table in registers (tile_first) and its survivors go through the fused pipeline as bounce 1 in the
 //                lanes they have -- no pool in between
-enum { MODE_FUSED = 0, MODE_ISECT = 1, MODE_CACHE0 = 2, MODE_FIRST2 = 3 };
+// MODE_STATE2  : MODE_FIRST2 for the sessions whose bounce 0 is fixed per pixel up to the diffuse draw:
+//                a tile reads its pixels' first-state records (tile_state) instead of generating and shading camera rays, and a
+//                tile none of whose paths survives bounce 0 never enters the pipeline
+enum { MODE_FUSED = 0, MODE_ISECT = 1, MODE_CACHE0 = 2, MODE_FIRST2 = 3, MODE_STATE2 = 4 };
+// the launch that does bounces 0 and 1
+constexpr bool mode_first2(int mode) { return mode == MODE_FIRST2 || mode == MODE_STATE2; }
 
 // per-launch constants of a wave
 // A field of the kernel's argument block read again where it is used (k_bounce: BounceArgs is the one kernel
@@ -155,6 +160,49 @@ __device__ __forceinline__ void tile_first(const BounceArgs &a, const TileCtx &c
             tr.miss0 = true;
         } else {
             put_final(c.kargs ? karg_field<float *>(offsetof(BounceArgs, fin)) : a.fin, tr.pid, ps.c, c.stamp);
+        }
+    }
+    tr.active = alive;
+}
+
+// MODE_STATE2: tile_load<GEN> and tile_first in one, from the first-state table.  The lane's pid, sample and pixel are set as
+// tile_load sets them (the engine seeds and put_final need them); the record -- one Pool slot, read in one burst -- then says what
+// bounce 0 made of the pixel's camera ray: a diffuse hit draws its direction about the stored normal with the sample's engine of
+// depth 0 (tile_first's eager draw: same engine, same sampler, same normal bits), a mirror's ray is the stored one, a constant
+// colour is stored as the path's final colour, and a pixel that ends with colour 0 does nothing.  No camera, no lens, no
+// material and no shader branch is read here.
+template <bool OWN>
+__device__ __forceinline__ void tile_state(const BounceArgs &a, const TileCtx &c, uint32_t tile, uint32_t i, bool have, bool active,
+                                           TileRegs &tr, f3 &ro, f3 &rd, uint32_t &own) {
+    own = 0u;
+    tr.have = have; tr.i = i; tr.src = i; tr.tile = tile;
+    tr.miss0 = false;
+    tr.pid = DEAD_PID; tr.smp = 0; tr.pixel = 0;
+    tr.col = ptd::mk(1.0f, 1.0f, 1.0f);
+    tr.mb.t = FLT_MAX; tr.mb.geom = -1; tr.mb.tri = -1;
+    ro = ptd::mk(0, 0, 0); rd = ptd::mk(0, 0, 1);
+    bool alive = false;
+    if (active) {
+        tr.pid = i;
+        tr.smp = sample_of(a.map, tr.pid);
+        const uint32_t k = tr.pid - tr.smp * (uint32_t)a.map.tile_pixels;
+        tr.pixel = local_to_pixel(a.map, (int)k);
+        const SlotPtr p = Pool{karg_field<float *>(offsetof(BounceArgs, first_state)), 0u}.slot(k);
+        const uint32_t word = ppid(p);
+        const f3 so = ptd::mk(pf(p, 0), pf(p, 1), pf(p, 2));
+        const f3 sd = ptd::mk(pf(p, 3), pf(p, 4), pf(p, 5));
+        const f3 sc = ptd::mk(pf(p, 6), pf(p, 7), pf(p, 8));
+        const uint32_t kind = word & FS_KIND_MASK;
+        if (kind == FS_DIFFUSE || kind == FS_FIXED) {
+            alive = true;
+            ro = so; rd = sd; tr.col = sc;
+            if (OWN) own = (word & OWN_MASK) >> OWN_SHIFT;
+            if (kind == FS_DIFFUSE) {
+                uint32_t rng = ptd::seeded_engine(c.iter0 + (int)tr.smp, tr.pixel, 0);
+                rd = ptd::hemisphere(sd, rng);
+            }
+        } else if (kind == FS_CONST) {
+            put_final(karg_field<float *>(offsetof(BounceArgs, fin)), tr.pid, sc, c.stamp);
         }
     }
     tr.active = alive;
@@ -382,9 +430,20 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
     // candidate primitives k_cull0_mask has written down
     const bool masked = MODE == MODE_FUSED && GEN && a.cull0 != nullptr;
     uint32_t mtile = masked ? first_tile % a.cull0_tiles : 0u;
+    // MODE_STATE2: pool tile t holds the pixels of camera tile t mod (tiles per sample) in the same way, and k_cache_first has
+    // written down which camera tiles end whole at bounce 0 with colour 0 (one word each; null where the tile's pixels are no
+    // multiple of 64).  Such a tile is absent for the pipeline: nothing is loaded, stored or culled for it, and the tile in
+    // flight (prev, par, tickets) stays as it is.
+    const uint32_t *ended = MODE == MODE_STATE2 ? a.first_ended : nullptr;
+    uint32_t etile = ended ? first_tile % a.first_ended_tiles : 0u;
     for (uint32_t r = 0; r < count; ++r) {
         const uint32_t tile = first_tile + r;
         if (!own_span && tile >= tiles) break;
+        if (MODE == MODE_STATE2 && ended) {
+            const uint32_t whole = ((const __attribute__((address_space(4))) uint32_t *)(unsigned long long)ended)[etile];
+            if (++etile == a.first_ended_tiles) etile = 0;
+            if (whole) continue;
+        }
         rotate_priority(r + (uint32_t)depth, PT_MIN_WAVES + 1);
         unsigned long long gmask = 0;
         if (masked) {
@@ -423,9 +482,15 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
         TileRegs tr;
         f3 ro, rd;
         uint32_t own;
-        tile_load<GEN, RESOLVE, OWN>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd, own);
+        if constexpr (MODE == MODE_STATE2) {
+            tile_state<OWN>(a, c, tile, i, have, active, tr, ro, rd, own);
+            // (also where the words do not apply, or some pixel of the tile ends with a colour: no survivor, no cull, no finish)
+            if (ballot64(tr.active) == 0) continue;
+        } else {
+            tile_load<GEN, RESOLVE, OWN>(a, c, in, depth, tile, i, src, have, active, tr, ro, rd, own);
+        }
         if (MODE == MODE_FIRST2) tile_first<OWN, SH>(a, c, tr, ro, rd, own);
-        if (MODE == MODE_FUSED || MODE == MODE_FIRST2) {
+        if (MODE == MODE_FUSED || mode_first2(MODE)) {
             const float4 *pre_hit = nullptr;
             if (MESH == MESH_PRE && tr.active) {
                 // slots whose flag is set carry a mesh result from k_mesh (a hit, or "walked, nothing hit")
@@ -440,7 +505,7 @@ __device__ __forceinline__ void run_tiles(const BounceArgs &a, const TileCtx &c,
             }
             // (after the load has drawn a pending direction: the row test needs the ray as it is traced)
             cull_scene<MESH, OWN>(a.scene, c.acc, q, par, c.tri_lds, tr.active, ro, rd, tr.mb, pre_hit, masked, gmask,
-                                  (OWN && (!GEN || MODE == MODE_FIRST2)) ? own_surface_miss(c.acc, own, ro, rd) : 0xffffffffu);
+                                  (OWN && (!GEN || mode_first2(MODE))) ? own_surface_miss(c.acc, own, ro, rd) : 0xffffffffu);
             const uint32_t ticket = q.total;
             if (pending) {
                 drain_to(q, c.acc, prev_ticket);
@@ -488,12 +553,13 @@ __device__ uint32_t g_wave_hw[8][8192];
 #endif
 
 template <int MODE, bool COMPACT, int MESH, bool SLDS, bool GEN = false, bool SORT = false, bool OWN = false, int SH = 0>
-__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
+__global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH == MESH_PRE && PT_PRE_WAVES > PT_MIN_WAVES) ? PT_PRE_WAVES : (SORT && MODE == MODE_FUSED && MESH == MESH_NONE) ? PT_SORT_WAVES : ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || mode_first2(MODE)) && COMPACT && MESH == MESH_NONE && !SORT && PT_FUSED_WAVES > PT_MIN_WAVES) ? PT_FUSED_WAVES : PT_MIN_WAVES) void k_bounce(BounceArgs a) {
     // (MODE_CACHE0 only writes the bits: bounce 0 reads no own surface)
-    static_assert(!OWN || ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || MODE == MODE_FIRST2) && COMPACT && MESH == MESH_NONE && !SORT),
+    static_assert(!OWN || ((MODE == MODE_FUSED || MODE == MODE_CACHE0 || mode_first2(MODE)) && COMPACT && MESH == MESH_NONE && !SORT),
                   "own-surface form: the plain fused compacting kernel, or the table form of its bounce 0");
     // (the launch of bounces 0 and 1: BounceArgs::depth is 1 -- directory, election and scan are bounce 1's -- and the paths are generated)
-    static_assert(MODE != MODE_FIRST2 || (COMPACT && MESH == MESH_NONE && GEN && !SORT), "MODE_FIRST2: the plain compacting pipeline's first launch");
+    static_assert(!mode_first2(MODE) || (COMPACT && MESH == MESH_NONE && GEN && !SORT), "MODE_FIRST2 / MODE_STATE2: the plain compacting pipeline's first launch");
+    static_assert(MODE != MODE_STATE2 || SH == 0, "MODE_STATE2: sessions without environment map or lobes");
 #ifdef PT_WAVE_TIMES
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -575,7 +641,7 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
 #endif
     // paths traced this bounce: with compaction it is simply the live count; otherwise count the alive
     // slots, one atomic per workgroup (summed through LDS) rather than one per wave on a single address
-    if (MODE == MODE_FIRST2) {
+    if (mode_first2(MODE)) {
         // bounce 0 traced the whole pool; bounce 1 the survivors tile_shade has counted per wave (`traced`): no directory holds
         // their number, so it is summed like the non-compacting kernels' -- one atomic per workgroup (Control is zeroed per batch)
         if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->alive[0] = n;

@@ -267,9 +267,13 @@ __global__ __launch_bounds__(BLOCK) void k_cull0_mask(SceneDev sc, pt_camera cam
 // jitter, pathtrace.cu:134), so computeIntersections of bounce 0 is evaluated once per pixel and
 // camera and reused by every sample.  The table (pt_types.hpp: Isect::first_hit / first_id) is indexed by the tile's local
 // pixel; one workgroup pass covers BLOCK consecutive pixels, every wave writes 1024 + 512 consecutive bytes.
+// `state` (null: none): the same pass also shades every pixel's bounce 0 once and writes the first-state record (pt_types.hpp:
+// the FS_ kinds) -- the call tile_first makes per sample, with the diffuse direction deferred, so the
+// rows hold the bits that call leaves in the path.  `ended` (null: the tile's pixels are no multiple of 64): one word per 64
+// local pixels, non-zero when all of them are FS_ZERO.  A wave of this kernel covers exactly those 64 pixels.
 template <int MESH, bool SLDS>
 __global__ __launch_bounds__(BLOCK, PT_MIN_WAVES) void k_cache_first(Isect cache, SceneDev sc, pt_camera cam,
-                                                                      TileMap map) {
+                                                                      TileMap map, float *state, uint32_t *ended) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
     const LdsCarve lc = carve_lds(lds_raw, sc, SLDS);
     const SceneAcc acc = stage_scene<SLDS>(lc.scene, sc);
@@ -284,6 +288,7 @@ __global__ __launch_bounds__(BLOCK, PT_MIN_WAVES) void k_cache_first(Isect cache
         MeshBest mb;
         cull_scene<MESH>(sc, acc, q, 0, lc.tri, active, ro, rd, mb, nullptr);
         drain_to(q, acc, q.total);
+        uint32_t kind = FS_ZERO;                                 // (a lane past the tile's pixels: nothing to trace)
         if (active) {
             // exactly what tile_result hands the fused kernel for this ray, the winning primitive included (a miss: t = -1,
             // geom = -1): bounce 0 of the table form shades and tags its survivors as the fused bounce 0 does
@@ -291,6 +296,32 @@ __global__ __launch_bounds__(BLOCK, PT_MIN_WAVES) void k_cache_first(Isect cache
             tile_result(q, 0, acc, sc.tris, mb, t, nrm, mat, outside, geom);
             *cache.first_hit(j) = make_float4(t, nrm.x, nrm.y, nrm.z);
             *cache.first_id(j) = make_int2(mat | (outside ? 0 : (int)0x80000000u), geom);
+            if (state) {
+                // tile_first's call on this record and this ray (its engine is never seeded: the host gives `state` only to
+                // sessions without dielectrics or lobes, and the diffuse direction is left to the reader)
+                bool deferred = false;
+                ptd::PathState ps;
+                ps.o = ro; ps.d = rd; ps.c = ptd::mk(1.0f, 1.0f, 1.0f);
+                const bool alive = ptd::shade_scatter<false>(ps, t, nrm, mat, outside, acc.mats, 0, local_to_pixel(map, (int)j), 0, false,
+                                                             true, &deferred, nullptr);
+                uint32_t word;
+                if (alive) {
+                    kind = deferred ? FS_DIFFUSE : FS_FIXED;
+                    word = kind | (((uint32_t)(geom + 1) << OWN_SHIFT) & OWN_MASK);
+                } else {
+                    if (!(ps.c.x == 0.0f && ps.c.y == 0.0f && ps.c.z == 0.0f)) kind = FS_CONST;     // put_final's test
+                    word = kind;
+                }
+                const SlotPtr p = Pool{state, 0u}.slot(j);
+                pf(p, 0) = ps.o.x; pf(p, 1) = ps.o.y; pf(p, 2) = ps.o.z;
+                pf(p, 3) = ps.d.x; pf(p, 4) = ps.d.y; pf(p, 5) = ps.d.z;
+                pf(p, 6) = ps.c.x; pf(p, 7) = ps.c.y; pf(p, 8) = ps.c.z;
+                ppid(p) = word;
+            }
+        }
+        if (ended) {                                             // (wave-uniform; tile_pixels % 64 == 0: whole waves)
+            const uint64_t live = ballot64(kind != FS_ZERO);
+            if (active && (threadIdx.x & 63) == 0) ended[j >> 6] = live == 0 ? 1u : 0u;
         }
     }
 }

@@ -377,7 +377,25 @@ struct BounceArgs {
     // table of n == 0 where no colour texture is), so the TEX instantiations are launched; no other kernel reads these words.
     const ptd::bump_texel *bumps;
     const int2 *bump_tab;
+    // ... and the first-state table (k_bounce<MODE_STATE2> only): per local pixel what bounce 0 leaves of
+    // its camera ray, laid out as a Pool of tile_pixels slots (the FS_ kinds below), and per 64 local pixels one word that is
+    // non-zero when every one of them ends at bounce 0 with colour 0.  first_ended == nullptr: the words do not apply (the
+    // tile's pixels are no multiple of 64) and only the test after the record load skips a tile.
+    float *first_state;
+    const uint32_t *first_ended;
+    uint32_t first_ended_tiles;     // words in first_ended = tile_pixels / 64
 };
+
+// The first-state record of a pixel (k_cache_first writes it, k_bounce<MODE_STATE2> reads it): a Pool slot whose rows hold what
+// ptd::shade_scatter<false> at depth 0, not the last bounce, with a deferred diffuse direction, makes of the pixel's camera ray
+// and first hit -- origin row: the hit point P; direction row: the hit normal (FS_DIFFUSE) or the reflected direction (FS_FIXED);
+// colour row: the throughput, or the final colour of a path that ends there (FS_CONST).  The slot's pid word is the kind and, in
+// the pid's own-surface bits (OWN_MASK), the primitive hit as geom + 1.  FS_ZERO: the path ends and put_final would store
+// nothing (colour 0: a miss, or a material that emits 0).  Only sessions whose every pixel is one of the four by construction
+// have the table: no PT_GLOSSY and no refractive material (their bounce 0 draws from the sample's engine before it knows the
+// direction); an environment map makes a miss a fifth kind, so while one is set the table is not read.
+enum : uint32_t { FS_ZERO = 0, FS_CONST = 1, FS_DIFFUSE = 2, FS_FIXED = 3, FS_KIND_MASK = 3 };
+__host__ __device__ constexpr size_t first_state_bytes(size_t tile_pixels) { return ((tile_pixels + 63) / 64) * 2560; }
 
 // the shading kernels' variant switch (template parameter SH of k_bounce, k_iteration, k_shade_sorted, k_shade_sorted_w): the
 // launch plan picks the instantiation, so a session that uses neither runs the code it ran before they existed
