@@ -155,6 +155,19 @@ TEXTURED_SEEDS = COMMON_SEEDS
 DIRECT_SEEDS = COMMON_SEEDS                                          # every one has between 1 and 1024 light elements
 FILTER_SEEDS = PLAIN_SEEDS
 MESH_SEEDS = (1029, 1009, 1012, 1024)
+# The first-state table's sessions: no seed of the list draws a refractive material, so pt_init gives every
+# one of them the table.  They also run at STATE_FRAME, whose 1024 pixels are whole 64-pixel tiles: the ended-tile words exist.
+# 1110, 1136, 1176 and 1087 hold all four kinds of record with whole-ended tiles beside mixed ones; 1067 and 1087 have exactly 16
+# primitives; 1089 has 4; 1127 and 1013 have the eye inside a primitive; 1073 and 1060 have depth 2 (1060: 38 primitives, two
+# zero-scaled); every ray of 1153 misses; every pixel of 1100 is a mirror hit from inside; 1079 has depth 1; 1089, 1127 and 1191 have
+# depth 8 or more; in 1009, 1191 and 1188 emitter, mirror and diffuse pixels share tiles and no ray misses.
+STATE_SEEDS = (1009, 1191, 1110, 1136, 1176, 1087, 1067, 1089, 1127, 1013, 1073, 1060, 1153, 1188, 1079, 1100)
+STATE_FRAME = (64, 16)
+# ... of them, the PT_DIRECT_LIGHT session without PT_GLOSSY and sky: depth 3 (1136, the least at which bounces 0 and 1 are plain ones)
+# and more, between 1 and 1024 light elements
+STATE_DIRECT_SEEDS = (1009, 1110, 1136, 1087, 1089, 1127, 1153, 1100)
+STATE_DIRECT_MIN_DEPTH = 3                                           # below it bounce 1 is one of the session's DIRECT bounces
+STATE_KINDS = ("drawn", "fixed", "coloured", "zero")                 # FS_DIFFUSE, FS_FIXED, FS_CONST, FS_ZERO
 
 
 def groups(seeds):
@@ -309,6 +322,19 @@ def direct_run(po, pt, seed, w, h):
     return _cached(("direct", seed, w, h), make)
 
 
+def plain_direct_run(po, pt, seed, w, h):
+    """direct_model.Model without PT_GLOSSY and without a sky over iterations 1 .. 9, the scene's own materials: (run, counts,
+    light elements).  The PT_DIRECT_LIGHT session whose bounces 0 and 1 are plain ones."""
+    def make():
+        import direct_model as dm
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        depth = min(int(depth), MAX_DEPTH - 1)
+        m = dm.Model(po, geoms, mats, cam, depth, glossy=False)
+        run = _model_run(m, w * h, depth, range(1, 10), direct=True)
+        return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, len(m.table)
+    return _cached(("plain direct", seed, w, h), make)
+
+
 def light_table_size(po, pt, seed, w, h):
     import direct_model as dm
     geoms, mats, _, _ = scene(pt, seed, w, h)
@@ -363,6 +389,51 @@ def albedo_run(po, pt, seed, w, h):
                           3, *SIGMAS).reshape(-1, 3)
         return A, out
     return _cached(("albedo", seed, w, h), make)
+
+
+class FirstState:
+    """What bounce 0 leaves of a seed's camera rays, per pixel and per 64-pixel tile: `kinds` ([pixels] indices into STATE_KINDS),
+    `count` {kind: pixels}, `tiles` {"ended" | "mixed" | "live": tiles}, `inside`, `primitives`, `depth`."""
+
+
+def first_state_facts(po, pt, seed, w, h):
+    """The four kinds of the first-state record read from the oracle's bounce-0 snapshots of iterations
+    1 and 2 -- the paths as its shade step and compaction leave them, put back in pixel order: a survivor whose direction has the
+    same bits in both iterations carries a fixed direction, one whose direction differs drew it; a path that ended did so with a
+    colour or with 0 (put_final's test).  The oracle runs at depth max(depth, 2): the record holds what a bounce 0 that is not
+    the last one leaves, whatever the session's depth, and at depth 1 the oracle zeroes every colour that does not end on a light.
+    A tile is 64 consecutive pixels (a last, shorter one included): "ended" when every pixel ends with colour 0 (the condition
+    of the table's word), "live" when every pixel survives, "mixed" otherwise -- a tile whose pixels all end, some with a colour,
+    is mixed: no word skips it."""
+    def make():
+        geoms, mats, cam, depth = scene(pt, seed, w, h)
+        g = np.ascontiguousarray(geoms).view(po.GEOM_DT)
+        after = []
+        for it in (1, 2):
+            ref = po.Tracer(g, mats.view(po.MATERIAL_DT), cam, max(depth, 2), flags=po.F_COMPACT, trig=po.TRIG_SHARED)
+            snaps = []
+            ref.iterate(it, snapshots=snaps)
+            p = snaps[0]["paths"]
+            assert snaps[0]["depth"] == 0 and len(p) == w * h
+            by_pixel = np.empty_like(p)
+            by_pixel[p["pixelIndex"]] = p
+            after.append(by_pixel)
+        a, b = after
+        alive = a["remainingBounces"] > 0
+        assert (alive == (b["remainingBounces"] > 0)).all()
+        same = (np.ascontiguousarray(a["direction"]).view(np.uint32) == np.ascontiguousarray(b["direction"]).view(np.uint32)).all(axis=1)
+        coloured = (a["color"] != 0).any(axis=1)
+        f = FirstState()
+        f.kinds = np.where(alive, np.where(same, 1, 0), np.where(coloured, 2, 3)).astype(np.int8)
+        f.count = {k: int((f.kinds == i).sum()) for i, k in enumerate(STATE_KINDS)}
+        f.tiles = {"ended": 0, "mixed": 0, "live": 0}
+        for t0 in range(0, w * h, 64):
+            k = f.kinds[t0:t0 + 64]
+            f.tiles["ended" if (k == 3).all() else "live" if (k <= 1).all() else "mixed"] += 1
+        f.inside = first_hit_facts(po, pt, seed, w, h)[1]
+        f.primitives, f.depth = len(geoms), depth
+        return f
+    return _cached(("first state", seed, w, h), make)
 
 
 def first_hit_facts(po, pt, seed, w, h):

@@ -3,7 +3,9 @@ environment map the launch that does bounces 0 and 1 (section 6.23) reads, per p
 ends with colour 0, ends with a constant colour, diffuse hit (point, normal, throughput) or fixed direction (a mirror) -- from a
 table filled once per camera (k_bounce<MODE_STATE2>), and a 64-path tile none of whose paths survives bounce 0 never enters the
 pipeline.  Only the work moves: image, rays counted and live counts stay bit-identical to the oracle.  Every case asks the library
-whether the form engaged (ptdbg_first_state: such launches since pathtraceInit), the sessions that must not take it included.
+whether the form engaged (ptdbg_first_state: such launches since pathtraceInit), the sessions that must not take it included, and
+the sessions that switch between the forms on the way -- a map, textures or a lens set and removed, traceDepth changed, pt_free
+and pt_init between scenes with and without glass -- after every step.
 
 Batches take the per-bounce plan here (PTMI355_WHOLE_MAX=0): k_iteration never reads the table."""
 import ctypes as C
@@ -21,6 +23,7 @@ import environment_model as em  # noqa: E402
 import glossy_model as gm  # noqa: E402
 import test_gpu_direct as td  # noqa: E402
 import test_gpu_textures as tt  # noqa: E402
+import texture_model as tm  # noqa: E402
 from gpu_common import pt, bits, _resized  # noqa: E402,F401
 from test_gpu_first_hit import small, tracer, check_batch, init, first_hit, moved_cameras  # noqa: E402
 from test_gpu_first_two import first_two, with_depth  # noqa: E402
@@ -167,6 +170,23 @@ def test_own_surface_bits_of_the_record(pt, po, scenes, shape):
     two_batches(pt, po, s, 3, 3)
 
 
+@pytest.mark.parametrize("w, h", [(64, 48), (31, 29)])
+def test_lamp_without_red(pt, po, scenes, w, h):
+    """The lamp's colour (0, 0.8, 0.6), seen directly: those pixels end with a colour whose first component is 0 -- a constant
+    colour all the same (put_final's test looks at all three components), not the kind that ends with 0."""
+    s = small(scenes, "cornell", w, h)
+    mats = s["materials"].copy()
+    assert mats["emittance"][0] > 0
+    mats["color"][0] = (0.0, 0.8, 0.6)
+    s = dict(s, materials=mats, camera=looking_at_the_light(s["camera"]))
+    snaps = []
+    tracer(po, s).iterate(1, snapshots=snaps)
+    p = snaps[0]["paths"]
+    seen = (p["remainingBounces"] == 0) & (p["color"][:, 0] == 0) & (p["color"][:, 1] > 0)
+    assert seen.sum() >= 8
+    two_batches(pt, po, s, 3, 3)
+
+
 def test_glass_keeps_the_per_sample_form(pt, po, scenes):
     """A refractive material anywhere in the scene: the Fresnel choice draws from the sample's engine at bounce 0."""
     two_batches(pt, po, small(scenes, "cornell_glass"), 3, 3, taken=False)
@@ -174,7 +194,8 @@ def test_glass_keeps_the_per_sample_form(pt, po, scenes):
 
 
 def test_environment_map_keeps_the_per_sample_form(pt, po, scenes):
-    """While a map is set a miss is a fifth kind; with the map taken away again the session reads its table."""
+    """While a map is set a miss is a fifth kind; with the map taken away again the session reads its table
+    (test_environment_map_set_removed_and_set_again)."""
     scn = pt.load_scene(os.path.join(ROOT, "scenes", "open_sky.txt"))
     cam = _resized(scn.camera, 50, 37)
     tex = np.random.default_rng(4001).uniform(0, 2, (6, 4, 4, 3)).astype(np.float32)
@@ -190,6 +211,152 @@ def test_environment_map_keeps_the_per_sample_form(pt, po, scenes):
         assert first_two(pt) == 1 and first_state(pt) == 0
     finally:
         pt.pathtraceFree()
+
+
+# ---- transitions inside one session ------------------------------------------------------------------------------------------------
+# Each step traces one batch of 3 and compares the running sum bit for bit; after it, `counters` must be (launches from the
+# first-state table, launches of bounces 0 and 1, (fills of the first-hit table, bounce-0 launches that read it)) as
+# enqueue_bounce and pt_set_camera imply: the first-hit form (auto0) does not ask about the map or the depth, so its table -- and
+# the first-state records k_cache_first writes in the same pass -- is filled by the first batch without lens and textures and
+# stands until the camera moves; the first-state form asks per launch for depth >= 2 and no map.
+FRAMES = [(64, 48), (64, 4)]
+
+
+def counters(pt):
+    return first_state(pt), first_two(pt), first_hit(pt)
+
+
+def model_batch(pt, m, n, iter0, what):
+    pt.trace_batch(iter0, 3)
+    for it in range(iter0, iter0 + 3):
+        want = m.iterate(it)
+    assert (bits(pt.get_image(n)) == bits(want)).all(), what
+
+
+@pytest.mark.parametrize("w, h", FRAMES)
+def test_environment_map_set_removed_and_set_again(pt, po, scenes, w, h):
+    """Map set: the per-sample form, which fills the tables -- (0, 1, (1, 1)); map removed: the table form on the records filled
+    under the map -- (1, 2, (1, 2)); map set again: the per-sample form -- (1, 3, (1, 3))."""
+    s = small(scenes, "cornell", w, h)
+    tex = np.random.default_rng(4001).uniform(0, 2, (6, 4, 4, 3)).astype(np.float32)
+    m = em.Model(po, s["geoms"], s["materials"], s["camera"], s["depth"])
+    init(pt, s, max_batch=3)
+    try:
+        for k, (env, want) in enumerate([(tex, (0, 1, (1, 1))), (None, (1, 2, (1, 2))), (tex, (1, 3, (1, 3)))]):
+            pt.set_environment(env)
+            m.set_environment(env)
+            model_batch(pt, m, w * h, 1 + 3 * k, k)
+            assert counters(pt) == want, k
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("w, h", FRAMES)
+def test_textures_set_removed_and_one_set_back(pt, po, scenes, w, h):
+    """PT_TEXTURES without PT_GLOSSY on cornell_textured against texture_model.Model.  Textures set: the TEX forms, no table --
+    (0, 0, (0, 0)); all removed: the session launches what one without the flag does, and the tables are filled at that moment
+    -- (1, 1, (1, 1)); one set back: the TEX forms again -- (1, 1, (1, 1))."""
+    scn = pt.load_scene(os.path.join(ROOT, "scenes", "cornell_textured.txt"))
+    cam = _resized(scn.camera, w, h)
+    textures = dict(scn.textures)
+    back = min(textures)
+    m = tm.Model(po, scn.geoms, scn.materials, cam, scn.traceDepth)
+    pt.pathtraceInit(pt.Scene(scn.geoms, scn.materials, cam, scn.traceDepth), flags=pt.PT_COMPACT | pt.PT_TEXTURES, max_batch=3)
+    try:
+        steps = [(textures, (0, 0, (0, 0))), ({k: None for k in textures}, (1, 1, (1, 1))), ({back: textures[back]}, (1, 1, (1, 1)))]
+        for k, (change, want) in enumerate(steps):
+            for mat, t in change.items():
+                pt.set_texture(mat, t)
+                m.set_texture(mat, t)
+            model_batch(pt, m, w * h, 1 + 3 * k, k)
+            assert counters(pt) == want, k
+        assert m.tinted > 0
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("w, h", FRAMES)
+def test_lens_set_and_back_to_a_pinhole(pt, po, scenes, w, h):
+    """A lens from the start: rays differ per sample, no table -- (0, 0, (0, 0)); pinhole: the tables are filled now --
+    (1, 1, (1, 1)); lens again: nothing reads them -- (1, 1, (1, 1)); pinhole: the camera has not moved, no second fill --
+    (2, 2, (1, 2))."""
+    s = small(scenes, "cornell", w, h)
+    init(pt, s, max_batch=3)
+    try:
+        image = None
+        steps = [((0.4, 9.0), (0, 0, (0, 0))), ((0.0, 0.0), (1, 1, (1, 1))), ((0.4, 9.0), (1, 1, (1, 1))), ((0.0, 0.0), (2, 2, (1, 2)))]
+        for k, (lens, want) in enumerate(steps):
+            pt.set_lens(*lens)
+            ref = tracer(po, s, image=image, **({"lens": lens} if lens[0] > 0 else {}))
+            check_batch(pt, ref, s, 1 + 3 * k, 3, k)
+            image = ref.image
+            assert counters(pt) == want, k
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("w, h", FRAMES)
+def test_depth_changes_under_one_camera(pt, po, scenes, w, h):
+    """traceDepth 1 -> 3 -> 2 -> 8 through pt_set_camera with the camera's bytes unchanged: one fill in all, at depth 1, by the
+    first-hit form (there is no bounce 1) -- (0, 0, (1, 1)); its records are what a bounce 0 that is not the last leaves, and depth
+    3 reads them -- (1, 1, (1, 2)); depth 2, where bounce 1 is the last -- (2, 2, (1, 3)); depth 8 -- (3, 3, (1, 4))."""
+    s = with_depth(small(scenes, "cornell", w, h), 1)
+    init(pt, s, max_batch=3)
+    try:
+        image = None
+        for k, (depth, want) in enumerate([(1, (0, 0, (1, 1))), (3, (1, 1, (1, 2))), (2, (2, 2, (1, 3))), (8, (3, 3, (1, 4)))]):
+            s = with_depth(s, depth)
+            pt.set_camera(s["camera"], depth)
+            ref = tracer(po, s, image=image)
+            check_batch(pt, ref, s, 1 + 3 * k, 3, depth)
+            image = ref.image
+            assert counters(pt) == want, depth
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("w, h", FRAMES)
+def test_fill_on_a_lane_under_a_map_then_the_table_form(pt, po, scenes, w, h):
+    """Four asynchronous batches of 3 under a map (the per-sample form; the first of them enqueues the fill of both tables from its
+    lane), the map removed with no synchronisation of the caller's, four more (the table form, on other lanes than the one that
+    filled): one synchronize, one image -- (4, 8, (1, 8))."""
+    s = small(scenes, "cornell", w, h)
+    tex = np.random.default_rng(4001).uniform(0, 2, (6, 4, 4, 3)).astype(np.float32)
+    m = em.Model(po, s["geoms"], s["materials"], s["camera"], s["depth"])
+    init(pt, s, max_batch=3)
+    try:
+        pt.set_environment(tex)
+        for k in range(4):
+            pt.trace_batch_async(1 + 3 * k, 3)
+        pt.set_environment(None)
+        for k in range(4, 8):
+            pt.trace_batch_async(1 + 3 * k, 3)
+        pt.synchronize()
+        m.set_environment(tex)
+        for it in range(1, 25):
+            if it == 13:
+                m.set_environment(None)
+            want = m.iterate(it)
+        assert (bits(pt.get_image(w * h)) == bits(want)).all()
+        assert counters(pt) == (4, 8, (1, 8))
+    finally:
+        pt.pathtraceFree()
+
+
+def test_free_and_init_between_glass_free_and_glass_scenes(pt, po, scenes):
+    """pt_free / pt_init in a row: Cornell 64 x 4 (table and words), cornell_glass 31 x 29 (no table), Cornell 31 x 29 (table
+    without words), Cornell 64 x 4 (words again)."""
+    two_batches(pt, po, small(scenes, "cornell", 64, 4), 3, 3)
+    two_batches(pt, po, small(scenes, "cornell_glass", 31, 29), 3, 3, taken=False)
+    two_batches(pt, po, small(scenes, "cornell", 31, 29), 3, 3)
+    two_batches(pt, po, small(scenes, "cornell", 64, 4), 3, 3)
+
+
+@pytest.mark.parametrize("w, h", [(64, 4), (31, 29), (64, 48)])
+def test_frames_without_the_scene_in_lds(pt, po, scenes, monkeypatch, w, h):
+    """test_frames with the scene gathered from global memory (PTMI355_SCENE_LDS=0): the two other instantiations."""
+    monkeypatch.setenv("PTMI355_SCENE_LDS", "0")
+    two_batches(pt, po, small(scenes, "cornell", w, h), 3, 3)
 
 
 def test_glossy_session_keeps_the_per_sample_form(pt, po, scenes):

@@ -8,6 +8,9 @@ Every session is the tool's call sequence -- pt_trace_batch(1, 2), one pathtrace
 at 40 x 26 (16 full waves and a 16-lane tail; several tiles of the fused kernels), the first seed of a list also at 130 x 9, under
 both launch plans; running sums are compared byte for byte with the numpy models (computed here, once per seed; no golden files),
 live and ray counters wherever the model counts them.  A test item is one group of four seeds under one session.
+The first-state table (k_bounce<MODE_STATE2>) has a list of its own, rs.STATE_SEEDS: scenes without a
+refractive material, which also run at 64 x 16 -- whole 64-pixel tiles, so the ended-tile words are read -- and every such session
+asks ptdbg_first_state whether each launch of bounces 0 and 1 was the table form.
 tests/test_random_scenes_cpu.py shows from the models alone that the seed lists reach the branches named above.
 
 A failure names the seed, the session, the number of differing pixels, the first of them with both values, and the bounce at which
@@ -130,6 +133,121 @@ def test_plain_sessions(pt, po, launch_plan, pipeline, group):
                 trace_sequence(pt, rep, seed, w, h, run2, depth, rays=run2.rays, what="camera of seed %d: " % rs.next_seed(rs.PLAIN_SEEDS, seed))
                 if fused:
                     rep.equal(seed, "fused launches under the second camera > 0", first_two(pt) > before, True)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+# ---- the first-state table on glass-free scenes ----------------------------------------------------------
+def first_state(pt):
+    """launches whose bounce 0 came from the first-state table since pathtraceInit"""
+    out = (C.c_ulonglong * 1)()
+    assert pt.library().ptdbg_first_state(out) == 0
+    return int(out[0])
+
+
+def state_frames(seeds, group):
+    """(seed, w, h) of a group: every seed at 64 x 16 (whole tiles: the ended-tile words exist) and at 40 x 26 (they do not), the
+    list's first seed also at 130 x 9."""
+    out = [(s,) + rs.STATE_FRAME for s in group] + [(s, W, H) for s in group]
+    if seeds[0] in group:
+        out.append((seeds[0],) + rs.WIDE)
+    return out
+
+
+def state_counters(pt, rep, seed, what, launch_plan, depth, before=0):
+    """Every launch of bounces 0 and 1 of these sessions is the table form; a kernel per bounce at depth 2 or more makes some."""
+    two, state = first_two(pt), first_state(pt)
+    rep.equal(seed, what + "launches from the first-state table == launches of bounces 0 and 1", state, two)
+    if depth == 1:
+        rep.equal(seed, what + "launches of bounces 0 and 1 at depth 1", two, 0)
+    elif launch_plan == "one launch per bounce":
+        rep.equal(seed, what + "launches from the first-state table rose above %d" % before, state > before, True)
+    return state
+
+
+STATE_CASES = [(g, "1") for g in rs.groups(rs.STATE_SEEDS)] + [(rs.groups(rs.STATE_SEEDS)[0], "0")]
+
+
+@pytest.mark.parametrize("group, scene_lds", STATE_CASES)
+def test_first_state_sessions(pt, po, launch_plan, monkeypatch, group, scene_lds):
+    """PT_COMPACT on the scenes without a refractive material against po.Tracer, the call sequence of test_plain_sessions under the
+    seed's camera and under the NEXT seed's: bounce 0 of every launch of the two comes from the per-pixel table
+    (k_bounce<MODE_STATE2>), whose records here are of all four kinds in odd mixtures -- an eye inside an emitter, frames that
+    mostly miss, mirror hits from inside, slabs of 0.001 -- and whose ended-tile words are read at 64 x 16.  The first group runs
+    once more with the scene gathered from global memory (PTMI355_SCENE_LDS=0: the two other instantiations)."""
+    if scene_lds == "0":
+        monkeypatch.setenv("PTMI355_SCENE_LDS", "0")
+    rep = Report("first state" + (", scene not in LDS" if scene_lds == "0" else ""), launch_plan)
+    for seed, w, h in state_frames(rs.STATE_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        scene = pt.Scene(geoms, mats, cam, depth)
+        pt.pathtraceInit(scene, flags=pt.PT_COMPACT, max_batch=2)
+        try:
+            at = "%d x %d: " % (w, h)
+            run = rs.plain_run(po, pt, seed, w, h, po.F_COMPACT)
+            trace_sequence(pt, rep, seed, w, h, run, depth, rays=run.rays, what=at)
+            before = state_counters(pt, rep, seed, at, launch_plan, depth)
+            other = rs.next_seed(rs.STATE_SEEDS, seed)
+            cam2 = rs.scene(pt, other, w, h)[2]
+            scene.camera = cam2
+            pt.set_camera(cam2, depth)
+            pt.clear_image()
+            run2 = rs.plain_run(po, pt, seed, w, h, po.F_COMPACT, cam=cam2)
+            at += "camera of seed %d: " % other
+            trace_sequence(pt, rep, seed, w, h, run2, depth, rays=run2.rays, what=at)
+            state_counters(pt, rep, seed, at, launch_plan, depth, before)
+        finally:
+            pt.pathtraceFree()
+    rep.done()
+
+
+@pytest.mark.parametrize("seed", [rs.STATE_SEEDS[0], rs.STATE_SEEDS[2]])
+def test_first_state_tile_of_a_frame(pt, po, launch_plan, seed):
+    """The list's first seed (no pixel ends with 0) and its third (whole-ended tiles beside mixed ones) at 64 x 16 as tile 1 of 2 in
+    strips of 4 rows: 512 local pixels, so the words exist, and records and words are indexed by the tile's local pixel.  Compared
+    over the tile's own pixels."""
+    w, h = rs.STATE_FRAME
+    rep = Report("first state, tile 1 of 2", launch_plan)
+    geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+    own = pt.sharding.tile_pixel_indices(1, 2, 4, w, h)
+    assert len(own) == 512
+    run = rs.plain_run(po, pt, seed, w, h, po.F_COMPACT)
+    pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT, max_batch=2, tile=(1, 2, 4))
+    try:
+        img = np.zeros((w * h, 3), dtype=F32)
+        for iter0 in (1, 3, 5):
+            pt.trace_batch(iter0, 2, img)
+            rep.equal(seed, "paths of the batch at %d" % iter0, int(pt.get_stats().live[0]), 2 * len(own))
+            bad = (bits(img[own]) != bits(run.images[iter0 + 1][own])).any(axis=1)
+            if bad.any():
+                p = int(own[np.nonzero(bad)[0][0]])
+                rep.lines.append("seed %d, %s [%s], batch at %d: %d of %d pixels differ; first pixel %d (x %d, y %d): got %r, want %r; its "
+                                 "path ended at bounce %d" % (seed, rep.session, rep.plan, iter0, int(bad.sum()), len(own), p, p % w, p // w,
+                                                              img[p].tolist(), run.images[iter0 + 1][p].tolist(), run.ended[iter0 + 1][p]))
+        two, state = first_two(pt), first_state(pt)
+        rep.equal(seed, "launches from the first-state table == launches of bounces 0 and 1", state, two)
+        if launch_plan == "one launch per bounce":
+            rep.equal(seed, "launches from the first-state table", state, 3 if depth >= 2 else 0)
+    finally:
+        pt.pathtraceFree()
+    rep.done()
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.STATE_DIRECT_SEEDS))
+def test_first_state_direct_sessions(pt, po, launch_plan, group):
+    """PT_COMPACT | PT_DIRECT_LIGHT without PT_GLOSSY and without a sky, at depth 3 or more, against direct_model.Model: bounces 0
+    and 1 are plain ones, so the launch of the two reads the table; D + 1 bounces counted."""
+    rep = Report("first state + direct", launch_plan)
+    for seed, w, h in state_frames(rs.STATE_DIRECT_SEEDS, group):
+        geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+        run, _, elements = rs.plain_direct_run(po, pt, seed, w, h)
+        assert depth >= rs.STATE_DIRECT_MIN_DEPTH and 0 < elements <= 1024, seed     # (tests/test_random_scenes_cpu.py asserts it)
+        pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT | pt.PT_DIRECT_LIGHT, max_batch=2)
+        try:
+            at = "%d x %d: " % (w, h)
+            trace_sequence(pt, rep, seed, w, h, run, depth + 1, what=at)
+            state_counters(pt, rep, seed, at, launch_plan, depth)
         finally:
             pt.pathtraceFree()
     rep.done()

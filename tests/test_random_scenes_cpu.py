@@ -81,7 +81,7 @@ def test_seed_lists_are_sixteen_literal_seeds():
     assert len(rs.MESH_SEEDS) == 4
 
 
-@pytest.mark.parametrize("seed", sorted(set(rs.PLAIN_SEEDS + rs.TEXTURED_SEEDS + rs.DIRECT_SEEDS + (1, 2, 3, 1000, 1049))))
+@pytest.mark.parametrize("seed", sorted(set(rs.PLAIN_SEEDS + rs.TEXTURED_SEEDS + rs.DIRECT_SEEDS + rs.STATE_SEEDS + (1, 2, 3, 1000, 1049))))
 def test_a_seed_builds_the_scene_it_always_built(pt, seed):
     """At the tool's 64 x 64 the new function's bytes are the old inline code's -- geoms, materials, camera, depth, the launch-plan
     coin and the place the stream stands at afterwards; at 40 x 26 only the camera's resolution and pixel lengths differ."""
@@ -211,6 +211,66 @@ def test_filter_session_floors(pt, po):
     assert max(kept) > 0.5 and min(kept) < 0.05                                           # history that survives a move, and history that does not
     far = [np.abs(rs.filter_run(po, pt, s, rs.next_seed(rs.FILTER_SEEDS, s), W, H)["g"][0]["position"]).max() for s in rs.FILTER_SEEDS]
     assert max(far) >= 50
+
+
+# ---- the first-state table's list ------------------------------------------------------------------------------------------------
+def test_first_state_list_is_glass_free_and_literal(pt):
+    assert len(rs.STATE_SEEDS) == 16 and len(set(rs.STATE_SEEDS)) == 16 and len(rs.groups(rs.STATE_SEEDS)) == 4
+    for seed in rs.STATE_SEEDS:
+        mats = rs.scene(pt, seed, W, H)[1]
+        assert not (mats["hasRefractive"] > 0).any(), seed                                # pt_init gives the session its table
+    assert set(rs.STATE_DIRECT_SEEDS) <= set(rs.STATE_SEEDS) and len(set(rs.STATE_DIRECT_SEEDS)) == len(rs.STATE_DIRECT_SEEDS)
+
+
+def on(facts, cond):
+    return sum(bool(cond(f)) for f in facts)
+
+
+def test_first_state_list_floors(pt, po):
+    """What the oracle's bounce-0 snapshots say about the list (random_scenes.first_state_facts), as floors."""
+    w, h = rs.STATE_FRAME
+    facts = [rs.first_state_facts(po, pt, s, w, h) for s in rs.STATE_SEEDS]
+    for f in facts:
+        assert sum(f.count.values()) == w * h and sum(f.tiles.values()) == w * h // 64
+    for kind in rs.STATE_KINDS:
+        assert on(facts, lambda f: f.count[kind] > 0) >= 6, kind
+    assert on(facts, lambda f: all(f.count[k] > 0 for k in rs.STATE_KINDS)) >= 3          # all four kinds in one frame
+    assert on(facts, lambda f: f.tiles["ended"] > 0 and f.tiles["mixed"] > 0) >= 5         # tiles the words skip beside tiles they do not
+    assert on(facts, lambda f: f.tiles["ended"] == w * h // 64) >= 1
+    assert on(facts, lambda f: f.tiles["ended"] == 0) >= 5
+    assert on(facts, lambda f: f.primitives <= 16) >= 3 and on(facts, lambda f: f.primitives == 16) >= 1
+    assert on(facts, lambda f: f.primitives >= 17) >= 8                                   # either side of the own-surface form's 15 + 1
+    assert on(facts, lambda f: f.depth == 1) == 1 and on(facts, lambda f: f.depth == 2) >= 2 and on(facts, lambda f: f.depth >= 8) >= 3
+    assert sum(bool(rs.zero_scaled(rs.scene(pt, s, w, h)[0]).any()) for s in rs.STATE_SEEDS) >= 4
+    assert on(facts, lambda f: f.inside) >= 6
+    # 40 x 26: no words, the kinds still occur
+    small = [rs.first_state_facts(po, pt, s, W, H) for s in rs.STATE_SEEDS]
+    for kind in rs.STATE_KINDS:
+        assert on(small, lambda f: f.count[kind] > 0) >= 2, kind
+
+
+def test_first_state_session_images_are_finite(pt, po):
+    frames = [(s,) + rs.STATE_FRAME for s in rs.STATE_SEEDS] + [(s, W, H) for s in rs.STATE_SEEDS] + [(rs.STATE_SEEDS[0],) + rs.WIDE]
+    for seed, w, h in frames:
+        assert finite(*rs.plain_run(po, pt, seed, w, h, po.F_COMPACT).images.values()), (seed, w, h)
+        cam2 = rs.scene(pt, rs.next_seed(rs.STATE_SEEDS, seed), w, h)[2]
+        assert finite(*rs.plain_run(po, pt, seed, w, h, po.F_COMPACT, cam=cam2).images.values()), (seed, w, h)
+    lit = sum(bool((rs.plain_run(po, pt, s, *rs.STATE_FRAME, po.F_COMPACT).images[9] != 0).any()) for s in rs.STATE_SEEDS)
+    assert lit >= 8
+
+
+def test_first_state_direct_subset(pt, po):
+    assert len(rs.STATE_DIRECT_SEEDS) >= 6
+    lit = 0
+    for seed in rs.STATE_DIRECT_SEEDS:
+        for w, h in (rs.STATE_FRAME, (W, H)):
+            geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+            assert depth >= rs.STATE_DIRECT_MIN_DEPTH, seed                              # bounces 0 and 1 are plain ones
+            assert 0 < rs.light_table_size(po, pt, seed, w, h) <= 1024, seed
+            run, counts, elements = rs.plain_direct_run(po, pt, seed, w, h)
+            assert finite(*run.images.values()), seed
+            lit += counts.get("final rays", 0)
+    assert lit >= 300                                                                     # the sessions do reach their final rays
 
 
 def test_mesh_session_images_are_finite(pt, po):
