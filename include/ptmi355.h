@@ -249,6 +249,18 @@ enum pt_flags {
                                     visibility: on a featureless sky it is noisier than the ordinary bounce, under a small
                                     bright region far quieter.  Refused by pt_init (PT_ERR_INVALID) without PT_DIRECT_LIGHT;
                                     PT_FAKE_SHADER ignores both. */
+    PT_SMOOTH_NORMALS = 1u << 16, /* opt-in: smooth shading of triangle meshes.  While per-vertex normals are set
+                                    (pt_set_vertex_normals) a hit on a mesh triangle is shaded about the normal interpolated
+                                    from its three corners instead of the facet normal ("smooth shading" below; DESIGN.md
+                                    section 6.26).  Colours, origins, t, misses, spheres, cubes and the ray counters are
+                                    untouched; a flagged session with no normals set, or with all-zero normals, is the plain
+                                    session bit for bit.  While normals are set the session runs a kernel per bounce.  Honoured
+                                    by the fused pipelines (with and without PT_COMPACT, the fused form of PT_SORT_MATERIAL,
+                                    meshes with and without PT_MESH_BVH, PT_GLOSSY, an environment map).  Refused by pt_init
+                                    (PT_ERR_INVALID) with PT_UNFUSED, with PT_CACHE_FIRST, with a PT_SORT_MATERIAL session that
+                                    would take the two-kernel form (their planes carry one normal, and the guard needs two)
+                                    and with PT_TEXTURES or PT_DIRECT_LIGHT (the combined kernel forms are a later change).
+                                    PT_FAKE_SHADER ignores the flag. */
     PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after
@@ -405,6 +417,42 @@ int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n);
  * PT_ERR_INVALID: what pt_texture_texel refuses, and a null texels, normals, dirs, out_normals or perturbed with count > 0. */
 int pt_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *points, const float *normals, const float *dirs,
                    int count, const float *texels, int n, float *out_normals, uint8_t *perturbed);
+
+/* ---- smooth shading (PT_SMOOTH_NORMALS): per-vertex normals replace a mesh triangle's facet normal in the shader ---------------
+ * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/smooth_model.py is the numpy form, and
+ * the device's result equals it bit for bit).  The normals are world-space, as pt_triangle is: nine floats
+ * n0, n1, n2 per triangle, indexed by the ORIGINAL triangle index (the order of pt_scene_desc::triangles) in both mesh modes.
+ * They need not be unit vectors.  At a hit with t > 0 whose winner is triangle k of a mesh primitive, with (v0, e1 = fl(v1 - v0),
+ * e2 = fl(v2 - v0)) as the device records hold them, the ray (o, I), nr the facet normal the intersection reported and n0, n1, n2
+ * the normals of k:
+ *   1  the barycentrics of glm::intersectRayTriangle as the intersection computed them:  p = cross(I, e2);  a = dot(e1, p);
+ *      f = 1 / a;  s = o - v0;  bx = f * dot(s, p);  q = cross(s, e1);  by = f * dot(I, q);  bw = (1 - bx) - by
+ *   2  w = (n0 * bw + n1 * bx) + n2 * by per component;  l2 = dot(w, w);  l2 not a finite number > 0: not smoothed (an all-zero
+ *      triple therefore means "this triangle stays faceted")
+ *   3  ns = w * (1 / sqrt(l2))
+ *   4  dot(ns, nr) > 0 is false: not smoothed (meshes are one-sided: there is no flip)
+ *   5  dot(I, ns) < 0 is false: not smoothed
+ * A smoothed hit is shaded with ns where nr stands (the glossy lobe, the mirror, the dielectric, the diffuse sampler; the same
+ * engine, the same draws).  Then the guard of bump mapping applies: a survivor whose material is a mirror or is neither mirror
+ * nor dielectric and whose new direction has dot(dir, nr) > 0 false takes reflect(dir, nr), not renormalised.  Everything else --
+ * colours, origins, t, outside, the emitter and last-bounce exits, misses, spheres and cubes, the ray counters, pt_stats -- is
+ * unchanged, and a hit that is not smoothed is shaded exactly as without normals.  pt_gbuffer, pt_albedo and the filters keep the
+ * FACET normal; handing them the shading normal is a later change.
+ * pt_set_vertex_normals(normals, num_triangles): num_triangles must equal the session's; (NULL, 0) removes the normals.  The
+ * call synchronises the session, discards the PT_LOOKAHEAD windows and leaves the accumulation buffer alone; the state survives
+ * pt_set_camera and pt_clear_image and ends with pt_free; every context of a multi-device session keeps its own copy.
+ * pt_get_vertex_normals: *num_triangles = the count set (0: none; `normals` may then be NULL); otherwise copies 9 floats per
+ * triangle as they were set when capacity_triangles suffices.
+ * PT_ERR_INVALID (both): before pt_init; a session without PT_SMOOTH_NORMALS; a count that differs from the session's; a null
+ * array with a positive count (the getter: too small a capacity, a null num_triangles). */
+int pt_set_vertex_normals(const float *normals, int num_triangles);
+int pt_get_vertex_normals(float *normals, int capacity_triangles, int *num_triangles);
+/* host-only (no GPU): steps 1-5 for each of `count` records (triangle tri[i], ray origins[3 i ..], dirs[3 i ..]) with nr the
+ * facet normal normalize(cross(e1, e2)): out_normals = ns and smoothed = 1 where the hit is smoothed, out_normals = nr and
+ * smoothed = 0 elsewhere.  The ray need not hit the triangle: the arithmetic is the same.
+ * PT_ERR_INVALID: a negative count, a null array with count > 0, a tri entry outside [0, num_triangles). */
+int pt_smooth_normal(const pt_triangle *triangles, const float *normals, int num_triangles, const int32_t *tri, const float *origins,
+                     const float *dirs, int count, float *out_normals, uint8_t *smoothed);
 
 /* ---- glossy reflection and frosted glass (PT_GLOSSY): SPECEX gives the specular surfaces a GGX lobe ------------------------
  * All arithmetic binary32, one rounding per operation in the order written, no FMA (tests/glossy_model.py is the numpy form,
@@ -777,6 +825,10 @@ int pt_probe_shade_scatter_bumped(int iter, int depth, const pt_material *materi
                                   const pt_geom *geoms, int num_geoms, const int32_t *hit_geom, const float *tex_texels,
                                   const int32_t *tex_n, const int32_t *tex_offset, const float *bump_texels, const int32_t *bump_n,
                                   const int32_t *bump_offset);
+/* pt_probe_smooth_normal: pt_smooth_normal's arguments, results and refusals (plus count above 2^26) through the function the
+ * kernels call (csrc/pt_smooth.hpp: smooth_normal), one lane per record.  No session is needed; count == 0 launches nothing. */
+int pt_probe_smooth_normal(const pt_triangle *triangles, const float *normals, int num_triangles, const int32_t *tri, const float *origins,
+                           const float *dirs, int count, float *out_normals, uint8_t *smoothed);
 /* pt_probe_direct_sample: PT_DIRECT_LIGHT's sampler (above; csrc/pt_device.hpp: direct_sample) on the device through the function
  * the kernels call, one lane per record: for each of `count` (P, n, engine seed) triples (P, n: count x 3 floats; seeded like
  * pt_probe_hemisphere) the direction (count x 3), the weight and the element picked, on the light table of the scene given as for

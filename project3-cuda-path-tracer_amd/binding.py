@@ -43,6 +43,7 @@ PT_GLOSSY = 4096            # SPECEX gives mirrors and dielectrics a GGX lobe (i
 PT_DIRECT_LIGHT = 8192      # the last bounce aims a final ray at a sampled light (include/ptmi355.h)
 PT_DIRECT_SKY = 32768       # ... and the environment map is one more light element (with PT_DIRECT_LIGHT; include/ptmi355.h)
 PT_TEXTURES = 16384         # a cube texture per material tints spheres and cubes (include/ptmi355.h)
+PT_SMOOTH_NORMALS = 65536   # per-vertex normals smooth the shading of triangle meshes (include/ptmi355.h)
 BVH_NODE_WORDS = 16
 
 
@@ -208,6 +209,10 @@ def library():
                                          C.c_void_p, C.c_void_p]
             L.pt_probe_bump_normal.argtypes = L.pt_bump_normal.argtypes
             L.pt_probe_shade_scatter_bumped.argtypes = L.pt_probe_shade_scatter_textured.argtypes + [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_set_vertex_normals.argtypes = [C.c_void_p, C.c_int]
+            L.pt_get_vertex_normals.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+            L.pt_smooth_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_probe_smooth_normal.argtypes = L.pt_smooth_normal.argtypes
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -239,15 +244,18 @@ def has_experiments():
 
 
 def pathtraceInit(scene, flags=PT_COMPACT, device=0, stream=None, tile=(0, 1, 8), max_batch=1,
-                  device_image=None, lens=(0.0, 0.0), devices=None, pin_image=True, host_sparse=False):
+                  device_image=None, lens=(0.0, 0.0), devices=None, pin_image=True, host_sparse=False, vertex_normals=None):
     """pathtraceInit(Scene*) (pathtrace.cu:79-98) + the run-time toggles of include/ptmi355.h.
     devices=[d0, d1, ...]: the frame tiled over several GPUs inside the library (tile[2] = rows per strip).
     pin_image: PT_PIN_IMAGE -- pathtrace() below always hands over scene.image, which lives as long as the scene
     (like the reference's scene->state.image); callers that pass their own short-lived buffers to pt_trace say False.
     host_sparse: PT_HOST_SPARSE -- the caller only READS the image between calls, so a call writes just the pixels whose
     sum changed; pathtrace() then returns a read-only view of scene.image (a host that scribbles on it gets an error
-    instead of stale pixels)."""
+    instead of stale pixels).
+    vertex_normals: [num_triangles, 3, 3] float32 -- sets PT_SMOOTH_NORMALS and uploads them (set_vertex_normals)."""
     global _scene, _host_sparse
+    if vertex_normals is not None:
+        flags |= PT_SMOOTH_NORMALS
     _host_sparse = bool(host_sparse or (flags & PT_HOST_SPARSE))
     d = _SceneDesc()
     d.geoms, d.num_geoms = _p(scene.geoms), len(scene.geoms)
@@ -268,6 +276,8 @@ def pathtraceInit(scene, flags=PT_COMPACT, device=0, stream=None, tile=(0, 1, 8)
         d.devices, d.num_devices = _p(devs), len(devs)
     _chk(library().pt_init(C.byref(d)))
     _scene = scene
+    if vertex_normals is not None:
+        set_vertex_normals(vertex_normals)
 
 
 def pathtraceFree():
@@ -557,6 +567,66 @@ def get_bump_map(material):
     out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
     _chk(L.pt_get_bump_map(int(material), _p(out), 6 * n.value * n.value, C.byref(n)))
     return out
+
+
+def _vertex_normals(who, normals):
+    n = np.ascontiguousarray(normals, dtype=np.float32)
+    if n.size % 9:
+        raise PtError("%s: %s is not 9 floats per triangle" % (who, n.shape))
+    return n.reshape(-1, 3, 3)
+
+
+def set_vertex_normals(normals):
+    """The per-vertex normals of the session's triangles (include/ptmi355.h: pt_set_vertex_normals): [num_triangles, 3, 3]
+    float32, world space, in the order of the scene's triangles; None removes them.  The running sum is not touched."""
+    if normals is None:
+        _chk(library().pt_set_vertex_normals(None, 0))
+        return
+    n = _vertex_normals("set_vertex_normals", normals)
+    _chk(library().pt_set_vertex_normals(_p(n), len(n)))
+
+
+def get_vertex_normals():
+    """The session's vertex normals as they were set, [num_triangles, 3, 3] float32, or None."""
+    k = C.c_int(0)
+    L = library()
+    rc = L.pt_get_vertex_normals(None, 0, C.byref(k))             # the size: PT_OK with 0 when none are set
+    if k.value == 0:
+        _chk(rc)
+        return None
+    out = np.zeros((k.value, 3, 3), dtype=np.float32)
+    _chk(L.pt_get_vertex_normals(_p(out), k.value, C.byref(k)))
+    return out
+
+
+def _smooth_records(who, triangles, normals, tri, origins, dirs):
+    t = np.ascontiguousarray(triangles, dtype=TRI_DT).reshape(-1)
+    n = _vertex_normals(who, normals)
+    k = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1)
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    if len(n) != len(t) or len(o) != len(k) or len(d) != len(k):
+        raise PtError("%s: %d triangles, %d normal triples, %d records, %d origins, %d directions" % (who, len(t), len(n), len(k), len(o), len(d)))
+    return t, n, k, o, d
+
+
+def smooth_normal(triangles, normals, tri, origins, dirs):
+    """Host-only: the shading normal of each (triangle, ray) record under per-vertex normals (include/ptmi355.h:
+    pt_smooth_normal).  Returns (normals [count, 3] float32, smoothed [count] bool)."""
+    t, n, k, o, d = _smooth_records("smooth_normal", triangles, normals, tri, origins, dirs)
+    out = np.zeros((len(k), 3), dtype=np.float32)
+    flag = np.zeros(len(k), dtype=np.uint8)
+    _chk(library().pt_smooth_normal(_p(t), _p(n), len(t), _p(k), _p(o), _p(d), len(k), _p(out), _p(flag)))
+    return out, flag.astype(bool)
+
+
+def probe_smooth_normal(triangles, normals, tri, origins, dirs):
+    """smooth_normal on the device through the function the kernels call (include/ptmi355.h: pt_probe_smooth_normal)."""
+    t, n, k, o, d = _smooth_records("probe_smooth_normal", triangles, normals, tri, origins, dirs)
+    out = np.zeros((len(k), 3), dtype=np.float32)
+    flag = np.zeros(len(k), dtype=np.uint8)
+    _chk(library().pt_probe_smooth_normal(_p(t), _p(n), len(t), _p(k), _p(o), _p(d), len(k), _p(out), _p(flag)))
+    return out, flag.astype(bool)
 
 
 def studs_bumpmap(n, cells, slope):

@@ -855,6 +855,23 @@ PTD bool shade_scatter(PathState &ps, float t, f3 n, int matId, int outside, con
     return false;
 }
 
+// The shader about a shading normal n that may differ from the normal nr the intersection test reported (`perturbed`: bump
+// mapping; smooth mesh normals, section 6.26), and the guard behind it.  A perturbed lane never defers
+// its diffuse direction: the guard needs it -- a mirror's or a diffuse surface's new direction that does not leave the surface
+// the intersection test reported is reflected about nr, not renormalised.  Dielectrics keep what comes out.
+// TEX: `mcol` stands where material.color stands (shade_scatter<.., TEX>).
+template <bool GLOSSY, bool TEX>
+PTD bool shade_scatter_about(PathState &ps, float t, f3 n, f3 nr, bool perturbed, int matId, int outside, const float *mats, int iter,
+                             int pixel, int depth, bool last_bounce, bool defer_diffuse, bool *deferred, bool *missed, const f3 *mcol) {
+    const bool alive = shade_scatter<GLOSSY, false, TEX>(ps, t, n, matId, outside, mats, iter, pixel, depth, last_bounce,
+                                                         defer_diffuse && !perturbed, deferred, missed, nullptr, 0, mcol);
+    if (perturbed && alive) {
+        const float *m = mats + matId * MAT_WORDS;
+        if ((m[6] > 0.0f || !(m[7] > 0.0f)) && !(dot(ps.d, nr) > 0.0f)) ps.d = reflect(ps.d, nr);
+    }
+    return alive;
+}
+
 // The TEX form as tile_shade calls it (DESIGN.md sections 6.19 and 6.22): mcol from the material's colour texture, the shading
 // normal from its bump map, then shade_scatter<GLOSSY, false, true> about that normal.  A perturbed lane never defers its
 // diffuse direction: the guard needs it -- a mirror's or a diffuse surface's new direction that does not leave the surface
@@ -867,13 +884,22 @@ PTD bool shade_scatter_tex(PathState &ps, float t, f3 nr, int matId, int outside
     f3 mcol = mk(0.0f, 0.0f, 0.0f), n = nr;
     bool bumped = false;
     if (t > 0.0f) mcol = texture_bump_mcol(mats, matId, type, rec, ps.o, ps.d, t, nr, tab, texels, btab, bumps, !last_bounce, n, bumped);
-    const bool alive = shade_scatter<GLOSSY, false, true>(ps, t, n, matId, outside, mats, iter, pixel, depth, last_bounce,
-                                                          defer_diffuse && !bumped, deferred, missed, nullptr, 0, &mcol);
-    if (bumped && alive) {
-        const float *m = mats + matId * MAT_WORDS;
-        if ((m[6] > 0.0f || !(m[7] > 0.0f)) && !(dot(ps.d, nr) > 0.0f)) ps.d = reflect(ps.d, nr);
-    }
-    return alive;
+    return shade_scatter_about<GLOSSY, true>(ps, t, n, nr, bumped, matId, outside, mats, iter, pixel, depth, last_bounce, defer_diffuse,
+                                             deferred, missed, &mcol);
+}
+
+// smooth shading of triangle meshes (PT_SMOOTH_NORMALS): per-vertex normals replace the facet normal
+// (steps 1-5, host and device, plain C++: pt_smooth.hpp -- ptd::smooth_normal)
+}  // namespace ptd
+#include "pt_smooth.hpp"
+namespace ptd {
+// The SMOOTH form as tile_shade calls it: `smoothed` lanes (mesh hits whose interpolated normal passed steps 2, 4 and 5) shade
+// about ns, then take section 6.22's guard with the facet normal nr; every other lane is the plain call.
+template <bool GLOSSY>
+PTD bool shade_scatter_smooth(PathState &ps, float t, f3 nr, f3 ns, bool smoothed, int matId, int outside, const float *mats, int iter,
+                              int pixel, int depth, bool last_bounce, bool defer_diffuse, bool *deferred, bool *missed) {
+    return shade_scatter_about<GLOSSY, false>(ps, t, smoothed ? ns : nr, nr, smoothed, matId, outside, mats, iter, pixel, depth, last_bounce,
+                                              defer_diffuse, deferred, missed, nullptr);
 }
 
 #undef PTD

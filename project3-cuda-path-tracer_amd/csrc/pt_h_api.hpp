@@ -49,6 +49,7 @@ void pt_free(void) {
     if (R.d_tex_tab) (void)hipFree(R.d_tex_tab);
     if (R.d_bump) (void)hipFree(R.d_bump);
     if (R.d_bump_tab) (void)hipFree(R.d_bump_tab);
+    if (R.d_vnormals) (void)hipFree(R.d_vnormals);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
     if (R.d_bvh_nodes) (void)hipFree(R.d_bvh_nodes);
@@ -193,6 +194,19 @@ static int init_impl(const pt_scene_desc *d) {
             return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_CACHE_FIRST (the table form of bounce 0 has no TEX variant)");
         if (d->flags & PT_DIRECT_LIGHT)
             return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with PT_DIRECT_LIGHT (the direct kernels have no textured form yet)");
+    }
+    // PT_SMOOTH_NORMALS: the smoothing needs the winning triangle and a second normal for the guard, which
+    // the intersection planes and the first-hit table do not carry (the two-kernel sort is refused further down); the combined
+    // forms with the TEX and DIRECT kernels are a later change; PT_FAKE_SHADER ignores the flag
+    if ((d->flags & PT_SMOOTH_NORMALS) && !(d->flags & PT_FAKE_SHADER)) {
+        if (d->flags & PT_UNFUSED)
+            return fail(PT_ERR_INVALID, "pt_init: PT_SMOOTH_NORMALS cannot be combined with PT_UNFUSED (its intersection planes carry one normal and no triangle)");
+        if (d->flags & PT_CACHE_FIRST)
+            return fail(PT_ERR_INVALID, "pt_init: PT_SMOOTH_NORMALS cannot be combined with PT_CACHE_FIRST (the table form of bounce 0 has no SMOOTH variant)");
+        if (d->flags & PT_TEXTURES)
+            return fail(PT_ERR_INVALID, "pt_init: PT_SMOOTH_NORMALS cannot be combined with PT_TEXTURES (the textured kernels have no smooth form yet)");
+        if (d->flags & PT_DIRECT_LIGHT)
+            return fail(PT_ERR_INVALID, "pt_init: PT_SMOOTH_NORMALS cannot be combined with PT_DIRECT_LIGHT (the direct kernels have no smooth form yet)");
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -418,6 +432,9 @@ static int init_impl(const pt_scene_desc *d) {
     if ((R.flags & PT_TEXTURES) && !(R.flags & PT_FAKE_SHADER) && (R.flags & PT_SORT_MATERIAL) && !R.sort_keys)
         return fail(PT_ERR_INVALID, "pt_init: PT_TEXTURES cannot be combined with the two-kernel form of PT_SORT_MATERIAL, which this "
                                     "session would take (its intersection planes do not carry the winning primitive)");
+    if ((R.flags & PT_SMOOTH_NORMALS) && !(R.flags & PT_FAKE_SHADER) && (R.flags & PT_SORT_MATERIAL) && !R.sort_keys)
+        return fail(PT_ERR_INVALID, "pt_init: PT_SMOOTH_NORMALS cannot be combined with the two-kernel form of PT_SORT_MATERIAL, which this "
+                                    "session would take (its intersection planes carry one normal and no triangle)");
     if (!light_el.empty()) {
         std::vector<float> lrec;
         ptlight::records(d->geoms, light_el, lrec);
@@ -484,20 +501,22 @@ static int init_impl(const pt_scene_desc *d) {
         // for its last two bounces
         auto size_for = [&](auto sh) -> int {
             constexpr int SH = decltype(sh)::value;
+            // (the forms without a mesh have no SMOOTH variant: a session that launches the SMOOTH forms has a mesh, and `own` is false)
+            constexpr int SHN = SH & ~SH_SMOOTH;
             const void *fns[2];
             if (R.mesh_mode == MESH_BVH) { fns[0] = bounce_fn<MESH_PRE, SH>(R.scene_lds, false, false); fns[1] = bounce_fn<MESH_PRE, SH>(R.scene_lds, true, false); }
             else if (R.mesh_mode == MESH_TILES) { fns[0] = bounce_fn<MESH_TILES, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_TILES, SH>(R.scene_lds, true, sorted); }
-            else { fns[0] = bounce_fn<MESH_NONE, SH>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE, SH>(R.scene_lds, true, sorted); }
-            const void *fns_own[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true) : fns[1]};
+            else { fns[0] = bounce_fn<MESH_NONE, SHN>(R.scene_lds, false, sorted); fns[1] = bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, sorted); }
+            const void *fns_own[2] = {own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, true) : fns[1]};
             // (... and the table form of bounce 0, stepped or generating, with and without the own-surface bits: enqueue_bounce)
-            const void *fns_tab[4] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true) : fns[1],
-                                      own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, false, false, true, true) : fns[0], own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true) : fns[1]};
+            const void *fns_tab[4] = {own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, false, false, false, true) : fns[0], own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, false, true) : fns[1],
+                                      own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, false, false, true, true) : fns[0], own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, true, true) : fns[1]};
             // (... and the launch that does bounces 0 and 1, with and without the own-surface form)
-            const void *fns_two[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true, true) : fns[0],
-                                      own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true, true) : fns[0]};
+            const void *fns_two[2] = {own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, false, true, true) : fns[0],
+                                      own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, true, true, true) : fns[0]};
             // (... and its first-state form)
-            const void *fns_state[2] = {own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, false, true, true, true) : fns[0],
-                                        own ? bounce_fn<MESH_NONE, SH>(R.scene_lds, true, false, true, true, true, true) : fns[0]};
+            const void *fns_state[2] = {own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, false, true, true, true) : fns[0],
+                                        own ? bounce_fn<MESH_NONE, SHN>(R.scene_lds, true, false, true, true, true, true) : fns[0]};
             for (const void *f : {fns[0], fns[1], fns_own[0], fns_own[1], fns_tab[0], fns_tab[1], fns_tab[2], fns_tab[3], fns_two[0], fns_two[1],
                                   fns_state[0], fns_state[1]}) {
                 int n = 0;
@@ -511,6 +530,10 @@ static int init_impl(const pt_scene_desc *d) {
         if (rc == PT_OK && (R.nlights > 0 || sky_session())) rc = size_for(std::integral_constant<int, SH_DIRECT>{});
         // (a PT_TEXTURES session launches the TEX forms whenever a texture is set: pt_set_texture comes after this)
         if (rc == PT_OK && (R.flags & PT_TEXTURES) && !(R.flags & PT_FAKE_SHADER)) rc = size_for(std::integral_constant<int, SH_TEX>{});
+        // (a PT_SMOOTH_NORMALS session with a mesh launches the SMOOTH forms whenever normals are set: pt_set_vertex_normals comes
+        // after this.  Only the mesh kernels have them.)
+        if (rc == PT_OK && (R.flags & PT_SMOOTH_NORMALS) && !(R.flags & PT_FAKE_SHADER) && R.mesh_mode != MESH_NONE)
+            rc = size_for(std::integral_constant<int, SH_SMOOTH>{});
         if (rc != PT_OK) return rc;
     }
     if (per_cu < 1) per_cu = 1;
@@ -921,6 +944,57 @@ int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
     if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
         return fail(PT_ERR_INVALID, "pt_get_bump_map: room for %d texels, the map has %zu", texels ? capacity_texels : 0, count);
     memcpy(texels, R.bump_keep[(size_t)material].data(), count * 12);
+    return PT_OK;
+}
+
+// Smooth shading of triangle meshes (include/ptmi355.h): pt_set_bump_map's contract with one array -- nine
+// floats per triangle, in the order of pt_scene_desc::triangles.  pt_gbuffer, pt_albedo and the filters keep the facet normal, so
+// nothing of theirs goes stale.
+int pt_set_vertex_normals(const float *normals, int num_triangles) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: not initialised");
+    if (!(R.flags & PT_SMOOTH_NORMALS)) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS");
+    if (num_triangles < 0) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: num_triangles = %d", num_triangles);
+    if (num_triangles > 0 && !normals) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: null normals with num_triangles = %d", num_triangles);
+    if (!normals) num_triangles = 0;
+    if (num_triangles != 0 && num_triangles != R.desc.num_triangles)
+        return fail(PT_ERR_INVALID, "pt_set_vertex_normals: %d triangles, the session has %d", num_triangles, R.desc.num_triangles);
+    const int rc = la_discard(LA_HOST);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(R.stream));
+    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
+        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
+        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
+    }
+    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    R.ov_active = false;
+    const size_t words = (size_t)num_triangles * 9;
+    // (PT_FAKE_SHADER ignores the flag: the normals are kept for pt_get_vertex_normals and no kernel reads them)
+    float *d_new = nullptr;
+    if (words > 0) {
+        if (hipMalloc((void **)&d_new, words * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PT_ERR_NOMEM, "pt_set_vertex_normals: %zu bytes of device memory for the session's vertex normals", words * 4);
+        }
+        HIPCHK(hipMemcpy(d_new, normals, words * 4, hipMemcpyHostToDevice));
+    }
+    if (R.d_vnormals) (void)hipFree(R.d_vnormals);
+    R.d_vnormals = d_new;
+    if (words > 0) R.vn_keep.assign(normals, normals + words);
+    else std::vector<float>().swap(R.vn_keep);
+    return PT_OK;
+}
+
+int pt_get_vertex_normals(float *normals, int capacity_triangles, int *num_triangles) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: not initialised");
+    if (!(R.flags & PT_SMOOTH_NORMALS)) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS");
+    if (!num_triangles) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: null num_triangles");
+    const size_t count = R.vn_keep.size() / 9;
+    *num_triangles = (int)count;
+    if (count == 0) return PT_OK;
+    if (!normals || capacity_triangles < 0 || (size_t)capacity_triangles < count)
+        return fail(PT_ERR_INVALID, "pt_get_vertex_normals: room for %d triangles, the session has %zu", normals ? capacity_triangles : 0, count);
+    memcpy(normals, R.vn_keep.data(), count * 36);
     return PT_OK;
 }
 

@@ -36,6 +36,7 @@ BounceArgs bounce_args(int depth) {
     a.lights = R.d_lights; a.nlights = R.nlights;
     if (R.ntex + R.nbump > 0) { a.tex = R.d_tex; a.tex_tab = R.d_tex_tab; }
     if (R.nbump > 0) { a.bumps = R.d_bump; a.bump_tab = R.d_bump_tab; }
+    a.vnormals = R.d_vnormals;                                  // (null while none are set)
     return a;
 }
 
@@ -200,6 +201,15 @@ void launch_k_bounce(const BounceArgs &a) {
             if (a.tex_tab != nullptr) {
                 PT_SHADE_DISPATCH_WITH(SH_TEX, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
                 return;
+            }
+            // PT_SMOOTH_NORMALS: while the session has vertex normals set, every bounce launches the
+            // SMOOTH forms; a flagged session without them launches what a session without the flag does (bounce_args leaves
+            // vnormals null).  Only a session with a mesh has them (pt_set_vertex_normals wants one normal triple per triangle).
+            if constexpr (MESH != MESH_NONE) {
+                if (a.vnormals != nullptr) {
+                    PT_SHADE_DISPATCH_WITH(SH_SMOOTH, hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));
+                    return;
+                }
             }
         }
         PT_SHADE_DISPATCH(hipLaunchKernelGGL((k_bounce<MODE, COMPACT, MESH, SLDS, GEN, SORT, OWN, SH>), dim3(R.grid), dim3(BLOCK), R.lds_bytes, R.stream, a));

@@ -108,6 +108,11 @@ struct Renderer {
     ptd::bump_texel *d_bump = nullptr;
     int2 *d_bump_tab = nullptr;
     int nbump = 0;
+    // PT_SMOOTH_NORMALS: the per-vertex normals, 9 floats per triangle in the order of
+    // pt_scene_desc::triangles -- vn_keep as the caller gave them (pt_get_vertex_normals), d_vnormals the device's copy.  Null /
+    // empty: none set; otherwise the SMOOTH forms, a kernel per bounce.
+    std::vector<float> vn_keep;
+    float *d_vnormals = nullptr;
     size_t lds_bytes = 0;
     Control *ctl = nullptr;
     Persist *persist = nullptr;

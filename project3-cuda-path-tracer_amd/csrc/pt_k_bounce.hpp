@@ -260,9 +260,12 @@ template <bool COMPACT, int MESH = MESH_NONE, bool SORT = false, bool DEFER = fa
 __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c, const Pool &in, const Pool &out, int depth,
                                            const TileRegs &tr, f3 ro, f3 rd, float t, f3 nrm, int mat, int outside,
                                            uint32_t n, uint32_t dst_base, uint32_t &packed, uint32_t &traced,
-                                           uint32_t key_stride = 0, uint32_t own_bits = 0, int geom = -1) {
+                                           uint32_t key_stride = 0, uint32_t own_bits = 0, int geom = -1,
+                                           f3 ns = f3{0.0f, 0.0f, 0.0f}, bool smoothed = false) {
     constexpr bool ENV = (SH & SH_ENV) != 0, GLOSSY = (SH & SH_GLOSSY) != 0, DIRECT = (SH & SH_DIRECT) != 0, TEX = (SH & SH_TEX) != 0;
+    constexpr bool SMOOTH = (SH & SH_SMOOTH) != 0;
     static_assert(!(DIRECT && TEX), "pt_init refuses PT_TEXTURES with PT_DIRECT_LIGHT");
+    static_assert(!(SMOOTH && (TEX || DIRECT)), "pt_init refuses PT_SMOOTH_NORMALS with PT_TEXTURES and with PT_DIRECT_LIGHT");
     const int lane = c.lane;
     bool alive = false, deferred = false, missed = false;
     ptd::PathState ps;
@@ -328,6 +331,10 @@ __device__ __forceinline__ void tile_shade(const BounceArgs &a, const TileCtx &c
                                    c.kargs ? karg_field<const int2 *>(offsetof(BounceArgs, tex_tab)) : a.tex_tab,
                                    c.kargs ? karg_field<const float4 *>(offsetof(BounceArgs, tex)) : a.tex, btab,
                                    c.kargs ? karg_field<const ptd::bump_texel *>(offsetof(BounceArgs, bumps)) : a.bumps);
+        } else if constexpr (SMOOTH) {
+            // (tile_finish has run steps 1-5 of section 6.26 for the lanes whose winner is a mesh triangle: `smoothed`, ns)
+            alive = ptd::shade_scatter_smooth<GLOSSY>(ps, t, nrm, ns, smoothed, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
+                                   depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr);
         } else {
             alive = ptd::shade_scatter<GLOSSY>(ps, t, nrm, mat, outside, c.acc.mats, c.iter0 + (int)tr.smp, tr.pixel, depth,
                                    depth == a.trace_depth - 1, defer, &deferred, ENV ? &missed : nullptr);
@@ -387,9 +394,25 @@ __device__ __forceinline__ void tile_finish(const BounceArgs &a, const TileCtx &
     float t = -1.0f; f3 nrm = ptd::mk(0, 0, 0); int mat = 0, outside = 1;
     int geom = -1;
     if (tr.active) tile_result(q, par, c.acc, a.scene.tris, tr.mb, t, nrm, mat, outside, geom);
-    // OWN: the launch plan admits scenes of up to OWN_MAX_GEOMS primitives, so geom + 1 fits the pid's four bits
-    tile_shade<COMPACT, MESH, SORT, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
-                                           OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom);
+    if constexpr ((SH & SH_SMOOTH) != 0) {
+        // PT_SMOOTH_NORMALS: the lanes whose winner is a mesh triangle (tile_result took MeshBest's hit:
+        // only a mesh primitive carries that number) gather its three vertex normals -- 36 B at the original triangle index --
+        // and run steps 1-5 on the triangle record tile_result read; the shader then runs about ns, the guard with nrm
+        f3 ns = nrm;
+        bool smoothed = false;
+        // (not at the last bounce, whose shader reads no normal and leaves no survivor)
+        if (tr.active && t > 0.0f && tr.mb.geom >= 0 && geom == tr.mb.geom && depth != a.trace_depth - 1) {
+            const float *vn = (c.kargs ? karg_field<const float *>(offsetof(BounceArgs, vnormals)) : a.vnormals) + (size_t)tr.mb.tri * 9;
+            smoothed = ptd::smooth_normal(a.scene.tris + (size_t)tr.mb.tri * TRI_WORDS, vn, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z,
+                                          nrm.x, nrm.y, nrm.z, ns.x, ns.y, ns.z);
+        }
+        tile_shade<COMPACT, MESH, SORT, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
+                                               OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom, ns, smoothed);
+    } else {
+        // OWN: the launch plan admits scenes of up to OWN_MAX_GEOMS primitives, so geom + 1 fits the pid's four bits
+        tile_shade<COMPACT, MESH, SORT, DEFER, SH>(a, c, in, out, depth, tr, ro, rd, t, nrm, mat, outside, n, dst_base, packed, traced, key_stride,
+                                               OWN ? (uint32_t)(geom + 1) << OWN_SHIFT : 0u, geom);
+    }
     if constexpr (FIRST && (SH & SH_ENV) != 0) {
         if (tr.miss0)
             put_final(karg_field<float *>(offsetof(BounceArgs, fin)), tr.pid,
@@ -560,6 +583,7 @@ __global__ __launch_bounds__(BLOCK, MESH == MESH_TILES ? PT_LOOP_WAVES : (MESH =
     // (the launch of bounces 0 and 1: BounceArgs::depth is 1 -- directory, election and scan are bounce 1's -- and the paths are generated)
     static_assert(!mode_first2(MODE) || (COMPACT && MESH == MESH_NONE && GEN && !SORT), "MODE_FIRST2 / MODE_STATE2: the plain compacting pipeline's first launch");
     static_assert(MODE != MODE_STATE2 || SH == 0, "MODE_STATE2: sessions without environment map or lobes");
+    static_assert((SH & SH_SMOOTH) == 0 || (MODE == MODE_FUSED && MESH != MESH_NONE), "the SMOOTH forms: the fused kernel of a session with a mesh");
 #ifdef PT_WAVE_TIMES
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif

@@ -791,6 +791,19 @@ int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
     return on_one(0, [&](Worker &) -> int { return one::pt_get_bump_map(material, texels, capacity_texels, n); });
 }
 
+// ... and the same vertex normals: every context holds the whole scene, so each takes the whole array
+int pt_set_vertex_normals(const float *normals, int num_triangles) {
+    if (!G.live) return one::pt_set_vertex_normals(normals, num_triangles);
+    const int rc = multi_sync();
+    if (rc) return rc;
+    return on_all([&](Worker &) -> int { return one::pt_set_vertex_normals(normals, num_triangles); });
+}
+
+int pt_get_vertex_normals(float *normals, int capacity_triangles, int *num_triangles) {
+    if (!G.live) return one::pt_get_vertex_normals(normals, capacity_triangles, num_triangles);
+    return on_one(0, [&](Worker &) -> int { return one::pt_get_vertex_normals(normals, capacity_triangles, num_triangles); });
+}
+
 int pt_synchronize(void) {
     if (!G.live) return one::pt_synchronize();
     return multi_sync();

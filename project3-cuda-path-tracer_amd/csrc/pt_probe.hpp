@@ -180,6 +180,23 @@ __global__ __launch_bounds__(64) void k_probe_bump_normal(const float *__restric
     perturbed[i] = hit ? 1 : 0;
 }
 
+// smooth mesh normals through the kernels' own ptd::smooth_normal: one lane per (triangle, ray) record.
+// rec: the device's triangle records (TRI_WORDS each: v0, e1, e2); vn: nine floats per triangle.  The reported normal is the
+// facet normal tile_result computes.
+__global__ __launch_bounds__(64) void k_probe_smooth_normal(const float *__restrict__ rec, const float *__restrict__ vn, const int32_t *__restrict__ tri,
+                                                             const float *__restrict__ origins, const float *__restrict__ dirs, int count,
+                                                             float *__restrict__ out_normals, uint8_t *__restrict__ smoothed) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const float *tv = rec + (size_t)tri[i] * TRI_WORDS;
+    const ptd::f3 nr = ptd::normalize(ptd::cross(ptd::mk(tv[3], tv[4], tv[5]), ptd::mk(tv[6], tv[7], tv[8])));
+    float x = nr.x, y = nr.y, z = nr.z;
+    const bool hit = ptd::smooth_normal(tv, vn + (size_t)tri[i] * 9, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2],
+                                        dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], nr.x, nr.y, nr.z, x, y, z);
+    out_normals[3 * i] = x; out_normals[3 * i + 1] = y; out_normals[3 * i + 2] = z;
+    smoothed[i] = hit ? 1 : 0;
+}
+
 // k_probe_shade_scatter_textured through ptd::shade_scatter_tex, the call of tile_shade<.., SH_TEX>: lookup, shader, guard
 __global__ __launch_bounds__(64) void k_probe_shade_scatter_bumped(int iter, int depth, const float *__restrict__ mats, pt_path_segment *paths,
                                                                     const pt_shadeable_intersection *__restrict__ isects,
@@ -868,6 +885,76 @@ int pt_probe_bump_normal(const pt_geom *geoms, int num_geoms, const int32_t *hit
     HIPCHK(hipGetLastError());
     HIPCHK(b.fetch(out_normals, d_out, 3 * (size_t)count));
     HIPCHK(b.fetch(perturbed, d_flag, (size_t)count));
+    HIPCHK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+// ---- smooth mesh normals (PT_SMOOTH_NORMALS) ----
+namespace {
+int smooth_args(const char *who, const pt_triangle *triangles, const float *normals, int num_triangles, const int32_t *tri, const float *origins,
+                const float *dirs, int count, float *out_normals, uint8_t *smoothed) {
+    if (count < 0 || num_triangles < 0) return fail(PT_ERR_INVALID, "%s: bad argument (count %d, num_triangles %d)", who, count, num_triangles);
+    if ((num_triangles > 0 && (!triangles || !normals)) || (count > 0 && (!tri || !origins || !dirs || !out_normals || !smoothed)))
+        return fail(PT_ERR_INVALID, "%s: null array (count %d)", who, count);
+    for (int i = 0; i < count; ++i)
+        if (tri[i] < 0 || tri[i] >= num_triangles) return fail(PT_ERR_INVALID, "%s: tri[%d] = %d outside [0, %d)", who, i, tri[i], num_triangles);
+    return PT_OK;
+}
+// the triangles as the device records hold them (pt_init): v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0)
+std::vector<float> smooth_records(const pt_triangle *triangles, int num_triangles) {
+    std::vector<float> rec((size_t)std::max(1, num_triangles) * TRI_WORDS, 0.0f);
+    for (int i = 0; i < num_triangles; ++i) {
+        const pt_triangle &t = triangles[i];
+        float *r = rec.data() + (size_t)i * TRI_WORDS;
+        r[0] = t.v0.x; r[1] = t.v0.y; r[2] = t.v0.z;
+        r[3] = t.v1.x - t.v0.x; r[4] = t.v1.y - t.v0.y; r[5] = t.v1.z - t.v0.z;
+        r[6] = t.v2.x - t.v0.x; r[7] = t.v2.y - t.v0.y; r[8] = t.v2.z - t.v0.z;
+    }
+    return rec;
+}
+}  // namespace
+
+int pt_smooth_normal(const pt_triangle *triangles, const float *normals, int num_triangles, const int32_t *tri, const float *origins,
+                     const float *dirs, int count, float *out_normals, uint8_t *smoothed) {
+    const int rc = smooth_args("pt_smooth_normal", triangles, normals, num_triangles, tri, origins, dirs, count, out_normals, smoothed);
+    if (rc) return rc;
+    const std::vector<float> rec = smooth_records(triangles, num_triangles);
+    for (int i = 0; i < count; ++i) {
+        const float *tv = rec.data() + (size_t)tri[i] * TRI_WORDS;
+        // the facet normal of tile_result: glm's normalize(cross(e1, e2))
+        const float cx = tv[4] * tv[8] - tv[7] * tv[5], cy = tv[5] * tv[6] - tv[8] * tv[3], cz = tv[3] * tv[7] - tv[6] * tv[4];
+        const float inv_len = 1.0f / __builtin_sqrtf((cx * cx + cy * cy) + cz * cz);
+        const float nrx = cx * inv_len, nry = cy * inv_len, nrz = cz * inv_len;
+        float x = nrx, y = nry, z = nrz;
+        const bool hit = ptd::smooth_normal(tv, normals + (size_t)tri[i] * 9, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2],
+                                            dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], nrx, nry, nrz, x, y, z);
+        out_normals[3 * i] = x; out_normals[3 * i + 1] = y; out_normals[3 * i + 2] = z;
+        smoothed[i] = hit ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+int pt_probe_smooth_normal(const pt_triangle *triangles, const float *normals, int num_triangles, const int32_t *tri, const float *origins,
+                           const float *dirs, int count, float *out_normals, uint8_t *smoothed) {
+    // (the bound on the count first: smooth_args reads every tri entry)
+    if (count > (1 << 26)) return fail(PT_ERR_INVALID, "pt_probe_smooth_normal: bad argument (count %d)", count);
+    const int rc = smooth_args("pt_probe_smooth_normal", triangles, normals, num_triangles, tri, origins, dirs, count, out_normals, smoothed);
+    if (rc) return rc;
+    if (count == 0) return PT_OK;
+    const std::vector<float> rec = smooth_records(triangles, num_triangles);
+    ProbeBufs b;
+    const float *d_rec = b.in(rec.data(), rec.size());
+    const float *d_vn = b.in(normals, 9 * (size_t)num_triangles);
+    const int32_t *d_tri = b.in(tri, (size_t)count);
+    const float *d_org = b.in(origins, 3 * (size_t)count);
+    const float *d_dir = b.in(dirs, 3 * (size_t)count);
+    float *d_out = b.out<float>(3 * (size_t)count);
+    uint8_t *d_flag = b.out<uint8_t>((size_t)count);
+    if (!b.ok()) return probe_no_device("pt_probe_smooth_normal");
+    hipLaunchKernelGGL(k_probe_smooth_normal, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, d_rec, d_vn, d_tri, d_org, d_dir, count, d_out, d_flag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(b.fetch(out_normals, d_out, 3 * (size_t)count));
+    HIPCHK(b.fetch(smoothed, d_flag, (size_t)count));
     HIPCHK(hipDeviceSynchronize());
     return PT_OK;
 }

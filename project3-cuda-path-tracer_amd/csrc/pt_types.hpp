@@ -384,6 +384,11 @@ struct BounceArgs {
     float *first_state;
     const uint32_t *first_ended;
     uint32_t first_ended_tiles;     // words in first_ended = tile_pixels / 64
+    // ... and PT_SMOOTH_NORMALS' per-vertex normals: 9 floats {n0, n1, n2} per triangle, indexed by the
+    // ORIGINAL triangle index (what MeshBest::tri holds in both mesh modes).  nullptr: the session has no flag or no normals set.
+    // Read by the SMOOTH instantiations of k_bounce, which such a session launches for every bounce, on the lanes whose winner
+    // is a mesh triangle.
+    const float *vnormals;
 };
 
 // The first-state record of a pixel (k_cache_first writes it, k_bounce<MODE_STATE2> reads it): a Pool slot whose rows hold what
@@ -403,7 +408,8 @@ enum : int {
     SH_ENV = 1,        // the session has an environment map
     SH_GLOSSY = 2,     // the session has PT_GLOSSY
     SH_DIRECT = 4,     // bounces D - 1 and D of a PT_DIRECT_LIGHT session (k_bounce only)
-    SH_TEX = 8         // every bounce of a PT_TEXTURES session while a texture is set (k_bounce only)
+    SH_TEX = 8,        // every bounce of a PT_TEXTURES session while a texture is set (k_bounce only)
+    SH_SMOOTH = 16     // every bounce of a PT_SMOOTH_NORMALS session while normals are set (k_bounce with a mesh only)
 };
 
 // what k_intersect needs to generate bounce 0's camera rays itself (sorted batches: no k_raygen, no pool to read)

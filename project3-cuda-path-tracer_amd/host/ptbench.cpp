@@ -7,6 +7,11 @@
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
 //           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]
+//           [--smooth]
+//
+// --smooth: PT_SMOOTH_NORMALS -- the `vn` normals of the scene's mesh files (pthost.h: pth_scene_vertex_normals) are uploaded with
+// pt_set_vertex_normals after pathtraceInit; mesh hits are shaded about the interpolated normal (include/ptmi355.h, DESIGN.md
+// section 6.26).  scenes/cornell_smooth.txt.  Without the switch the normals are loaded and ignored.
 //
 // --albedo (needs --denoise): pt_set_denoise_albedo(1) before the first filtered picture -- every one of them, the --move /
 // --temporal ones included, is filtered as colour / first-hit albedo and multiplied back (include/ptmi355.h, DESIGN.md section
@@ -86,7 +91,7 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo] [--smooth]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -130,6 +135,7 @@ int main(int argc, char **argv) {
             sun = true;
         }
         else if (a == "--textures") flags |= PT_TEXTURES;
+        else if (a == "--smooth") flags |= PT_SMOOTH_NORMALS;
         else if (a == "--albedo") albedo = true;
         else if (a == "--lens" && i + 2 < argc) { lens_radius = (float)atof(argv[++i]); focal_distance = (float)atof(argv[++i]); }
         else if (a == "--pfm") pfm = true;
@@ -268,6 +274,14 @@ int main(int argc, char **argv) {
             ++bumps;
         }
         if (bumps > 0) printf("bump maps: %d of %d materials\n", bumps, sc->num_materials);
+    }
+
+    if (flags & PT_SMOOTH_NORMALS) {                      // the `vn` normals of the scene's mesh files (pthost.h: pth_scene_vertex_normals)
+        const float *vn = nullptr;
+        int nt = 0;
+        if (pth_scene_vertex_normals(sc, &vn, &nt) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        if (nt > 0 && pt_set_vertex_normals(vn, nt) != PT_OK) { fprintf(stderr, "pt_set_vertex_normals: %s\n", pt_last_error()); return 1; }
+        printf("vertex normals: %d of %d triangles\n", nt, sc->num_triangles);
     }
 
     std::vector<float> image((size_t)W * H * 3, 0.0f);    // scene->state.image

@@ -257,12 +257,28 @@ struct Builder {
     std::vector<pt_material> mats;
     std::vector<pt_triangle> tris;
     std::vector<pt_mesh> meshes;
+    std::vector<float> vnormals;                     // nine floats per triangle of `tris` (load_obj)
+    bool any_vn = false;                             // some mesh file carried `vn` lines
 };
 
-bool load_obj(const std::string &path, const M4 &T, std::vector<pt_triangle> &out, std::string &err) {
+// the third index of a face entry "i//k" or "i/j/k" (0: the entry names no normal)
+int face_normal_index(const std::string &entry) {
+    const size_t a = entry.find('/');
+    if (a == std::string::npos) return 0;
+    const size_t b = entry.find('/', a + 1);
+    if (b == std::string::npos || b + 1 >= entry.size()) return 0;
+    return atoi(entry.c_str() + b + 1);
+}
+
+// `vn_out` receives nine floats per triangle appended to `out` -- the `vn` lines the face's corners name, each
+// multiplyMV(NT, (vn, 0)) with NT the geom's invTranspose and then normalised in binary32 (v * (1 / sqrt(dot(v, v)))); a
+// triangle with a corner that names no normal gets three zero normals (PT_SMOOTH_NORMALS: "this triangle stays faceted").
+// `any_vn` is set when the file carried a `vn` line.
+bool load_obj(const std::string &path, const M4 &T, const M4 &NT, std::vector<pt_triangle> &out, std::vector<float> &vn_out, bool &any_vn,
+              std::string &err) {
     std::ifstream f(path.c_str());
     if (!f.is_open()) { err = "cannot open mesh file " + path; return false; }
-    std::vector<V3> vs;
+    std::vector<V3> vs, vns;
     std::string line;
     while (std::getline(f, line)) {
         std::vector<std::string> t = tokens_of(line);
@@ -274,18 +290,36 @@ bool load_obj(const std::string &path, const M4 &T, std::vector<pt_triangle> &ou
             for (int r = 0; r < 3; ++r)
                 w[r] = (T.m[0][r] * p.x + T.m[1][r] * p.y) + (T.m[2][r] * p.z + T.m[3][r] * 1.0f);
             vs.push_back(v3(w[0], w[1], w[2]));
+        } else if (t[0] == "vn" && t.size() >= 4) {
+            const V3 n = v3((float)atof(t[1].c_str()), (float)atof(t[2].c_str()), (float)atof(t[3].c_str()));
+            float w[3];
+            for (int r = 0; r < 3; ++r)
+                w[r] = (NT.m[0][r] * n.x + NT.m[1][r] * n.y) + (NT.m[2][r] * n.z + NT.m[3][r] * 0.0f);
+            const float inv_len = 1.0f / std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+            vns.push_back(v3(w[0] * inv_len, w[1] * inv_len, w[2] * inv_len));
+            any_vn = true;
         } else if (t[0] == "f" && t.size() >= 4) {
-            std::vector<int> idx;
+            std::vector<int> idx, nidx;
             for (size_t k = 1; k < t.size(); ++k) {
-                int i = atoi(t[k].c_str());                       // "i", "i/j", "i//k"
+                int i = atoi(t[k].c_str());                       // "i", "i/j", "i//k", "i/j/k"
                 if (i < 0) i = (int)vs.size() + 1 + i;
                 if (i < 1 || i > (int)vs.size()) { err = "bad face index in " + path; return false; }
                 idx.push_back(i - 1);
+                int n = face_normal_index(t[k]);
+                if (n < 0) n = (int)vns.size() + 1 + n;
+                if (n < 0 || n > (int)vns.size()) { err = "bad face normal index in " + path; return false; }
+                nidx.push_back(n - 1);                            // -1: none
             }
             for (size_t k = 1; k + 1 < idx.size(); ++k) {         // fan triangulation
                 pt_triangle tr;
                 tr.v0 = P(vs[idx[0]]); tr.v1 = P(vs[idx[k]]); tr.v2 = P(vs[idx[k + 1]]);
                 out.push_back(tr);
+                const int c[3] = {nidx[0], nidx[k], nidx[k + 1]};
+                const bool all = c[0] >= 0 && c[1] >= 0 && c[2] >= 0;
+                for (int j = 0; j < 3; ++j) {
+                    const V3 n = all ? vns[c[j]] : v3(0.0f, 0.0f, 0.0f);
+                    vn_out.push_back(n.x); vn_out.push_back(n.y); vn_out.push_back(n.z);
+                }
             }
         }
     }
@@ -301,6 +335,7 @@ struct SceneFull {
     float **tex;
     int32_t *bump_n;
     float **bump;
+    float *vnormals;          // ... and the meshes' `vn` normals, nine floats per triangle; NULL when no mesh file carried any
 };
 
 // the cube texture of a `CHECKER <n> <cells> r0 g0 b0 r1 g1 b1` line: texel (face, j, i) takes colour 0 or 1 by the parity of
@@ -334,6 +369,14 @@ int pth_scene_bump_map(const pth_scene *s, int material, const float **texels, i
     const SceneFull *f = reinterpret_cast<const SceneFull *>(s);
     *n = f->bump_n[material];
     if (texels) *texels = f->bump[material];
+    return 0;
+}
+
+int pth_scene_vertex_normals(const pth_scene *s, const float **normals, int *num_triangles) {
+    if (!s || !num_triangles) { snprintf(g_err, sizeof g_err, "pth_scene_vertex_normals: bad argument"); return -1; }
+    const SceneFull *f = reinterpret_cast<const SceneFull *>(s);
+    *num_triangles = f->vnormals ? s->num_triangles : 0;
+    if (normals) *normals = f->vnormals;
     return 0;
 }
 
@@ -436,9 +479,10 @@ pth_scene *pth_load_scene(const char *path) {
             if (g.type == PT_TRIANGLE_MESH) {
                 pt_mesh me; me.geom_index = (int32_t)b.geoms.size(); me.first_triangle = (int32_t)b.tris.size();
                 M4 T; memcpy(&T, &g.transform, 64);
+                M4 NT; memcpy(&NT, &g.invTranspose, 64);
                 std::string err;
                 std::string full = mesh_file.size() && mesh_file[0] == '/' ? mesh_file : dir + "/" + mesh_file;
-                if (!load_obj(full, T, b.tris, err)) { snprintf(g_err, sizeof g_err, "%s", err.c_str()); goto fail; }
+                if (!load_obj(full, T, NT, b.tris, b.vnormals, b.any_vn, err)) { snprintf(g_err, sizeof g_err, "%s", err.c_str()); goto fail; }
                 me.triangle_count = (int32_t)b.tris.size() - me.first_triangle;
                 b.meshes.push_back(me);
             }
@@ -550,6 +594,10 @@ pth_scene *pth_load_scene(const char *path) {
         memcpy(full->tex[m], tex.data(), tex.size() * sizeof(float));
         full->tex_n[m] = (int32_t)texture_n[i];
     }
+    if (b.any_vn && !b.tris.empty()) {
+        full->vnormals = (float *)malloc(b.vnormals.size() * sizeof(float));
+        memcpy(full->vnormals, b.vnormals.data(), b.vnormals.size() * sizeof(float));
+    }
     s->camera = s->camera_loaded;
     orbit_recompute(s->camera);
     s->num_geoms = (int32_t)b.geoms.size(); s->num_materials = (int32_t)b.mats.size();
@@ -576,6 +624,7 @@ void pth_free_scene(pth_scene *s) {
     free(full->tex); free(full->tex_n);
     if (full->bump) for (int32_t m = 0; m < s->num_materials; ++m) free(full->bump[m]);
     free(full->bump); free(full->bump_n);
+    free(full->vnormals);
     free(s->geoms); free(s->materials); free(s->triangles); free(s->meshes); free(full);
 }
 

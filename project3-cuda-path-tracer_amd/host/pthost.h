@@ -45,6 +45,12 @@ int pth_scene_texture(const pth_scene *s, int material, const float **texels, in
  * likewise from j; the texel is (slope * sa, slope * sb, 0) -- bevelled studs, every value 0 or +-slope exactly.  PFM as for
  * TEXTURE, a texel (da, db, unused).  The accessor has pth_scene_texture's contract. */
 int pth_scene_bump_map(const pth_scene *s, int material, const float **texels, int *n);
+/* ... and the per-vertex normals of its meshes (include/ptmi355.h "smooth shading"): the loader keeps the `vn` lines of a mesh
+ * file and the third index of `i//k` and `i/j/k` face entries.  Each vn becomes multiplyMV(invTranspose, (vn, 0)) of the mesh's
+ * geom, normalised in binary32; a triangle with a corner that names no normal gets three zero normals ("stays faceted").
+ * *num_triangles = the scene's num_triangles and *normals = nine floats per triangle in the order of pth_scene::triangles
+ * (owned by the scene) -- or 0 and NULL when no mesh file carried a `vn` line.  0, or -1 for a bad argument. */
+int pth_scene_vertex_normals(const pth_scene *s, const float **normals, int *num_triangles);
 
 /* utilityCore::buildTransformationMatrix (utilities.cpp:65-72) + glm::inverse + glm::inverseTranspose
  * (scene.cpp:82-85), GLM 0.9.6.3 operation order */

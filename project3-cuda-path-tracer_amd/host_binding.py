@@ -66,6 +66,7 @@ def host_library():
         L.pth_read_pfm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
         L.pth_scene_texture.argtypes = [C.POINTER(_PthScene), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         L.pth_scene_bump_map.argtypes = L.pth_scene_texture.argtypes
+        L.pth_scene_vertex_normals.argtypes = [C.POINTER(_PthScene), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -110,6 +111,11 @@ def load_scene(path):
                 raise PtError("load_scene(%s): %s" % (path, L.pth_last_error().decode()))
             if n.value > 0:
                 scene.bump_maps[m] = _copy(tex.value, 6 * n.value * n.value * 3, np.dtype("<f4")).reshape(6, n.value, n.value, 3)
+        # ... and its meshes' `vn` normals (pth_scene_vertex_normals): [num_triangles, 3, 3] float32, None when no file had any
+        vn, k = C.c_void_p(None), C.c_int(0)
+        if L.pth_scene_vertex_normals(p, C.byref(vn), C.byref(k)) != 0:
+            raise PtError("load_scene(%s): %s" % (path, L.pth_last_error().decode()))
+        scene.vertex_normals = _copy(vn.value, k.value * 9, np.dtype("<f4")).reshape(k.value, 3, 3) if k.value > 0 else None
     finally:
         L.pth_free_scene(p)
     return scene
