@@ -322,27 +322,36 @@ def _cube_texels(texels):
     return t.reshape(count, 3), n
 
 
-def set_environment(texels):
-    """The cube map a ray that leaves the scene reads (include/ptmi355.h: pt_set_environment): [6, n, n, 3] float32, indexed
-    [face, j, i]; None: no environment, a miss ends with colour 0 again.  The running sum is not touched."""
+def _set_cube(setter, texels, *material):
+    """`setter` (pt_set_environment, or pt_set_texture / pt_set_bump_map with their material) takes the cube map `texels`, or none."""
     if texels is None:
-        _chk(library().pt_set_environment(None, 0))
+        _chk(setter(*material, None, 0))
         return
     t, n = _cube_texels(texels)
-    _chk(library().pt_set_environment(_p(t), n))
+    _chk(setter(*material, _p(t), n))
 
 
-def get_environment():
-    """The session's cube map as it was set, [6, n, n, 3] float32, or None."""
+def _get_cube(getter, *material):
+    """The cube map `getter` gives back, [6, n, n, 3] float32, or None."""
     n = C.c_int(0)
-    L = library()
-    rc = L.pt_get_environment(None, 0, C.byref(n))              # the size: PT_OK with n = 0 when none is set
+    rc = getter(*material, None, 0, C.byref(n))                 # the size: PT_OK with n = 0 when none is set
     if n.value == 0:
         _chk(rc)
         return None
     out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
-    _chk(L.pt_get_environment(_p(out), 6 * n.value * n.value, C.byref(n)))
+    _chk(getter(*material, _p(out), 6 * n.value * n.value, C.byref(n)))
     return out
+
+
+def set_environment(texels):
+    """The cube map a ray that leaves the scene reads (include/ptmi355.h: pt_set_environment): [6, n, n, 3] float32, indexed
+    [face, j, i]; None: no environment, a miss ends with colour 0 again.  The running sum is not touched."""
+    _set_cube(library().pt_set_environment, texels)
+
+
+def get_environment():
+    """The session's cube map as it was set, [6, n, n, 3] float32, or None."""
+    return _get_cube(library().pt_get_environment)
 
 
 def gradient_cubemap(n, zenith, horizon, ground):
@@ -460,24 +469,12 @@ def probe_environment(texels, dirs, throughput):
 def set_texture(material, texels):
     """The cube texture of one material (include/ptmi355.h: pt_set_texture): [6, n, n, 3] float32, indexed [face, j, i]; None
     removes it.  Sessions initialised with PT_TEXTURES.  The running sum is not touched."""
-    if texels is None:
-        _chk(library().pt_set_texture(int(material), None, 0))
-        return
-    t, n = _cube_texels(texels)
-    _chk(library().pt_set_texture(int(material), _p(t), n))
+    _set_cube(library().pt_set_texture, texels, int(material))
 
 
 def get_texture(material):
     """That material's cube texture as it was set, [6, n, n, 3] float32, or None."""
-    n = C.c_int(0)
-    L = library()
-    rc = L.pt_get_texture(int(material), None, 0, C.byref(n))     # the size: PT_OK with n = 0 when none is set
-    if n.value == 0:
-        _chk(rc)
-        return None
-    out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
-    _chk(L.pt_get_texture(int(material), _p(out), 6 * n.value * n.value, C.byref(n)))
-    return out
+    return _get_cube(library().pt_get_texture, int(material))
 
 
 def checker_cubemap(n, cells, colour0, colour1):
@@ -549,24 +546,12 @@ def probe_shade_scatter_textured(iter, depth, materials, paths, isects, geoms, h
 def set_bump_map(material, texels):
     """The cube bump map of one material (include/ptmi355.h: pt_set_bump_map): [6, n, n, 3] float32, indexed [face, j, i], a
     texel (da, db, unused); None removes it.  Sessions initialised with PT_TEXTURES.  The running sum is not touched."""
-    if texels is None:
-        _chk(library().pt_set_bump_map(int(material), None, 0))
-        return
-    t, n = _cube_texels(texels)
-    _chk(library().pt_set_bump_map(int(material), _p(t), n))
+    _set_cube(library().pt_set_bump_map, texels, int(material))
 
 
 def get_bump_map(material):
     """That material's bump map as it was set, [6, n, n, 3] float32, or None."""
-    n = C.c_int(0)
-    L = library()
-    rc = L.pt_get_bump_map(int(material), None, 0, C.byref(n))    # the size: PT_OK with n = 0 when none is set
-    if n.value == 0:
-        _chk(rc)
-        return None
-    out = np.zeros((6, n.value, n.value, 3), dtype=np.float32)
-    _chk(L.pt_get_bump_map(int(material), _p(out), 6 * n.value * n.value, C.byref(n)))
-    return out
+    return _get_cube(library().pt_get_bump_map, int(material))
 
 
 def _vertex_normals(who, normals):

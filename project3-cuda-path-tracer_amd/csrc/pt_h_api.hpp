@@ -45,10 +45,10 @@ void pt_free(void) {
     if (R.d_ginfo) (void)hipFree(R.d_ginfo);
     if (R.d_env) (void)hipFree(R.d_env);
     if (R.d_lights) (void)hipFree(R.d_lights);
-    if (R.d_tex) (void)hipFree(R.d_tex);
-    if (R.d_tex_tab) (void)hipFree(R.d_tex_tab);
-    if (R.d_bump) (void)hipFree(R.d_bump);
-    if (R.d_bump_tab) (void)hipFree(R.d_bump_tab);
+    if (R.tex.d_texels) (void)hipFree(R.tex.d_texels);
+    if (R.tex.d_tab) (void)hipFree(R.tex.d_tab);
+    if (R.bump.d_texels) (void)hipFree(R.bump.d_texels);
+    if (R.bump.d_tab) (void)hipFree(R.bump.d_tab);
     if (R.d_vnormals) (void)hipFree(R.d_vnormals);
     if (R.mesh_hit) (void)hipFree(R.mesh_hit);
     for (int k = 0; k < 2; ++k) if (R.mesh_flags[k]) (void)hipFree(R.mesh_flags[k]);
@@ -711,292 +711,7 @@ int pt_set_lens(float lens_radius, float focal_distance) {
     return PT_OK;
 }
 
-// Environment lighting (include/ptmi355.h).  The map is scene state the launches in flight read:
-// the host waits for everything the session has enqueued -- windows traced ahead are void, as after a camera change --
-// before the old texels are released.  The accumulation buffer stays as it is.
-// PT_DIRECT_SKY: the device's light table of a flagged session -- the lamps' records alone (texels ==
-// nullptr, or a map that yields no element), or the lamps at half their probability, the sky's record and its two tables.
-// The caller has synchronised the session: nothing in flight reads the old table.  The light count, and with it the number
-// of bounces a batch runs, follows.
-static int upload_sky_lights(const float *texels, int n) {
-    std::vector<float> rows, cols, rec;
-    int count = (int)(R.lamp_rec.size() / (size_t)ptlight::RECORD_WORDS);
-    const std::vector<float> *src = &R.lamp_rec;
-    if (texels && n > 0 && ptlight::sky_table(texels, n, rows, cols)) {
-        count = ptlight::sky_records(R.lamp_rec, n, rows, cols, rec);
-        src = &rec;
-    }
-    if (R.d_lights) { (void)hipFree(R.d_lights); R.d_lights = nullptr; }
-    R.nlights = 0;
-    if (count == 0) return PT_OK;
-    if (hipMalloc((void **)&R.d_lights, src->size() * 4) != hipSuccess) {
-        (void)hipGetLastError(); R.d_lights = nullptr;
-        return fail(PT_ERR_NOMEM, "pt_set_environment: %zu bytes of device memory for the light table", src->size() * 4);
-    }
-    HIPCHK(hipMemcpy(R.d_lights, src->data(), src->size() * 4, hipMemcpyHostToDevice));
-    R.nlights = count;
-    return PT_OK;
-}
-
-int pt_set_environment(const float *texels, int n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_environment: not initialised");
-    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_environment: n = %d outside [0, 1024]", n);
-    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_environment: null texels with n = %d", n);
-    if (!texels) n = 0;
-    const int rc = la_discard(LA_HOST);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(R.stream));
-    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
-        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
-        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
-    }
-    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
-    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
-    R.ov_active = false;
-    R.env_n = 0;
-    if (R.d_env) { (void)hipFree(R.d_env); R.d_env = nullptr; }
-    R.env_keep.clear();
-    if (sky_session()) {                                        // the element disappears with the map
-        const int rc2 = upload_sky_lights(nullptr, 0);
-        if (rc2) return rc2;
-    }
-    if (n == 0) return PT_OK;
-    const size_t count = (size_t)6 * (size_t)n * (size_t)n;
-    std::vector<float> quad(count * 4);
-    for (size_t k = 0; k < count; ++k) {
-        quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; quad[4 * k + 3] = 0.0f;
-    }
-    if (hipMalloc((void **)&R.d_env, count * 16) != hipSuccess) {
-        (void)hipGetLastError(); R.d_env = nullptr;
-        return fail(PT_ERR_NOMEM, "pt_set_environment: %zu bytes of device memory for a %d x %d x 6 map", count * 16, n, n);
-    }
-    HIPCHK(hipMemcpy(R.d_env, quad.data(), count * 16, hipMemcpyHostToDevice));
-    R.env_keep.assign(texels, texels + count * 3);
-    R.env_n = n;
-    if (sky_session()) return upload_sky_lights(texels, n);
-    return PT_OK;
-}
-
-int pt_get_environment(float *texels, int capacity_texels, int *n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_environment: not initialised");
-    if (!n) return fail(PT_ERR_INVALID, "pt_get_environment: null n");
-    const int en = R.env_n;
-    *n = en;
-    if (en == 0) return PT_OK;
-    const size_t count = (size_t)6 * (size_t)en * (size_t)en;
-    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
-        return fail(PT_ERR_INVALID, "pt_get_environment: room for %d texels, the map has %zu", texels ? capacity_texels : 0, count);
-    memcpy(texels, R.env_keep.data(), count * 12);
-    return PT_OK;
-}
-
-// Texture mapping (include/ptmi355.h).  Textures are scene state the launches in flight read, like the
-// environment map: the host waits for everything the session has enqueued and the windows traced ahead are void before the
-// device copy is replaced.  The accumulation buffer stays as it is.  Every texture's texels sit back to back in ONE device
-// array, rebuilt per call (a host keeps a handful of textures and sets them once).
-int pt_set_texture(int material, const float *texels, int n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_texture: not initialised");
-    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_set_texture: the session was not initialised with PT_TEXTURES");
-    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_set_texture: material %d outside [0, %d)", material, R.scene.nmats);
-    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_texture: n = %d outside [0, 1024]", n);
-    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_texture: null texels with n = %d", n);
-    if (!texels) n = 0;
-    const int rc = la_discard(LA_HOST);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(R.stream));
-    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
-        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
-        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
-    }
-    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
-    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
-    R.ov_active = false;
-    if (R.tex_n.empty()) { R.tex_n.assign((size_t)R.scene.nmats, 0); R.tex_keep.resize((size_t)R.scene.nmats); }
-    // the new table on the host first: the session keeps its old textures when the device has no room for the new set
-    std::vector<int> tn = R.tex_n;
-    tn[(size_t)material] = n;
-    std::vector<int2> tab((size_t)R.scene.nmats);
-    size_t total = 0;
-    int ntex = 0;
-    for (int m = 0; m < R.scene.nmats; ++m) {
-        tab[(size_t)m] = make_int2((int)total, tn[(size_t)m]);
-        total += (size_t)6 * (size_t)tn[(size_t)m] * (size_t)tn[(size_t)m];
-        if (tn[(size_t)m] > 0) ++ntex;
-    }
-    if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "pt_set_texture: %zu texels in all (at most 2^31 - 1)", total);
-    float4 *d_new = nullptr;
-    if (ntex > 0) {
-        std::vector<float> quad(total * 4);
-        for (int m = 0; m < R.scene.nmats; ++m) {
-            const size_t cnt = (size_t)6 * (size_t)tn[(size_t)m] * (size_t)tn[(size_t)m];
-            const float *src = m == material ? texels : R.tex_keep[(size_t)m].data();
-            float *dst = quad.data() + (size_t)tab[(size_t)m].x * 4;
-            for (size_t k = 0; k < cnt; ++k) { dst[4 * k] = src[3 * k]; dst[4 * k + 1] = src[3 * k + 1]; dst[4 * k + 2] = src[3 * k + 2]; dst[4 * k + 3] = 0.0f; }
-        }
-        if (hipMalloc((void **)&d_new, total * 16) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PT_ERR_NOMEM, "pt_set_texture: %zu bytes of device memory for the session's textures", total * 16);
-        }
-        HIPCHK(hipMemcpy(d_new, quad.data(), total * 16, hipMemcpyHostToDevice));
-    }
-    // (the table also while no texture is left: a session with a bump map alone launches the TEX forms, which read it)
-    if (!R.d_tex_tab) HIPCHK(hipMalloc((void **)&R.d_tex_tab, tab.size() * sizeof(int2)));
-    HIPCHK(hipMemcpy(R.d_tex_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
-    // the albedo plane follows the table: stale unless this call left every texel as it was
-    const int old_n = R.tex_n[(size_t)material];
-    if (old_n != n || (n > 0 && memcmp(R.tex_keep[(size_t)material].data(), texels, (size_t)6 * (size_t)n * (size_t)n * 12) != 0))
-        R.alb_valid = false;
-    if (R.d_tex) (void)hipFree(R.d_tex);
-    R.d_tex = d_new;
-    R.tex_n = tn;
-    if (n > 0) R.tex_keep[(size_t)material].assign(texels, texels + (size_t)6 * (size_t)n * (size_t)n * 3);
-    else std::vector<float>().swap(R.tex_keep[(size_t)material]);
-    R.ntex = ntex;
-    return PT_OK;
-}
-
-int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_texture: not initialised");
-    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_get_texture: the session was not initialised with PT_TEXTURES");
-    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_get_texture: material %d outside [0, %d)", material, R.scene.nmats);
-    if (!n) return fail(PT_ERR_INVALID, "pt_get_texture: null n");
-    const int tn = R.tex_n.empty() ? 0 : R.tex_n[(size_t)material];
-    *n = tn;
-    if (tn == 0) return PT_OK;
-    const size_t count = (size_t)6 * (size_t)tn * (size_t)tn;
-    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
-        return fail(PT_ERR_INVALID, "pt_get_texture: room for %d texels, the texture has %zu", texels ? capacity_texels : 0, count);
-    memcpy(texels, R.tex_keep[(size_t)material].data(), count * 12);
-    return PT_OK;
-}
-
-// Bump mapping (include/ptmi355.h): pt_set_texture's contract with a table and an array of its own.  A
-// texel keeps its first two floats {da, db}; the albedo plane reads no normal and stays valid.
-int pt_set_bump_map(int material, const float *texels, int n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_bump_map: not initialised");
-    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_set_bump_map: the session was not initialised with PT_TEXTURES");
-    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_set_bump_map: material %d outside [0, %d)", material, R.scene.nmats);
-    if (n < 0 || n > 1024) return fail(PT_ERR_INVALID, "pt_set_bump_map: n = %d outside [0, 1024]", n);
-    if (n > 0 && !texels) return fail(PT_ERR_INVALID, "pt_set_bump_map: null texels with n = %d", n);
-    if (!texels) n = 0;
-    const int rc = la_discard(LA_HOST);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(R.stream));
-    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
-        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
-        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
-    }
-    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
-    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
-    R.ov_active = false;
-    if (R.bump_n.empty()) { R.bump_n.assign((size_t)R.scene.nmats, 0); R.bump_keep.resize((size_t)R.scene.nmats); }
-    std::vector<int> bn = R.bump_n;
-    bn[(size_t)material] = n;
-    std::vector<int2> tab((size_t)R.scene.nmats);
-    size_t total = 0;
-    int nbump = 0;
-    for (int m = 0; m < R.scene.nmats; ++m) {
-        tab[(size_t)m] = make_int2((int)total, bn[(size_t)m]);
-        total += (size_t)6 * (size_t)bn[(size_t)m] * (size_t)bn[(size_t)m];
-        if (bn[(size_t)m] > 0) ++nbump;
-    }
-    if (total > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "pt_set_bump_map: %zu texels in all (at most 2^31 - 1)", total);
-    ptd::bump_texel *d_new = nullptr;
-    if (nbump > 0) {
-        std::vector<float> pair(total * 2);
-        for (int m = 0; m < R.scene.nmats; ++m) {
-            const size_t cnt = (size_t)6 * (size_t)bn[(size_t)m] * (size_t)bn[(size_t)m];
-            const float *src = m == material ? texels : R.bump_keep[(size_t)m].data();
-            float *dst = pair.data() + (size_t)tab[(size_t)m].x * 2;
-            for (size_t k = 0; k < cnt; ++k) { dst[2 * k] = src[3 * k]; dst[2 * k + 1] = src[3 * k + 1]; }
-        }
-        if (hipMalloc((void **)&d_new, total * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PT_ERR_NOMEM, "pt_set_bump_map: %zu bytes of device memory for the session's bump maps", total * 8);
-        }
-        HIPCHK(hipMemcpy(d_new, pair.data(), total * 8, hipMemcpyHostToDevice));
-    }
-    if (!R.d_bump_tab) HIPCHK(hipMalloc((void **)&R.d_bump_tab, tab.size() * sizeof(int2)));
-    HIPCHK(hipMemcpy(R.d_bump_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
-    if (!R.d_tex_tab) {                                         // no pt_set_texture yet: the TEX forms read a table without textures
-        const std::vector<int2> none((size_t)R.scene.nmats, make_int2(0, 0));
-        HIPCHK(hipMalloc((void **)&R.d_tex_tab, none.size() * sizeof(int2)));
-        HIPCHK(hipMemcpy(R.d_tex_tab, none.data(), none.size() * sizeof(int2), hipMemcpyHostToDevice));
-    }
-    if (R.d_bump) (void)hipFree(R.d_bump);
-    R.d_bump = d_new;
-    R.bump_n = bn;
-    if (n > 0) R.bump_keep[(size_t)material].assign(texels, texels + (size_t)6 * (size_t)n * (size_t)n * 3);
-    else std::vector<float>().swap(R.bump_keep[(size_t)material]);
-    R.nbump = nbump;
-    return PT_OK;
-}
-
-int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_bump_map: not initialised");
-    if (!(R.flags & PT_TEXTURES)) return fail(PT_ERR_INVALID, "pt_get_bump_map: the session was not initialised with PT_TEXTURES");
-    if (material < 0 || material >= R.scene.nmats) return fail(PT_ERR_INVALID, "pt_get_bump_map: material %d outside [0, %d)", material, R.scene.nmats);
-    if (!n) return fail(PT_ERR_INVALID, "pt_get_bump_map: null n");
-    const int bn = R.bump_n.empty() ? 0 : R.bump_n[(size_t)material];
-    *n = bn;
-    if (bn == 0) return PT_OK;
-    const size_t count = (size_t)6 * (size_t)bn * (size_t)bn;
-    if (!texels || capacity_texels < 0 || (size_t)capacity_texels < count)
-        return fail(PT_ERR_INVALID, "pt_get_bump_map: room for %d texels, the map has %zu", texels ? capacity_texels : 0, count);
-    memcpy(texels, R.bump_keep[(size_t)material].data(), count * 12);
-    return PT_OK;
-}
-
-// Smooth shading of triangle meshes (include/ptmi355.h): pt_set_bump_map's contract with one array -- nine
-// floats per triangle, in the order of pt_scene_desc::triangles.  pt_gbuffer, pt_albedo and the filters keep the facet normal, so
-// nothing of theirs goes stale.
-int pt_set_vertex_normals(const float *normals, int num_triangles) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: not initialised");
-    if (!(R.flags & PT_SMOOTH_NORMALS)) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS");
-    if (num_triangles < 0) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: num_triangles = %d", num_triangles);
-    if (num_triangles > 0 && !normals) return fail(PT_ERR_INVALID, "pt_set_vertex_normals: null normals with num_triangles = %d", num_triangles);
-    if (!normals) num_triangles = 0;
-    if (num_triangles != 0 && num_triangles != R.desc.num_triangles)
-        return fail(PT_ERR_INVALID, "pt_set_vertex_normals: %d triangles, the session has %d", num_triangles, R.desc.num_triangles);
-    const int rc = la_discard(LA_HOST);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(R.stream));
-    for (int k = 0; k < OV_MAX_LANES; ++k) {                    // asynchronous batches on the lanes
-        if (R.lane[k].stream) HIPCHK(hipStreamSynchronize(R.lane[k].stream));
-        if (R.lane[k].la_stream) HIPCHK(hipStreamSynchronize(R.lane[k].la_stream));
-    }
-    if (R.la_gstream) HIPCHK(hipStreamSynchronize(R.la_gstream));
-    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
-    R.ov_active = false;
-    const size_t words = (size_t)num_triangles * 9;
-    // (PT_FAKE_SHADER ignores the flag: the normals are kept for pt_get_vertex_normals and no kernel reads them)
-    float *d_new = nullptr;
-    if (words > 0) {
-        if (hipMalloc((void **)&d_new, words * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PT_ERR_NOMEM, "pt_set_vertex_normals: %zu bytes of device memory for the session's vertex normals", words * 4);
-        }
-        HIPCHK(hipMemcpy(d_new, normals, words * 4, hipMemcpyHostToDevice));
-    }
-    if (R.d_vnormals) (void)hipFree(R.d_vnormals);
-    R.d_vnormals = d_new;
-    if (words > 0) R.vn_keep.assign(normals, normals + words);
-    else std::vector<float>().swap(R.vn_keep);
-    return PT_OK;
-}
-
-int pt_get_vertex_normals(float *normals, int capacity_triangles, int *num_triangles) {
-    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: not initialised");
-    if (!(R.flags & PT_SMOOTH_NORMALS)) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS");
-    if (!num_triangles) return fail(PT_ERR_INVALID, "pt_get_vertex_normals: null num_triangles");
-    const size_t count = R.vn_keep.size() / 9;
-    *num_triangles = (int)count;
-    if (count == 0) return PT_OK;
-    if (!normals || capacity_triangles < 0 || (size_t)capacity_triangles < count)
-        return fail(PT_ERR_INVALID, "pt_get_vertex_normals: room for %d triangles, the session has %zu", normals ? capacity_triangles : 0, count);
-    memcpy(normals, R.vn_keep.data(), count * 36);
-    return PT_OK;
-}
+// (pt_set_environment, pt_set_texture, pt_set_bump_map, pt_set_vertex_normals and their getters: pt_h_state.hpp)
 
 int pt_synchronize(void) {
     if (!R.live) return fail(PT_ERR_INVALID, "pt_synchronize: not initialised");
@@ -1036,7 +751,7 @@ int pt_trace_batch(int iter0, int count, float *host_image_sum) {
 // (what pt_trace decides per call; the multi-GPU form asks once at pt_init: pt_multi.hpp)
 bool whole_host_possible(void) {
     return R.live && !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && !sky_session() && R.ntex + R.nbump == 0 && R.epi_enabled &&
+           R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && !sky_session() && R.tex.count + R.bump.count == 0 && R.epi_enabled &&
            (uint64_t)R.map.tile_pixels <= std::max(R.whole_max_paths, R.whole_max_host_paths);
 }
 

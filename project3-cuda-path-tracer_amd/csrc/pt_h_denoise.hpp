@@ -36,9 +36,9 @@ static int ensure_gbuffer(bool albedo = false) {
     const int blocks = std::min(R.grid, (R.npix + BLOCK - 1) / BLOCK);
     if (need_alb) {
         // tinted only while the session's bounce kernels are launched in their textured form (bounce_args, launch_k_bounce)
-        const bool textured = R.ntex > 0 && !(R.flags & PT_FAKE_SHADER);
-        const GbAlbedo alb{R.alb_mem, textured ? (const int2 *)R.d_tex_tab : (const int2 *)nullptr,
-                           textured ? (const float4 *)R.d_tex : (const float4 *)nullptr};
+        const bool textured = R.tex.count > 0 && !(R.flags & PT_FAKE_SHADER);
+        const GbAlbedo alb{R.alb_mem, textured ? (const int2 *)R.tex.d_tab : (const int2 *)nullptr,
+                           textured ? (const float4 *)R.tex.d_texels : (const float4 *)nullptr};
         PT_MESH_DISPATCH(hipLaunchKernelGGL((k_gbuffer<MESH, SLDS, true>), dim3(blocks), dim3(BLOCK), R.lds_bytes, R.stream, gA, gB,
                                             R.scene, R.cam, R.map, alb));
     } else {

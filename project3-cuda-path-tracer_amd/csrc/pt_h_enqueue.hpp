@@ -34,8 +34,8 @@ BounceArgs bounce_args(int depth) {
     a.persist = R.persist;
     a.env = R.d_env; a.env_n = R.env_n;
     a.lights = R.d_lights; a.nlights = R.nlights;
-    if (R.ntex + R.nbump > 0) { a.tex = R.d_tex; a.tex_tab = R.d_tex_tab; }
-    if (R.nbump > 0) { a.bumps = R.d_bump; a.bump_tab = R.d_bump_tab; }
+    if (R.tex.count + R.bump.count > 0) { a.tex = R.tex.d_texels; a.tex_tab = R.tex.d_tab; }
+    if (R.bump.count > 0) { a.bumps = R.bump.d_texels; a.bump_tab = R.bump.d_tab; }
     a.vnormals = R.d_vnormals;                                  // (null while none are set)
     return a;
 }
@@ -710,7 +710,7 @@ int enqueue_batch_serial(int iter0, int count) {
     // (a PT_DIRECT_LIGHT session with lights to sample runs a kernel per bounce: k_iteration has no DIRECT form; nor has it a TEX
     // form -- a PT_TEXTURES session does while a texture is set, decided launch by launch)
     const bool whole = !(R.flags & (PT_UNFUSED | PT_SORT_MATERIAL | PT_FAKE_SHADER | PT_CACHE_FIRST)) && (R.flags & PT_COMPACT) &&
-                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.ntex + R.nbump == 0 && count >= 1 &&
+                       R.mesh_mode == MESH_NONE && R.sort_keys == 0 && R.nlights == 0 && R.tex.count + R.bump.count == 0 && count >= 1 &&
                        (uint64_t)R.map.tile_pixels * (uint64_t)count <= whole_limit;
     int rc = enqueue_begin(iter0, count, false, !whole);
     if (rc) return rc;

@@ -29,6 +29,17 @@ int fail(int code, const char *fmt, ...) {
                         hipGetErrorString(e_));                                                 \
     } while (0)
 
+// At most one cube map per material, in the device's `Texel`.  keep[m] / n[m]: material m's map as the caller gave it, RGB
+// (the getters; both empty until the first map is set); d_texels: every map's texels back to back; d_tab: per material {offset
+// in texels, n}; count: maps set.  The device's two are rebuilt whenever a map is set or removed (pt_h_state.hpp: cube_replace).
+template <class Texel> struct CubeMaps {
+    std::vector<std::vector<float>> keep;
+    std::vector<int> n;
+    Texel *d_texels = nullptr;
+    int2 *d_tab = nullptr;
+    int count = 0;
+};
+
 constexpr int OV_MAX_LANES = 8;
 struct Renderer {
     bool live = false;
@@ -91,23 +102,11 @@ struct Renderer {
     // PT_DIRECT_SKY: the lamps' records as pt_init made them.  In a flagged session nlights CHANGES
     // when a map arrives or goes (pt_set_environment: + 1 for the sky's element, and the two tables behind the records)
     std::vector<float> lamp_rec;
-    // PT_TEXTURES: at most one cube texture per material.  tex_keep[m] / tex_n[m]: as the caller gave
-    // them (pt_get_texture); d_tex: every texture's texels {r, g, b, 0} back to back, d_tex_tab: per material {offset in texels,
-    // n}, both rebuilt by pt_set_texture.  ntex = textures set; > 0: the session launches the TEX forms of k_bounce, a kernel
+    // PT_TEXTURES: the materials' cube textures, {r, g, b, 0} per texel, and their cube bump maps,
+    // {da, db} per texel (section 6.22).  tex.count + bump.count > 0: the session launches the TEX forms of k_bounce, a kernel
     // per bounce.
-    std::vector<std::vector<float>> tex_keep;
-    std::vector<int> tex_n;
-    float4 *d_tex = nullptr;
-    int2 *d_tex_tab = nullptr;
-    int ntex = 0;
-    // ... and at most one cube bump map per material, kept the same way: bump_keep[m] / bump_n[m] as
-    // the caller gave them (pt_get_bump_map); d_bump: every map's {da, db} back to back, d_bump_tab: per material {offset in
-    // texels, n}, both rebuilt by pt_set_bump_map.  nbump = maps set; ntex + nbump > 0: the TEX forms, a kernel per bounce.
-    std::vector<std::vector<float>> bump_keep;
-    std::vector<int> bump_n;
-    ptd::bump_texel *d_bump = nullptr;
-    int2 *d_bump_tab = nullptr;
-    int nbump = 0;
+    CubeMaps<float4> tex;
+    CubeMaps<ptd::bump_texel> bump;
     // PT_SMOOTH_NORMALS: the per-vertex normals, 9 floats per triangle in the order of
     // pt_scene_desc::triangles -- vn_keep as the caller gave them (pt_get_vertex_normals), d_vnormals the device's copy.  Null /
     // empty: none set; otherwise the SMOOTH forms, a kernel per bounce.

@@ -752,56 +752,39 @@ int pt_set_lens(float lens_radius, float focal_distance) {
     return on_all([&](Worker &) -> int { return one::pt_set_lens(lens_radius, focal_distance); });
 }
 
-// every context traces with the same map: each keeps its own device copy
-int pt_set_environment(const float *texels, int n) {
-    if (!G.live) return one::pt_set_environment(texels, n);
+// Scene state that is replaced between calls (pt_h_state.hpp) -- the environment map, the textures, the
+// bump maps (section 6.22), the vertex normals (section 6.26: every context holds the whole scene, so each takes the whole array):
+// every context traces with the same, and each keeps its own device copy.  Over several contexts a setter first settles what the
+// session has in flight; a getter asks context 0.
+static int set_everywhere(const std::function<int()> &set) {
+    if (!G.live) return set();
     const int rc = multi_sync();
     if (rc) return rc;
-    return on_all([&](Worker &) -> int { return one::pt_set_environment(texels, n); });
+    return on_all([&](Worker &) -> int { return set(); });
+}
+static int get_anywhere(const std::function<int()> &get) {
+    if (!G.live) return get();
+    return on_one(0, [&](Worker &) -> int { return get(); });
+}
+
+int pt_set_environment(const float *texels, int n) { return set_everywhere([&] { return one::pt_set_environment(texels, n); }); }
+int pt_set_texture(int material, const float *texels, int n) { return set_everywhere([&] { return one::pt_set_texture(material, texels, n); }); }
+int pt_set_bump_map(int material, const float *texels, int n) { return set_everywhere([&] { return one::pt_set_bump_map(material, texels, n); }); }
+int pt_set_vertex_normals(const float *normals, int num_triangles) {
+    return set_everywhere([&] { return one::pt_set_vertex_normals(normals, num_triangles); });
 }
 
 int pt_get_environment(float *texels, int capacity_texels, int *n) {
-    if (!G.live) return one::pt_get_environment(texels, capacity_texels, n);
-    return on_one(0, [&](Worker &) -> int { return one::pt_get_environment(texels, capacity_texels, n); });
+    return get_anywhere([&] { return one::pt_get_environment(texels, capacity_texels, n); });
 }
-
-// every context shades with the same textures: each keeps its own device copy
-int pt_set_texture(int material, const float *texels, int n) {
-    if (!G.live) return one::pt_set_texture(material, texels, n);
-    const int rc = multi_sync();
-    if (rc) return rc;
-    return on_all([&](Worker &) -> int { return one::pt_set_texture(material, texels, n); });
-}
-
 int pt_get_texture(int material, float *texels, int capacity_texels, int *n) {
-    if (!G.live) return one::pt_get_texture(material, texels, capacity_texels, n);
-    return on_one(0, [&](Worker &) -> int { return one::pt_get_texture(material, texels, capacity_texels, n); });
+    return get_anywhere([&] { return one::pt_get_texture(material, texels, capacity_texels, n); });
 }
-
-// ... and the same bump maps
-int pt_set_bump_map(int material, const float *texels, int n) {
-    if (!G.live) return one::pt_set_bump_map(material, texels, n);
-    const int rc = multi_sync();
-    if (rc) return rc;
-    return on_all([&](Worker &) -> int { return one::pt_set_bump_map(material, texels, n); });
-}
-
 int pt_get_bump_map(int material, float *texels, int capacity_texels, int *n) {
-    if (!G.live) return one::pt_get_bump_map(material, texels, capacity_texels, n);
-    return on_one(0, [&](Worker &) -> int { return one::pt_get_bump_map(material, texels, capacity_texels, n); });
+    return get_anywhere([&] { return one::pt_get_bump_map(material, texels, capacity_texels, n); });
 }
-
-// ... and the same vertex normals: every context holds the whole scene, so each takes the whole array
-int pt_set_vertex_normals(const float *normals, int num_triangles) {
-    if (!G.live) return one::pt_set_vertex_normals(normals, num_triangles);
-    const int rc = multi_sync();
-    if (rc) return rc;
-    return on_all([&](Worker &) -> int { return one::pt_set_vertex_normals(normals, num_triangles); });
-}
-
 int pt_get_vertex_normals(float *normals, int capacity_triangles, int *num_triangles) {
-    if (!G.live) return one::pt_get_vertex_normals(normals, capacity_triangles, num_triangles);
-    return on_one(0, [&](Worker &) -> int { return one::pt_get_vertex_normals(normals, capacity_triangles, num_triangles); });
+    return get_anywhere([&] { return one::pt_get_vertex_normals(normals, capacity_triangles, num_triangles); });
 }
 
 int pt_synchronize(void) {
@@ -874,7 +857,7 @@ static int multi_trace(uint8_t *pbo_rgba, int iter0, int count, float *host_imag
     // own tile's pixels (those whose sum changed) into the caller's image while it traces (pt_trace_mapped)
     // (G.direct_ok was asked at pt_init; a PT_TEXTURES session runs a kernel per bounce while a texture is set -- the contexts'
     // threads are idle between calls, and every context has the same textures)
-    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange && G.w[0]->ctx.ntex + G.w[0]->ctx.nbump == 0 &&
+    if (host_image_sum && !pbo_rgba && count == 1 && G.direct_ok && G.direct_enabled && !G.self_exchange && G.w[0]->ctx.tex.count + G.w[0]->ctx.bump.count == 0 &&
         (G.w[0]->ctx.flags & PT_PIN_IMAGE) && multi_pin(host_image_sum, (size_t)G.npix * 12)) {
         int rc = exchange_settled();
         if (rc) return rc;

@@ -391,19 +391,7 @@ int probe_check_geoms(const char *who, const pt_shadeable_intersection *isects, 
     return PT_OK;
 }
 
-// `count` RGB texels in the session's device layout: {r, g, b, 0}
-std::vector<float> rgb_quads(const float *texels, size_t count) {
-    std::vector<float> quad(std::max<size_t>(count, 1) * 4, 0.0f);
-    for (size_t k = 0; k < count; ++k) { quad[4 * k] = texels[3 * k]; quad[4 * k + 1] = texels[3 * k + 1]; quad[4 * k + 2] = texels[3 * k + 2]; }
-    return quad;
-}
-// {da, db} of `count` RGB texels
-std::vector<float> bump_pairs(const float *texels, size_t count) {
-    std::vector<float> pair(std::max<size_t>(count, 1) * 2, 0.0f);
-    for (size_t k = 0; k < count; ++k) { pair[2 * k] = texels[3 * k]; pair[2 * k + 1] = texels[3 * k + 1]; }
-    return pair;
-}
-
+// (texels in the session's device layouts: rgb_quads / bump_pairs, pt_h_state.hpp)
 // a per-material table of cube maps (`what`: "texture" / "bump map"; material m: n[m] x n[m] texels per face from texel offset[m],
 // n[m] == 0: none) as the kernels read it, {offset, n} per material, and the texels it reaches
 int probe_cube_table(const char *who, const char *what, int num_materials, const int32_t *n, const int32_t *offset, std::vector<int2> &tab,

@@ -73,6 +73,7 @@ static inline const char *pt_experiment(const char *name) {
 #include "pt_h_enqueue.hpp"
 #include "pt_h_image.hpp"
 #include "pt_h_api.hpp"       // (includes pt_h_scene.hpp between pt_free and pt_init)
+#include "pt_h_state.hpp"
 #include "pt_h_denoise.hpp"
 
 

@@ -58,6 +58,22 @@ def test_calls_before_init_fail_cleanly(pt):
     assert L.pt_device_image() is None
 
 
+def test_scene_state_calls_before_init_name_themselves(pt):
+    """The setters and getters of replaceable scene state before pt_init: PT_ERR_INVALID and the whole message."""
+    L = pt.library()
+    pt.pathtraceFree()
+    t = np.ones((24, 3), dtype=np.float32)
+    n = C.c_int(7)
+    calls = {"pt_set_environment": (t.ctypes.data, 2), "pt_get_environment": (t.ctypes.data, 24, C.byref(n)),
+             "pt_set_texture": (0, t.ctypes.data, 2), "pt_get_texture": (0, t.ctypes.data, 24, C.byref(n)),
+             "pt_set_bump_map": (0, t.ctypes.data, 2), "pt_get_bump_map": (0, t.ctypes.data, 24, C.byref(n)),
+             "pt_set_vertex_normals": (t.ctypes.data, 8), "pt_get_vertex_normals": (t.ctypes.data, 8, C.byref(n))}
+    for name, args in calls.items():
+        assert getattr(L, name)(*args) == -1, name
+        assert L.pt_last_error() == b"%s: not initialised" % name.encode(), L.pt_last_error()
+    assert n.value == 7                                          # nothing was reported
+
+
 def test_no_cpu_fallback(pt, scenes):
     """Without a GPU pt_init must fail (PT_ERR_DEVICE); with one this test is skipped."""
     import torch

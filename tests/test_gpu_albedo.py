@@ -298,6 +298,35 @@ def test_textures_and_camera_are_followed(pt, po, scenes, launch_plan):
         pt.pathtraceFree()
 
 
+def test_plane_goes_stale_with_a_texel_and_with_nothing_else(pt, po, scenes, launch_plan):
+    """k_gbuffer launches count what is recomputed (40 x 26): a material's own texels set again and bump maps set, replaced and
+    removed leave the plane as it is; one changed texel does not."""
+    w, h = 40, 26
+    geoms, mats, cam, depth, _, _, _ = open_session(pt, scenes, "flag without a texture", w, h, max_batch=2)
+    try:
+        tex = random_texture(4, 11)
+        pt.set_texture(5, tex)
+        plane = pt.albedo().copy()
+        same(plane, alm.albedo(po, geoms, mats, {5: tex}, cam, depth), "the plane")
+        assert launches(pt)[0] == 1
+        pt.set_texture(5, tex.copy())                                # the identical texture
+        assert pt.albedo().tobytes() == plane.tobytes() and launches(pt)[0] == 1
+        bump = np.random.default_rng(12).normal(0, 0.8, (6, 4, 4, 3)).astype(F32)
+        for m, t in ((5, bump), (6, bump[:, :2, :2]), (5, bump[:, :3, :3]), (5, None)):
+            pt.set_bump_map(m, t)
+            assert pt.albedo().tobytes() == plane.tobytes() and launches(pt)[0] == 1, m
+        one = tex.copy()
+        one[3, 2, 1, 2] = np.nextafter(one[3, 2, 1, 2], F32(4))      # one float of one texel, by one ulp
+        pt.set_texture(5, one)
+        same(pt.albedo(), alm.albedo(po, geoms, mats, {5: one}, cam, depth), "one texel changed")
+        assert launches(pt)[0] == 2
+        pt.set_texture(5, one.copy())
+        pt.albedo()
+        assert launches(pt)[0] == 2
+    finally:
+        pt.pathtraceFree()
+
+
 def test_unit_albedo_switched_on_is_switched_off(pt, po, scenes, launch_plan):
     w, h = 97, 61
     g0, mats, cam, depth, _ = textured(pt)

@@ -536,10 +536,77 @@ def test_get_bump_map_returns_what_was_set(pt, scenes, launch_plan):
         pt.pathtraceFree()
 
 
+def interleaved_steps(pt, po):
+    """Textures and bump maps of materials A < B set, replaced and removed in turn -- A's maps change size, which moves B's texels
+    in the session's arrays -- on cornell_bumped at 40 x 26, depth 3.  Returns (geoms, materials, camera, depth, the materials looked
+    at, steps [(kind, material, texels or None)], the running sum of iterations 1 and 2 after every step): the numpy model's, the
+    plain oracle's once nothing is left.  Computed once per module, never written afterwards."""
+    if "interleaved" not in _cache:
+        geoms, mats, cam, _, _ = bumped(pt)
+        cam, depth = _resized(cam, 40, 26), 3
+        A, B, other = 1, 5, 6
+        steps = [("bump", A, random_bump(4, 21)),                        # before any texture: the TEX forms read a texture table of zeros
+                 ("texture", B, random_texture(1, 22)), ("texture", A, random_texture(3, 23)), ("texture", A, random_texture(4, 24)),
+                 ("texture", B, None), ("bump", A, None), ("texture", A, None)]
+        held = {"texture": {}, "bump": {}}
+        want = []
+        for kind, m, t in steps:
+            held[kind][m] = t
+            model = bm.Model(po, geoms, mats, cam, depth)
+            for k, v in held["texture"].items():
+                model.set_texture(k, v)
+            for k, v in held["bump"].items():
+                model.set_bump_map(k, v)
+            for it in (1, 2):
+                model.iterate(it)
+            want.append(model.image.copy())
+        assert all(v is None for d in held.values() for v in d.values())
+        oracle = po.Tracer(np.ascontiguousarray(geoms).view(po.GEOM_DT), np.ascontiguousarray(mats).view(po.MATERIAL_DT), cam, depth,
+                           flags=po.F_COMPACT, trig=po.TRIG_SHARED)
+        for it in (1, 2):
+            oracle.iterate(it)
+        want[-1] = oracle.image.copy()
+        for k in range(1, len(want)):                                    # every step shows in the picture
+            assert (bits(want[k]) != bits(want[k - 1])).any(), k
+        for a in want:
+            a.setflags(write=False)
+        _cache["interleaved"] = (geoms, mats, cam, depth, (A, B, other), steps, want)
+    return _cache["interleaved"]
+
+
+def test_interleaved_set_replace_remove(pt, po, launch_plan):
+    """After every step of interleaved_steps: the getters give back what the test holds for each material, and a fresh render of
+    two iterations is the model's bit for bit -- the maps of the materials a call did not name are where the new tables say."""
+    geoms, mats, cam, depth, looked_at, steps, want = interleaved_steps(pt, po)
+    pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT | pt.PT_TEXTURES, max_batch=2)
+    try:
+        held = {"texture": {}, "bump": {}}
+        setters = {"texture": pt.set_texture, "bump": pt.set_bump_map}
+        getters = {"texture": pt.get_texture, "bump": pt.get_bump_map}
+        for k, (kind, m, t) in enumerate(steps):
+            setters[kind](m, t)
+            held[kind][m] = t
+            for kind2 in held:
+                for m2 in looked_at:
+                    got, kept = getters[kind2](m2), held[kind2].get(m2)
+                    assert (got is None) if kept is None else (got is not None and got.shape == kept.shape and got.tobytes() == kept.tobytes()), \
+                        (k, kind2, m2)
+            pt.clear_image()
+            pt.pathtrace(None, 0, 1)
+            same(pt.pathtrace(None, 0, 2), want[k], "after step %d (%s of material %d)" % (k, kind, m))
+    finally:
+        pt.pathtraceFree()
+
+
 def test_refusals(pt, scenes):
     geoms, mats, cam, depth, _, _, _, _ = scene_arrays(pt, scenes, "bumped")
     tex = np.ones((6, 2, 2, 3), dtype=F32)
     L = pt.library()
+    k = C.c_int(0)
+
+    def says(rc, text):                                              # PT_ERR_INVALID and the whole message
+        assert rc == -1 and L.pt_last_error() == text.encode(), (rc, L.pt_last_error())
+
     pt.pathtraceFree()
     with pytest.raises(pt.PtError):                                  # before pt_init
         pt.set_bump_map(0, tex)
@@ -549,6 +616,9 @@ def test_refusals(pt, scenes):
             pt.set_bump_map(0, tex)
         with pytest.raises(pt.PtError):
             pt.get_bump_map(0)
+        # (the flag is looked at before the material, the material before the size)
+        says(L.pt_set_bump_map(-1, tex.ctypes.data, -1), "pt_set_bump_map: the session was not initialised with PT_TEXTURES")
+        says(L.pt_get_bump_map(-1, None, 0, None), "pt_get_bump_map: the session was not initialised with PT_TEXTURES")
     finally:
         pt.pathtraceFree()
     pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT | pt.PT_TEXTURES)
@@ -558,9 +628,22 @@ def test_refusals(pt, scenes):
                 pt.set_bump_map(m, tex)
             with pytest.raises(pt.PtError):
                 pt.get_bump_map(m)
+            says(L.pt_set_bump_map(m, None, -1), "pt_set_bump_map: material %d outside [0, %d)" % (m, len(mats)))
+            says(L.pt_get_bump_map(m, None, 0, None), "pt_get_bump_map: material %d outside [0, %d)" % (m, len(mats)))
         assert L.pt_set_bump_map(0, tex.ctypes.data, -1) < 0 and L.pt_set_bump_map(0, tex.ctypes.data, 1025) < 0
+        for n in (-1, 1025):
+            says(L.pt_set_bump_map(0, None, n), "pt_set_bump_map: n = %d outside [0, 1024]" % n)
         assert L.pt_set_bump_map(0, None, 2) < 0 and b"null" in L.pt_last_error()
+        says(L.pt_set_bump_map(0, None, 2), "pt_set_bump_map: null texels with n = 2")
         assert L.pt_get_bump_map(0, None, 0, None) < 0
+        says(L.pt_get_bump_map(0, None, 0, None), "pt_get_bump_map: null n")
+        assert pt.get_bump_map(0) is None                            # a refused call changes nothing
+        pt.set_bump_map(0, tex)
+        out = np.zeros((24, 3), dtype=F32)
+        says(L.pt_get_bump_map(0, out.ctypes.data, 23, C.byref(k)), "pt_get_bump_map: room for 23 texels, the map has 24")
+        assert k.value == 2 and not out.any()
+        says(L.pt_get_bump_map(0, None, 24, C.byref(k)), "pt_get_bump_map: room for 0 texels, the map has 24")
+        assert L.pt_get_bump_map(0, out.ctypes.data, 24, C.byref(k)) == 0 and out.tobytes() == tex.tobytes()
         assert L.pt_set_bump_map(0, None, 0) == 0 and L.pt_set_bump_map(0, tex.ctypes.data, 0) == 0 and pt.get_bump_map(0) is None
     finally:
         pt.pathtraceFree()

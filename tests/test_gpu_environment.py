@@ -332,16 +332,25 @@ def test_refusals(pt, scenes):
     try:
         for size in (-1, 1025):
             assert L.pt_set_environment(t.ctypes.data, size) == -1 and b"pt_set_environment" in L.pt_last_error()
+            assert L.pt_last_error() == b"pt_set_environment: n = %d outside [0, 1024]" % size
+            assert L.pt_set_environment(None, size) == -1            # (the size is looked at before the texels)
+            assert L.pt_last_error() == b"pt_set_environment: n = %d outside [0, 1024]" % size
         assert L.pt_set_environment(None, 2) == -1 and b"pt_set_environment" in L.pt_last_error()
+        assert L.pt_last_error() == b"pt_set_environment: null texels with n = 2"
         assert L.pt_get_environment(None, 0, None) == -1
+        assert L.pt_last_error() == b"pt_get_environment: null n"
         assert pt.get_environment() is None                          # a refused call changes nothing
         pt.set_environment(t)
         assert L.pt_get_environment(t.ctypes.data, 23, C.byref(n)) == -1 and n.value == 2      # room for 23 of 24 texels
+        assert L.pt_last_error() == b"pt_get_environment: room for 23 texels, the map has 24"
+        assert L.pt_get_environment(None, 24, C.byref(n)) == -1
+        assert L.pt_last_error() == b"pt_get_environment: room for 0 texels, the map has 24"
         assert L.pt_set_environment(None, 0) == 0 and L.pt_set_environment(t.ctypes.data, 0) == 0
         assert pt.get_environment() is None
     finally:
         pt.pathtraceFree()
     assert L.pt_set_environment(t.ctypes.data, 2) == -1 and b"pt_set_environment" in L.pt_last_error()     # before pt_init
+    assert L.pt_last_error() == b"pt_set_environment: not initialised"
 
 
 # ---- the headless host -------------------------------------------------------------------------------------------------

@@ -317,6 +317,11 @@ def test_refusals(pt):
     geoms, mats, cam, depth, tris, meshes, vn = cases.scene_arrays(pt, "cornell")
     L = pt.library()
     scene = pt.Scene(geoms, mats, cam, depth, triangles=tris, meshes=meshes)
+    k = C.c_int(0)
+
+    def says(rc, text):                                              # PT_ERR_INVALID and the whole message
+        assert rc == -1 and L.pt_last_error() == text.encode(), (rc, L.pt_last_error())
+
     pt.pathtraceFree()
     with pytest.raises(pt.PtError):                                  # before pt_init
         pt.set_vertex_normals(vn)
@@ -328,6 +333,8 @@ def test_refusals(pt):
             pt.set_vertex_normals(vn)
         with pytest.raises(pt.PtError):
             pt.get_vertex_normals()
+        says(L.pt_set_vertex_normals(None, -1), "pt_set_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS")
+        says(L.pt_get_vertex_normals(None, 0, None), "pt_get_vertex_normals: the session was not initialised with PT_SMOOTH_NORMALS")
     finally:
         pt.pathtraceFree()
     S = pt.PT_SMOOTH_NORMALS
@@ -344,8 +351,19 @@ def test_refusals(pt):
         assert L.pt_set_vertex_normals(vn.ctypes.data, -1) < 0
         assert L.pt_set_vertex_normals(None, len(vn)) < 0 and b"null" in L.pt_last_error()
         assert L.pt_get_vertex_normals(None, 0, None) < 0
+        for count in (len(vn) - 1, len(vn) + 1):
+            says(L.pt_set_vertex_normals(vn.ctypes.data, count), "pt_set_vertex_normals: %d triangles, the session has %d" % (count, len(vn)))
+        says(L.pt_set_vertex_normals(None, -1), "pt_set_vertex_normals: num_triangles = -1")
+        says(L.pt_set_vertex_normals(None, len(vn) + 1), "pt_set_vertex_normals: null normals with num_triangles = %d" % (len(vn) + 1))
+        says(L.pt_get_vertex_normals(None, 0, None), "pt_get_vertex_normals: null num_triangles")
         assert L.pt_set_vertex_normals(None, 0) == 0 and pt.get_vertex_normals() is None
         assert L.pt_set_vertex_normals(vn.ctypes.data, len(vn)) == 0
+        out = np.zeros_like(vn)
+        says(L.pt_get_vertex_normals(out.ctypes.data, len(vn) - 1, C.byref(k)),
+             "pt_get_vertex_normals: room for %d triangles, the session has %d" % (len(vn) - 1, len(vn)))
+        assert k.value == len(vn) and not out.any()
+        says(L.pt_get_vertex_normals(None, len(vn), C.byref(k)), "pt_get_vertex_normals: room for 0 triangles, the session has %d" % len(vn))
+        assert L.pt_get_vertex_normals(out.ctypes.data, len(vn), C.byref(k)) == 0 and out.tobytes() == vn.tobytes()
     finally:
         pt.pathtraceFree()
 

@@ -425,12 +425,20 @@ def test_refusals(pt, scenes):
     refused(T | pt.PT_COMPACT | pt.PT_DIRECT_LIGHT, "PT_DIRECT_LIGHT")
     tex = np.ones((6, 2, 2, 3), dtype=F32)
     L = pt.library()
+    k = C.c_int(0)
+
+    def says(rc, text):                                              # PT_ERR_INVALID and the whole message
+        assert rc == -1 and L.pt_last_error() == text.encode(), (rc, L.pt_last_error())
+
     pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT)        # a session without the flag
     try:
         with pytest.raises(pt.PtError):
             pt.set_texture(0, tex)
         with pytest.raises(pt.PtError):
             pt.get_texture(0)
+        # (the flag is looked at before the material, the material before the size)
+        says(L.pt_set_texture(-1, tex.ctypes.data, -1), "pt_set_texture: the session was not initialised with PT_TEXTURES")
+        says(L.pt_get_texture(-1, None, 0, None), "pt_get_texture: the session was not initialised with PT_TEXTURES")
     finally:
         pt.pathtraceFree()
     pt.pathtraceInit(pt.Scene(geoms, mats, cam, depth), flags=pt.PT_COMPACT | T)
@@ -440,9 +448,22 @@ def test_refusals(pt, scenes):
                 pt.set_texture(m, tex)
             with pytest.raises(pt.PtError):
                 pt.get_texture(m)
+            says(L.pt_set_texture(m, None, -1), "pt_set_texture: material %d outside [0, %d)" % (m, len(mats)))
+            says(L.pt_get_texture(m, None, 0, None), "pt_get_texture: material %d outside [0, %d)" % (m, len(mats)))
         assert L.pt_set_texture(0, tex.ctypes.data, -1) < 0 and L.pt_set_texture(0, tex.ctypes.data, 1025) < 0
+        for n in (-1, 1025):
+            says(L.pt_set_texture(0, None, n), "pt_set_texture: n = %d outside [0, 1024]" % n)
         assert L.pt_set_texture(0, None, 2) < 0 and b"null" in L.pt_last_error()
+        says(L.pt_set_texture(0, None, 2), "pt_set_texture: null texels with n = 2")
         assert L.pt_get_texture(0, None, 0, None) < 0
+        says(L.pt_get_texture(0, None, 0, None), "pt_get_texture: null n")
+        assert pt.get_texture(0) is None                             # a refused call changes nothing
+        pt.set_texture(0, tex)
+        out = np.zeros((24, 3), dtype=F32)
+        says(L.pt_get_texture(0, out.ctypes.data, 23, C.byref(k)), "pt_get_texture: room for 23 texels, the texture has 24")
+        assert k.value == 2 and not out.any()
+        says(L.pt_get_texture(0, None, 24, C.byref(k)), "pt_get_texture: room for 0 texels, the texture has 24")
+        assert L.pt_get_texture(0, out.ctypes.data, 24, C.byref(k)) == 0 and out.tobytes() == tex.tobytes()
         assert L.pt_set_texture(0, None, 0) == 0 and L.pt_set_texture(0, tex.ctypes.data, 0) == 0 and pt.get_texture(0) is None
     finally:
         pt.pathtraceFree()
