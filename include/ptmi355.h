@@ -261,7 +261,20 @@ enum pt_flags {
                                     would take the two-kernel form (their planes carry one normal, and the guard needs two)
                                     and with PT_TEXTURES or PT_DIRECT_LIGHT (the combined kernel forms are a later change).
                                     PT_FAKE_SHADER ignores the flag. */
-    PT_ASYNC_IMAGE   = 1u << 7   /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
+    PT_MOMENTS       = 1u << 17, /* opt-in: the session keeps, beside the running sum, two float planes of per-pixel LUMINANCE
+                                    MOMENTS -- M1 += l, M2 += l * l for every iteration gathered, in iteration order, l =
+                                    (0.2126f r + 0.7152f g) + 0.0722f b of the colour that iteration's path ended with (0 for a
+                                    path that ended with colour 0) -- which pt_denoise_variance turns into the noise estimate
+                                    that steers its filter ("the filter steered by the pixels' own noise" below; DESIGN.md
+                                    section 6.27).  The image, pt_stats, the ray counters and pt_export_paths are those of the
+                                    unflagged session bit for bit.  Every sample of a flagged session is gathered by the gather
+                                    kernel: a one-iteration call does not gather inside its launch, a host image is handed
+                                    over by the plain copies, and PT_LOOKAHEAD is ignored (as with PT_ASYNC_IMAGE or
+                                    PT_CACHE_FIRST).  Batches, asynchronous batches, the stepping interface and every shading
+                                    flag (PT_FAKE_SHADER included) work unchanged.  8 bytes per pixel, zeroed by pt_init,
+                                    released by pt_free.  Refused by pt_init (PT_ERR_INVALID) with tile_count > 1 or several
+                                    devices. */
+    PT_ASYNC_IMAGE   = 1u << 7  /* opt-in: pt_trace / pt_trace_batch return without waiting; the copy of the
                                     running sum into host_image_sum overlaps the NEXT call's tracing and is
                                     complete when the next pt_trace / pt_trace_batch returns, or after
                                     pt_synchronize, pt_get_image or pt_free (pt_get_stats needs pt_synchronize).  (pt_trace: the launch
@@ -592,7 +605,8 @@ int pt_clear_image(void);
 /* Resume an accumulation: the running sum becomes `host_image_sum` (W*H*3 floats, e.g. what pt_get_image / the host's
  * PFM dump returned after iteration k); tracing iterations k+1.. then yields, bit for bit, the image of the
  * uninterrupted run -- the running sum is the whole state the reference carries from one iteration to the next
- * (dev_image, pathtrace.cu:71,84,389; the iteration number is the caller's).  Synchronises the session first. */
+ * (dev_image, pathtrace.cu:71,84,389; the iteration number is the caller's).  Synchronises the session first.  A PT_MOMENTS
+ * session carries its two moment planes as well, which this call leaves alone: a host that resumes one calls pt_set_moments too. */
 int pt_set_image(const float *host_image_sum);
 float *pt_device_image(void);                        /* device pointer of the accumulation buffer */
 
@@ -695,6 +709,48 @@ int pt_history_reset(void);       /* forget everything; the next temporal call e
  * Out of scope: demodulating by specular.color or by the albedo seen through a mirror or glass; history kept demodulated. */
 int pt_set_denoise_albedo(int enable);
 int pt_albedo(float *rgb);
+
+/* ---- the filter steered by the pixels' own noise: per-pixel luminance moments (PT_MOMENTS) ------------------------------------
+ * pt_denoise's colour stop is a constant in absolute radiance units that fits one scene, sample count and exposure.  A session
+ * with PT_MOMENTS measures every pixel's noise instead, and pt_denoise_variance stops at a multiple of it -- the core of SVGF
+ * (Schied et al. 2017) on top of Dammertz' filter (DESIGN.md section 6.27 has the complete specification; tests/variance_model.py
+ * is its numpy form, equal bit for bit).  All arithmetic binary32, one rounding per operation in the order written, no FMA;
+ * lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b;  n = (float)iter.
+ * Moments: see PT_MOMENTS above.  pt_get_moments copies them to the host (W*H floats each, either pointer may be NULL) and
+ * synchronises like pt_get_image; pt_set_moments replaces them (both pointers required) and is the companion of pt_set_image:
+ * pt_set_image leaves the moments alone, so a host that RESUMES an accumulation calls BOTH.  pt_clear_image zeroes the moments
+ * with the sum; pt_set_camera leaves them alone, as it does the sum.  PT_ERR_INVALID: before pt_init; a session without the
+ * flag; a NULL pointer to pt_set_moments.
+ * Filter:  c_0[P] = sum[P] / n per channel;  mu = M1[P] / n;  var_0[P] = fmaxf(M2[P] / n - mu * mu, 0) / fmaxf(n - 1, 1) -- the
+ * variance of the MEAN; iter = 1 gives exactly 0.  Level l = 0 .. levels - 1, step s = 2^l, on (c, var):
+ *   gv[P]  = the 3 x 3 Gaussian {1/4, 1/2, 1/4}^2 of var around P: acc = acc + var[Q] * (g[dy] * g[dx]) from 0, dy outer, the
+ *            coordinates of Q clamped to the image, none skipped;
+ *   den[P] = sigma_luminance * sqrt(fmaxf(gv[P], 2^-40)), the root correctly rounded;
+ *   for the 5 x 5 taps Q = P + (dx s, dy s) of pt_denoise's kernel h, dy outer, those outside the image skipped:
+ *     w = exp_neg(fabsf(lum(c[P]) - lum(c[Q])) / den[P]) * exp_neg(|dn|^2 / sn^2) * exp_neg(|dp|^2 / sp^2);  wt = w * (h[dy] * h[dx]);
+ *     sum += c[Q] * wt per channel;  vsum += var[Q] * (wt * wt);  cum += wt;
+ *   c'[P] = sum / cum;  var'[P] = vsum / (cum * cum).
+ * sigma_luminance is NOT halved per level: the variance it multiplies shrinks by itself as the levels average.  levels = 0
+ * returns the mean (and var_0 through pt_variance).  The RGBA bytes follow pt_denoise's rule.  Denormal intermediates (l * l of
+ * a nearly black sample) follow IEEE; the floor 2^-40 keeps them out of every divisor.  With iter = 1 every den is
+ * sigma_luminance * 2^-20 and only taps of equal luminance pass: the first sample of a view is pt_denoise's business.
+ * pt_denoise_variance shares pt_denoise's contract: synchronous, on the session's stream behind everything enqueued; it READS the
+ * session and changes nothing in it (no counter moves); its buffers (48 bytes per pixel) are allocated on first use and released
+ * by pt_free; it uses the same G-buffer, computed once per camera; the result stays on the device, where
+ * pt_denoised_device_image returns it; it neither reads nor disturbs pt_denoise's planes or the temporal history.  It IGNORES the
+ * pt_set_denoise_albedo switch: demodulation would need the moments of demodulated luminance, a later change.  One launch per
+ * level.  pt_variance: var_0 of the last pt_denoise_variance call's input (W*H floats, host; NULL copies nothing).
+ * PT_ERR_INVALID: everything pt_denoise refuses (before pt_init; params == NULL; levels outside [0, 10]; iter < 1; sigma_normal or
+ * sigma_position not a finite number > 0 or with a square that is not a normal number; tiled / multi-device sessions); a session
+ * without PT_MOMENTS; sigma_luminance not a finite number > 0, or sigma_luminance * 2^-20 not a normal binary32 number;
+ * pt_variance before the first pt_denoise_variance call.
+ * Out of scope: moments in tiled or multi-device sessions and under PT_LOOKAHEAD windows; temporal accumulation of the moments
+ * across camera moves; albedo-demodulated variance; SVGF's spatial variance estimate for iter < 4. */
+typedef struct pt_variance_params { int32_t levels; float sigma_luminance, sigma_normal, sigma_position; } pt_variance_params;
+int pt_get_moments(float *m1, float *m2);
+int pt_set_moments(const float *m1, const float *m2);
+int pt_denoise_variance(const pt_variance_params *params, int iter, float *host_rgb, uint8_t *host_rgba);
+int pt_variance(float *host_var);
 int pt_get_stats(pt_stats *stats);
 /* rays traced since pt_init, read from the device-side counter (includes
  * asynchronous batches); synchronises the stream.  Negative = pt_status. */

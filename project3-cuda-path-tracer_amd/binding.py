@@ -44,6 +44,7 @@ PT_DIRECT_LIGHT = 8192      # the last bounce aims a final ray at a sampled ligh
 PT_DIRECT_SKY = 32768       # ... and the environment map is one more light element (with PT_DIRECT_LIGHT; include/ptmi355.h)
 PT_TEXTURES = 16384         # a cube texture per material tints spheres and cubes (include/ptmi355.h)
 PT_SMOOTH_NORMALS = 65536   # per-vertex normals smooth the shading of triangle meshes (include/ptmi355.h)
+PT_MOMENTS = 131072         # the session keeps per-pixel luminance moments for denoise_variance (include/ptmi355.h)
 BVH_NODE_WORDS = 16
 
 
@@ -84,6 +85,11 @@ class Profile(C.Structure):
 
 class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float)]
+
+
+class VarianceParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_position", C.c_float)]
 
 
@@ -213,6 +219,10 @@ def library():
             L.pt_get_vertex_normals.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
             L.pt_smooth_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
             L.pt_probe_smooth_normal.argtypes = L.pt_smooth_normal.argtypes
+            L.pt_get_moments.argtypes = [C.c_void_p, C.c_void_p]
+            L.pt_set_moments.argtypes = [C.c_void_p, C.c_void_p]
+            L.pt_denoise_variance.argtypes = [C.POINTER(VarianceParams), C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_variance.argtypes = [C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -833,6 +843,47 @@ def albedo():
     w, h = _scene.resolution
     out = np.zeros((w * h, 3), dtype=np.float32)
     _chk(library().pt_albedo(_p(out)))
+    return out
+
+
+def get_moments():
+    """The luminance moments a PT_MOMENTS session keeps beside the running sum (include/ptmi355.h: pt_get_moments):
+    (M1, M2), [npix] float32 each."""
+    if _scene is None:
+        _chk(library().pt_get_moments(None, None))                          # raises "not initialised"
+    w, h = _scene.resolution
+    m1, m2 = np.zeros(w * h, dtype=np.float32), np.zeros(w * h, dtype=np.float32)
+    _chk(library().pt_get_moments(_p(m1), _p(m2)))
+    return m1, m2
+
+
+def set_moments(m1, m2):
+    """Resume an accumulation's moments, the companion of set_image() (include/ptmi355.h: pt_set_moments)."""
+    a, b = np.ascontiguousarray(m1, dtype=np.float32), np.ascontiguousarray(m2, dtype=np.float32)
+    _chk(library().pt_set_moments(_p(a), _p(b)))
+
+
+def denoise_variance(iteration, levels=5, sigma_luminance=4.0, sigma_normal=0.35, sigma_position=0.5, rgba=False):
+    """The A-trous filter steered by the pixels' own measured noise (include/ptmi355.h: pt_denoise_variance; a PT_MOMENTS
+    session): the denoised MEAN as [npix, 3] float32; with rgba=True also its RGBA8 form, (mean, [npix, 4] uint8)."""
+    if _scene is None:
+        _chk(library().pt_denoise_variance(None, int(iteration), None, None))   # raises "not initialised"
+    w, h = _scene.resolution
+    prm = VarianceParams(int(levels), float(sigma_luminance), float(sigma_normal), float(sigma_position))
+    img = np.zeros((w * h, 3), dtype=np.float32)
+    px = np.zeros((w * h, 4), dtype=np.uint8) if rgba else None
+    _chk(library().pt_denoise_variance(C.byref(prm), int(iteration), _p(img), _p(px)))
+    return (img, px) if rgba else img
+
+
+def variance():
+    """var_0, the variance of the mean's luminance, of the last denoise_variance() call's input (include/ptmi355.h:
+    pt_variance): [npix] float32."""
+    if _scene is None:
+        _chk(library().pt_variance(None))                                   # raises "not initialised"
+    w, h = _scene.resolution
+    out = np.zeros(w * h, dtype=np.float32)
+    _chk(library().pt_variance(_p(out)))
     return out
 
 

@@ -78,6 +78,10 @@ void pt_free(void) {
     }
     if (R.tp_hc) (void)hipFree(R.tp_hc);
     if (R.tp_hn) (void)hipFree(R.tp_hn);
+    if (R.mom_mem) (void)hipFree(R.mom_mem);
+    for (int k = 0; k < 2; ++k) if (R.vr_plane[k]) (void)hipFree(R.vr_plane[k]);
+    if (R.vr_var0) (void)hipFree(R.vr_var0);
+    if (R.vr_out) (void)hipFree(R.vr_out);
     if (R.dbg_counts) (void)hipFree(R.dbg_counts);
     if (R.copy_stream) (void)hipStreamSynchronize(R.copy_stream);
     for (auto &h : R.host_regs) (void)hipHostUnregister(h.ptr);
@@ -146,6 +150,8 @@ static int init_impl(const pt_scene_desc *d) {
     const int tile_count = d->tile_count <= 0 ? 1 : d->tile_count;
     if (d->tile_index < 0 || d->tile_index >= tile_count) return fail(PT_ERR_INVALID, "pt_init: tile_index %d / tile_count %d", d->tile_index, tile_count);
     if (tile_count > 1 && d->strip_rows <= 0) return fail(PT_ERR_INVALID, "pt_init: strip_rows must be > 0 when tiling");
+    if ((d->flags & PT_MOMENTS) && tile_count > 1)
+        return fail(PT_ERR_INVALID, "pt_init: PT_MOMENTS needs a session that holds the frame, not one tile of it (tile_count = %d)", tile_count);
     for (int i = 0; i < d->num_geoms; ++i) {
         const pt_geom &g = d->geoms[i];
         if (g.type < PT_SPHERE || g.type > PT_TRIANGLE_MESH) return fail(PT_ERR_INVALID, "pt_init: geom %d has type %d", i, g.type);
@@ -231,6 +237,9 @@ static int init_impl(const pt_scene_desc *d) {
     if (const char *e = pt_experiment("PTMI355_LANE_STREAMS")) R.ov_streams = std::max(1, atoi(e));
     R.epi_enabled = true;
     if (const char *e = pt_experiment("PTMI355_HOST_EPILOGUE")) R.epi_enabled = atoi(e) != 0;
+    // PT_MOMENTS: every sample reaches the image through k_gather, whose MOM form keeps the moments -- no
+    // finalGather inside a one-iteration k_iteration (the launch itself stays, k_gather behind it), a host image by the plain copies
+    if (d->flags & PT_MOMENTS) R.epi_enabled = false;
     if (const char *e = pt_experiment("PTMI355_EPI_DIRECT")) R.epi_direct_enabled = atoi(e) != 0;
     R.defer_enabled = true;
     if (const char *e = pt_experiment("PTMI355_DEFER_DIR")) R.defer_enabled = atoi(e) != 0;
@@ -475,6 +484,10 @@ static int init_impl(const pt_scene_desc *d) {
         HIPCHK(hipMalloc(&R.image, (size_t)R.npix * 3 * 4));
         R.own_image = true;
         HIPCHK(hipMemsetAsync(R.image, 0, (size_t)R.npix * 3 * 4, R.stream));      // pathtrace.cu:85
+    }
+    if (R.flags & PT_MOMENTS) {                                // M1[npix], then M2[npix]: only a flagged session has them
+        HIPCHK(hipMalloc((void **)&R.mom_mem, (size_t)R.npix * 2 * sizeof(float)));
+        HIPCHK(hipMemsetAsync(R.mom_mem, 0, (size_t)R.npix * 2 * sizeof(float), R.stream));
     }
     R.max_tiles = (R.cap + TILE - 1) / TILE;
     // only the election buckets of the bounces this scene can run are cleared per batch
@@ -794,7 +807,8 @@ int pt_trace_mapped(int iter, float *mapped) {
 // other contexts or ranks (`shared` in la_trace) only ever receives this tile's pixels.
 // ---------------------------------------------------------------------------------------------------------------------
 bool la_possible(void) {
-    return (R.flags & PT_LOOKAHEAD) && !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST | PT_ASYNC_IMAGE)) &&
+    // (PT_MOMENTS: k_gather_one has no moments form -- its register budget is the point of it -- so the flag is ignored there too)
+    return (R.flags & PT_LOOKAHEAD) && !(R.flags & (PT_UNFUSED | PT_FAKE_SHADER | PT_CACHE_FIRST | PT_ASYNC_IMAGE | PT_MOMENTS)) &&
            (!(R.flags & PT_SORT_MATERIAL) || R.sort_keys > 0) && (R.map.tile_count == 1 || R.la_tiles_ok) && R.max_batch >= 2 &&
            R.ov_enabled && !R.profiling && !R.dbg_counts;
 }
@@ -1171,8 +1185,33 @@ int pt_clear_image(void) {
     if (!R.live) return fail(PT_ERR_INVALID, "pt_clear_image: not initialised");
     if (R.flags & PT_LOOKAHEAD) { const int rc = la_discard(LA_STREAM); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(R.image, 0, (size_t)R.npix * 12, R.stream));
+    if (R.mom_mem) HIPCHK(hipMemsetAsync(R.mom_mem, 0, (size_t)R.npix * 2 * sizeof(float), R.stream));   // (PT_MOMENTS: the moments of that sum)
     HIPCHK(hipStreamSynchronize(R.stream));
     R.image_epoch++;
+    return PT_OK;
+}
+
+// PT_MOMENTS: the two luminance moment planes k_gather<true> keeps beside the running sum.
+// pt_get_moments synchronises like pt_get_image; pt_set_moments is pt_set_image's companion (everything in flight comes first).
+int pt_get_moments(float *m1, float *m2) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_get_moments: not initialised");
+    if (!R.mom_mem) return fail(PT_ERR_INVALID, "pt_get_moments: the session was initialised without PT_MOMENTS");
+    HIPCHK(hipStreamSynchronize(R.stream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    if (m1) HIPCHK(hipMemcpy(m1, R.mom_mem, (size_t)R.npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (m2) HIPCHK(hipMemcpy(m2, R.mom_mem + R.npix, (size_t)R.npix * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_set_moments(const float *m1, const float *m2) {
+    if (!R.live) return fail(PT_ERR_INVALID, "pt_set_moments: not initialised");
+    if (!R.mom_mem) return fail(PT_ERR_INVALID, "pt_set_moments: the session was initialised without PT_MOMENTS");
+    if (!m1 || !m2) return fail(PT_ERR_INVALID, "pt_set_moments: null buffer");
+    HIPCHK(hipStreamSynchronize(R.stream));
+    if (R.copy_stream) HIPCHK(hipStreamSynchronize(R.copy_stream));
+    HIPCHK(hipMemcpy(R.mom_mem, m1, (size_t)R.npix * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.mom_mem + R.npix, m2, (size_t)R.npix * sizeof(float), hipMemcpyHostToDevice));
+    R.ov_active = false;
     return PT_OK;
 }
 

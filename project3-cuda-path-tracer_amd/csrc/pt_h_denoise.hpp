@@ -316,6 +316,135 @@ int pt_history_reset(void) {
     return PT_OK;
 }
 
+// ---- the filter steered by per-pixel luminance moments (PT_MOMENTS) --------------------------------
+// pt_denoise's contract: synchronous, on the launch stream behind everything enqueued, reads the session (running sum, the two
+// moment planes, the G-buffer it shares with pt_denoise) and writes buffers of its own -- not pt_denoise's planes, not the
+// temporal history --; no counter moves.  The albedo switch is not read.
+static int variance_args_ok(const char *who, const pt_variance_params *params, int iter, float &sn2, float &sp2) {
+    if (!R.live) return fail(PT_ERR_INVALID, "%s: not initialised", who);
+    if (!params) return fail(PT_ERR_INVALID, "%s: params is null", who);
+    const int levels = params->levels;
+    if (levels < 0 || levels > 10) return fail(PT_ERR_INVALID, "%s: levels %d outside [0, 10]", who, levels);
+    const float sig[3] = {params->sigma_luminance, params->sigma_normal, params->sigma_position};
+    const char *names[3] = {"sigma_luminance", "sigma_normal", "sigma_position"};
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(sig[k]) || !(sig[k] > 0.0f))
+            return fail(PT_ERR_INVALID, "%s: %s = %g is not a finite number > 0", who, names[k], (double)sig[k]);
+    sn2 = sig[1] * sig[1]; sp2 = sig[2] * sig[2];
+    if (!std::isnormal(sn2)) return fail(PT_ERR_INVALID, "%s: sigma_normal = %g: its square is not a normal binary32 number", who, (double)sig[1]);
+    if (!std::isnormal(sp2)) return fail(PT_ERR_INVALID, "%s: sigma_position = %g: its square is not a normal binary32 number", who, (double)sig[2]);
+    // the smallest divisor a tap meets is sigma_luminance * sqrt(2^-40): a normal number, or the centre tap is 0 / 0
+    if (!std::isnormal(sig[0] * ldexpf(1.0f, -20)))
+        return fail(PT_ERR_INVALID, "%s: sigma_luminance = %g: sigma_luminance * 2^-20 is not a normal binary32 number", who, (double)sig[0]);
+    if (iter < 1) return fail(PT_ERR_INVALID, "%s: iter %d < 1", who, iter);
+    const int rc = denoise_session_ok(who);
+    if (rc) return rc;
+    if (!R.mom_mem) return fail(PT_ERR_INVALID, "%s: the session was initialised without PT_MOMENTS", who);
+    return PT_OK;
+}
+
+static int ensure_variance(bool rgba) {
+    const size_t n = (size_t)R.npix;
+    for (int k = 0; k < 2; ++k)
+        if (!R.vr_plane[k]) HIPCHK(hipMalloc((void **)&R.vr_plane[k], n * sizeof(float4)));
+    if (!R.vr_var0) HIPCHK(hipMalloc((void **)&R.vr_var0, n * sizeof(float)));
+    if (!R.vr_out) HIPCHK(hipMalloc((void **)&R.vr_out, n * 3 * sizeof(float)));
+    if (rgba && !R.dn_rgba) HIPCHK(hipMalloc((void **)&R.dn_rgba, n * 4));
+    return PT_OK;
+}
+
+// level l of `levels`: step 2^l, from the sum and the moments (l = 0) or the plane the level before wrote, into plane l & 1 --
+// the last one into vr_out (and `rgba`)
+static int launch_atrous_var(int l, int levels, float div, float sl, float sn2, float sp2, uint8_t *rgba) {
+    const float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
+    const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
+    const bool last = l == levels - 1;
+    float4 *out = R.vr_plane[l & 1];
+    float *out3 = last ? R.vr_out : (float *)nullptr;
+    const float vdiv = fmaxf(div - 1.0f, 1.0f);
+    const float *m1 = R.mom_mem, *m2 = R.mom_mem + R.npix;
+    if (l == 0)
+        hipLaunchKernelGGL(k_atrous_var<true>, grid, dim3(BLOCK), 0, R.stream, (const float *)R.image, m1, m2, (const float4 *)nullptr, gA, gB,
+                           out, R.vr_var0, out3, last ? rgba : (uint8_t *)nullptr, R.map.W, R.map.H, 1, div, vdiv, sl, sn2, sp2);
+    else
+        hipLaunchKernelGGL(k_atrous_var<false>, grid, dim3(BLOCK), 0, R.stream, (const float *)nullptr, m1, m2, (const float4 *)R.vr_plane[(l & 1) ^ 1],
+                           gA, gB, out, (float *)nullptr, out3, last ? rgba : (uint8_t *)nullptr, R.map.W, R.map.H, 1 << l, div, vdiv, sl, sn2, sp2);
+    HIPCHK(hipGetLastError());
+    R.vr_launches[0]++;
+    return PT_OK;
+}
+
+int pt_denoise_variance(const pt_variance_params *params, int iter, float *host_rgb, uint8_t *host_rgba) {
+    float sn2, sp2;
+    int rc = variance_args_ok("pt_denoise_variance", params, iter, sn2, sp2);
+    if (rc) return rc;
+    rc = ensure_variance(host_rgba != nullptr);
+    if (rc) return rc;
+    const int levels = params->levels;
+    const size_t n = (size_t)R.npix;
+    uint8_t *rgba = host_rgba ? R.dn_rgba : (uint8_t *)nullptr;
+    const float div = (float)iter;
+    if (levels == 0) {
+        hipLaunchKernelGGL(k_variance_mean, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, R.stream, (const float *)R.image,
+                           (const float *)R.mom_mem, (const float *)(R.mom_mem + R.npix), R.vr_out, R.vr_var0, rgba, (uint32_t)n, div,
+                           fmaxf(div - 1.0f, 1.0f));
+        HIPCHK(hipGetLastError());
+        R.vr_launches[1]++;
+    } else {
+        rc = ensure_gbuffer();
+        if (rc) return rc;
+        for (int l = 0; l < levels; ++l) {
+            rc = launch_atrous_var(l, levels, div, params->sigma_luminance, sn2, sp2, rgba);
+            if (rc) return rc;
+        }
+    }
+    R.vr_called = true;
+    R.dn_result = R.vr_out;
+    if (host_rgb) HIPCHK(hipMemcpyAsync(host_rgb, R.vr_out, n * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (host_rgba) HIPCHK(hipMemcpyAsync(host_rgba, R.dn_rgba, n * 4, hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_variance(float *host_var) {
+    int rc = denoise_session_ok("pt_variance");
+    if (rc) return rc;
+    if (!R.mom_mem) return fail(PT_ERR_INVALID, "pt_variance: the session was initialised without PT_MOMENTS");
+    if (!R.vr_called) return fail(PT_ERR_INVALID, "pt_variance: no pt_denoise_variance call since pt_init");
+    if (host_var) HIPCHK(hipMemcpyAsync(host_var, R.vr_var0, (size_t)R.npix * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+// diagnostics (ptdbg_variance_times, not in include/ptmi355.h): device times of every level of k_atrous_var, HIP events on the
+// session's stream, denoise_times' method: one pt_denoise_variance as warm-up, then `reps` rounds; ms[rep * levels + l].  The
+// result of the last round is that call's.
+int variance_times(const pt_variance_params *params, int iter, int reps, float *ms) {
+    int rc = one::pt_denoise_variance(params, iter, nullptr, nullptr);
+    if (rc) return rc;
+    if (reps < 1 || !ms || params->levels < 1) return fail(PT_ERR_INVALID, "ptdbg_variance_times: reps >= 1, levels >= 1 and a buffer");
+    const int levels = params->levels;
+    std::vector<hipEvent_t> ev((size_t)2 * levels, nullptr);
+    auto run = [&]() -> int {
+        for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+        const float sn2 = params->sigma_normal * params->sigma_normal, sp2 = params->sigma_position * params->sigma_position;
+        for (int rep = 0; rep < reps; ++rep) {
+            for (int l = 0; l < levels; ++l) {
+                HIPCHK(hipEventRecord(ev[2 * l], R.stream));
+                const int r = launch_atrous_var(l, levels, (float)iter, params->sigma_luminance, sn2, sp2, nullptr);
+                if (r) return r;
+                HIPCHK(hipEventRecord(ev[2 * l + 1], R.stream));
+            }
+            HIPCHK(hipStreamSynchronize(R.stream));
+            for (int l = 0; l < levels; ++l) HIPCHK(hipEventElapsedTime(&ms[(size_t)rep * levels + l], ev[2 * l], ev[2 * l + 1]));
+        }
+        return PT_OK;
+    };
+    rc = run();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
 // diagnostics (ptdbg_denoise_times, not in include/ptmi355.h): device times of the filter's launches, HIP events on the
 // session's stream.  After one pt_denoise(params, iter) as warm-up, `reps` rounds of: k_gbuffer (forced), every level of
 // k_atrous, and a device-to-device hipMemcpyAsync of the 56 bytes per pixel one level moves (colour + two G-buffer planes

@@ -427,9 +427,9 @@ int enqueue_end(void) {
     if (R.la_tracing) {
         // a window traced ahead of the caller (PT_LOOKAHEAD): its final colours stay where they are until the calls that
         // consume them (k_gather_one, one sample each); only its counters are folded, on the lane's own stream
-        hipLaunchKernelGGL(k_gather, dim3(1), dim3(BLOCK), 0, R.stream, R.image, R.final_mem, R.cap, R.map, R.step_count, R.ctl,
+        hipLaunchKernelGGL(k_gather<false>, dim3(1), dim3(BLOCK), 0, R.stream, R.image, R.final_mem, R.cap, R.map, R.step_count, R.ctl,
                            R.persist, session_bounces(), 0u, R.whole ? 1 : 0, 1, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
-                           (HostStats *)nullptr);
+                           (HostStats *)nullptr, Moments{nullptr, nullptr});
         R.whole = false;
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(R.lane_cur->traced, R.stream));
@@ -443,12 +443,15 @@ int enqueue_end(void) {
         HIPCHK(hipStreamWaitEvent(R.lane_main, R.lane_cur->traced, 0));
         gs = R.lane_main;
     }
-    hipLaunchKernelGGL(k_gather, dim3((R.map.tile_pixels + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, gs, R.image,
+    // (a PT_MOMENTS session: the form that also accumulates the luminance moments -- every sample of such a session comes through here)
+    const auto gather = R.mom_mem ? k_gather<true> : k_gather<false>;
+    hipLaunchKernelGGL(gather, dim3((R.map.tile_pixels + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, gs, R.image,
                        R.final_mem, R.cap, R.map,
                        R.step_count, R.ctl, R.persist, (R.flags & PT_FAKE_SHADER) ? 0 : session_bounces(),
                        (R.flags & PT_FAKE_SHADER) ? (uint32_t)R.map.tile_pixels * (uint32_t)R.step_count : 0u,
                        R.whole ? 1 : 0, R.epi_done ? 1 : 0, R.fin_serial, R.iter_counts, (uint32_t)R.grid_iter_cur,
-                       (R.whole && R.host_stats_serial) ? R.d_stats : (HostStats *)nullptr);
+                       (R.whole && R.host_stats_serial) ? R.d_stats : (HostStats *)nullptr,
+                       Moments{R.mom_mem, R.mom_mem ? R.mom_mem + R.npix : (float *)nullptr});
     R.whole = false;
     R.image_epoch++;
     HIPCHK(hipGetLastError());

@@ -276,6 +276,15 @@ struct Renderer {
     int tp_k = 0;
     float *tp_hc = nullptr, *tp_hn = nullptr;
     uint64_t tp_launches[2] = {0, 0};      // k_reproject / k_temporal_blend launches since pt_init (ptdbg_temporal)
+    // PT_MOMENTS / pt_denoise_variance (pt_h_denoise.hpp).  mom_mem: M1[npix] then M2[npix], the luminance
+    // moments k_gather<true> keeps beside the running sum -- allocated by pt_init in a flagged session only (non-null = flagged).
+    // The filter's buffers, allocated by its first call: vr_plane = the levels' ping-pong planes of {r, g, b, var} records,
+    // vr_var0 = var_0 of the last call's input (pt_variance; vr_called: there was one), vr_out = the result (packed float3).
+    float *mom_mem = nullptr;
+    float4 *vr_plane[2] = {nullptr, nullptr};
+    float *vr_var0 = nullptr, *vr_out = nullptr;
+    bool vr_called = false;
+    uint64_t vr_launches[2] = {0, 0};      // k_atrous_var / k_variance_mean launches since pt_init (ptdbg_variance)
     void *scratch = nullptr;      // export / import staging
     size_t scratch_bytes = 0;
     // stepping state

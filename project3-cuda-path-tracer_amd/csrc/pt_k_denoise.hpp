@@ -201,6 +201,126 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_mean(const float *__restrict_
     if (rgba) reinterpret_cast<uchar4 *>(rgba)[i] = tonemap_pixel(r, g, b, 1);
 }
 
+// ---- the filter steered by the pixels' own noise (pt_denoise_variance) ------------------------------
+// k_atrous's geometry -- one lane per pixel, a workgroup = 64 x 4 pixels, a wave = 64 consecutive pixels of a row, a row's five
+// taps loaded together -- on ping-pong planes of 16-byte records {r, g, b, var}: a tap is one aligned float4 load beside the two
+// G-buffer records, and the variance of the mean travels through the levels with the colour (var' = sum var[Q] wt^2 / cum^2).
+// The colour stop is |L[P] - L[Q]| / den[P], L = luminance of the record's colour, den = sl * sqrt(max(gv, 2^-40)) with gv the
+// 3 x 3 Gaussian {1/4, 1/2, 1/4}^2 of var around P, coordinates clamped to the image: nine scalar loads per pixel, once.
+// sl is NOT halved per level.  The root is the kernels' own (ptd::sqrt_normal_range: correctly rounded on [2^-102, 2^128),
+// and the floor keeps its argument inside).
+// FIRST (level 0, step 1): the workgroup forms c_0 = sum / div and var_0 = fmaxf(M2 / div - mu * mu, 0) / vdiv, mu = M1 / div
+// (vdiv = fmaxf(div - 1, 1), formed by the host), for its tile plus the halo of 2 once, in LDS, as k_atrous<true> forms its
+// means; taps and the prefilter's nine values come from there (the clamped neighbours of a pixel inside the image are inside
+// the image and within the halo), and var_0 of the own pixel goes to `var0` (pt_variance).  16-byte entries: a ds_read_b128 of 16
+// consecutive lanes covers the 64 banks once.
+// `out3` (the last level): the result as the packed float3 plane pt_denoised_device_image returns, and `rgba` from it
+// (optional); the levels before write `cout`.
+constexpr float VAR_FLOOR = 9.094947017729282e-13f;         // 2^-40
+__device__ __forceinline__ float var_of_mean(float m1, float m2, float div, float vdiv) {
+    const float mu = m1 / div;
+    return fmaxf(m2 / div - mu * mu, 0.0f) / vdiv;
+}
+template <bool FIRST>
+__global__ __launch_bounds__(BLOCK) void k_atrous_var(const float *__restrict__ sum, const float *__restrict__ m1,
+                                                      const float *__restrict__ m2, const float4 *__restrict__ cin,
+                                                      const float4 *__restrict__ gA, const float4 *__restrict__ gB,
+                                                      float4 *__restrict__ cout, float *__restrict__ var0, float *__restrict__ out3,
+                                                      uint8_t *__restrict__ rgba, int W, int H, int step, float div, float vdiv,
+                                                      float sl, float sn2, float sp2) {
+    __shared__ float4 tile_lds[FIRST ? AT_LH * AT_LW : 1];
+    const int tx = (int)(threadIdx.x & 63), ty = (int)(threadIdx.x >> 6);
+    const int x = (int)blockIdx.x * 64 + tx;
+    const int y = (int)blockIdx.y * WAVES + ty;
+    if (FIRST) {                                               // (step == 1)
+        const int x0 = (int)blockIdx.x * 64 - 2, y0 = (int)blockIdx.y * WAVES - 2;
+        for (int i = (int)threadIdx.x; i < AT_LH * AT_LW; i += BLOCK) {
+            const int ly = i / AT_LW, lx = i - ly * AT_LW;
+            const int gx = x0 + lx, gy = y0 + ly;
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                const size_t Q = (size_t)gy * (size_t)W + (size_t)gx;
+                tile_lds[i] = make_float4(sum[3 * Q + 0] / div, sum[3 * Q + 1] / div, sum[3 * Q + 2] / div, var_of_mean(m1[Q], m2[Q], div, vdiv));
+            }
+        }
+        __syncthreads();
+    }
+    if (x >= W || y >= H) return;
+    const size_t P = (size_t)y * (size_t)W + (size_t)x;
+    const int Pl = (ty + 2) * AT_LW + tx + 2;                 // this pixel's entry of tile_lds
+    constexpr float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    constexpr float g3[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+    const float4 cP = FIRST ? tile_lds[Pl] : cin[P];
+    // the 3 x 3 Gaussian of the variance around P: clamped coordinates, none skipped, dy outer
+    float pv[9];
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int yy = min(max(y + dy, 0), H - 1);
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xx = min(max(x + dx, 0), W - 1);
+            if (FIRST) pv[(dy + 1) * 3 + dx + 1] = tile_lds[Pl + (yy - y) * AT_LW + (xx - x)].w;
+            else pv[(dy + 1) * 3 + dx + 1] = cin[(size_t)yy * (size_t)W + (size_t)xx].w;
+        }
+    }
+    float gv = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) gv = gv + pv[k] * (g3[k / 3] * g3[k % 3]);
+    const float den = sl * ptd::sqrt_normal_range(fmaxf(gv, VAR_FLOOR));
+    const float LP = luminance(cP.x, cP.y, cP.z);
+    const float4 nP = gA[P], pP = gB[P];
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f, cum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = y + dy * step;
+        if (yy < 0 || yy >= H) continue;                       // (the same for the whole wave)
+        const size_t row = (size_t)yy * (size_t)W;
+        float4 qc[5], qn[5], qp[5];
+        bool in[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int xx = x + (k - 2) * step;
+            in[k] = xx >= 0 && xx < W;
+            const size_t Q = in[k] ? row + (size_t)xx : P;
+            if (FIRST) qc[k] = tile_lds[in[k] ? Pl + dy * AT_LW + (k - 2) : Pl];
+            else qc[k] = cin[Q];
+            qn[k] = gA[Q]; qp[k] = gB[Q];
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            if (!in[k]) continue;
+            const float4 q = qc[k];
+            const float w = exp_neg(fabsf(LP - luminance(q.x, q.y, q.z)) / den) *
+                            exp_neg(dist2(nP.x, nP.y, nP.z, qn[k].x, qn[k].y, qn[k].z) / sn2) *
+                            exp_neg(dist2(pP.x, pP.y, pP.z, qp[k].x, qp[k].y, qp[k].z) / sp2);
+            const float wt = w * (h[dy + 2] * h[k]);
+            sr = sr + q.x * wt; sg = sg + q.y * wt; sb = sb + q.z * wt;
+            sv = sv + q.w * (wt * wt);
+            cum = cum + wt;
+        }
+    }
+    const float outr = sr / cum, outg = sg / cum, outb = sb / cum;      // cum >= 9/64: the centre tap has w = 1
+    if (FIRST) var0[P] = cP.w;
+    if (out3) {
+        out3[3 * P + 0] = outr; out3[3 * P + 1] = outg; out3[3 * P + 2] = outb;
+        if (rgba) reinterpret_cast<uchar4 *>(rgba)[P] = tonemap_pixel(outr, outg, outb, 1);
+    } else {
+        cout[P] = make_float4(outr, outg, outb, sv / (cum * cum));
+    }
+}
+
+// levels = 0: the result is the mean itself, and var_0 beside it
+__global__ __launch_bounds__(BLOCK) void k_variance_mean(const float *__restrict__ sum, const float *__restrict__ m1,
+                                                         const float *__restrict__ m2, float *__restrict__ out3,
+                                                         float *__restrict__ var0, uint8_t *__restrict__ rgba, uint32_t npix,
+                                                         float div, float vdiv) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= npix) return;
+    const float r = sum[3 * (size_t)i + 0] / div, g = sum[3 * (size_t)i + 1] / div, b = sum[3 * (size_t)i + 2] / div;
+    out3[3 * (size_t)i + 0] = r; out3[3 * (size_t)i + 1] = g; out3[3 * (size_t)i + 2] = b;
+    var0[i] = var_of_mean(m1[i], m2[i], div, vdiv);
+    if (rgba) reinterpret_cast<uchar4 *>(rgba)[i] = tonemap_pixel(r, g, b, 1);
+}
+
 // ---- history across camera moves (pt_denoise_temporal) -------------------------------------------
 // Reprojection: for pixel P of the NEW camera's grid (its G-buffer gA / gB), the pixel Q of the OLD camera `A` that saw the
 // same surface point -- the inverse of generateRayFromCamera, nearest pixel -- and, when Q's first hit is that point (same

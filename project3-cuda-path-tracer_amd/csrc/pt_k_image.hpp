@@ -60,10 +60,18 @@ __global__ __launch_bounds__(BLOCK) void k_shade_fake(Pool p, Isect is, const fl
 
 // finalGather (pathtrace.cu:269-278): image[pixelIndex] += colour, one add per
 // pixel per iteration, samples added in iteration order
+// MOM (a PT_MOMENTS session): the same loop also adds every sample's luminance and its square to the
+// pixel's two moment planes, M1 += l, M2 += l * l with l = (0.2126f r + 0.7152f g) + 0.0722f b of the SAMPLE (0 for an entry
+// that does not count) -- two more read-modify-writes per pixel, in the same iteration order.  Whole-frame sessions only
+// (pt_init refuses the flag with tiles): the planes are indexed like the image.  Without MOM `mom` is not touched.
+struct Moments { float *m1, *m2; };
+__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+template <bool MOM>
 __global__ __launch_bounds__(BLOCK) void k_gather(float *image, const float *fin, uint32_t cap, TileMap map,
                                                   int count, Control *ctl, Persist *per, int depths,
                                                   uint32_t fake_rays, int partial_counts, int counters_only, uint32_t stamp,
-                                                  const uint32_t *iter_counts, uint32_t iter_grid, HostStats *host_stats) {
+                                                  const uint32_t *iter_counts, uint32_t iter_grid, HostStats *host_stats,
+                                                  Moments mom) {
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
     if (partial_counts) {            // the batch ran as ONE launch (k_iteration): its per-workgroup counts are added up here
         __shared__ uint32_t fold_lds[BLOCK / 32];
@@ -80,6 +88,8 @@ __global__ __launch_bounds__(BLOCK) void k_gather(float *image, const float *fin
     if (counters_only || j >= (uint32_t)map.tile_pixels) return;
     const int pix = local_to_pixel(map, (int)j);
     float r = image[3 * pix + 0], g = image[3 * pix + 1], b = image[3 * pix + 2];
+    float m1 = 0.0f, m2 = 0.0f;
+    if constexpr (MOM) { m1 = mom.m1[pix]; m2 = mom.m2[pix]; }
     // samples are added in iteration order (one add per pixel per iteration, as the reference does); the loads of
     // eight samples are issued together, the adds stay in order
     // an entry counts when it carries this batch's stamp; the others are paths that ended with colour 0 (put_final)
@@ -90,14 +100,20 @@ __global__ __launch_bounds__(BLOCK) void k_gather(float *image, const float *fin
 #pragma unroll
         for (int u = 0; u < 8; ++u) c[u] = f4[(size_t)(s + u) * map.tile_pixels];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (__float_as_uint(c[u].w) == stamp) { r += c[u].x; g += c[u].y; b += c[u].z; }
+        for (int u = 0; u < 8; ++u) {
+            const bool counts = __float_as_uint(c[u].w) == stamp;
+            if (counts) { r += c[u].x; g += c[u].y; b += c[u].z; }
+            if constexpr (MOM) { const float l = counts ? luminance(c[u].x, c[u].y, c[u].z) : 0.0f; m1 = m1 + l; m2 = m2 + l * l; }
+        }
     }
     for (; s < count; ++s) {
         const float4 c = f4[(size_t)s * map.tile_pixels];
-        if (__float_as_uint(c.w) == stamp) { r += c.x; g += c.y; b += c.z; }
+        const bool counts = __float_as_uint(c.w) == stamp;
+        if (counts) { r += c.x; g += c.y; b += c.z; }
+        if constexpr (MOM) { const float l = counts ? luminance(c.x, c.y, c.z) : 0.0f; m1 = m1 + l; m2 = m2 + l * l; }
     }
     image[3 * pix + 0] = r; image[3 * pix + 1] = g; image[3 * pix + 2] = b;
+    if constexpr (MOM) { mom.m1[pix] = m1; mom.m2[pix] = m2; }
 }
 
 // PT_ASYNC_IMAGE: the snapshot of the running sum -> the caller's page-locked image (device-mapped), 16 B per lane,

@@ -719,6 +719,8 @@ int pt_init(const pt_scene_desc *d) {
     }
     const char *x = getenv("PTMI355_XCHG");
     if (devs.size() > 1 || (devs.size() == 1 && x && !strcmp(x, "rccl"))) {
+        if (d->flags & PT_MOMENTS)          // (its contexts hold a tile each, and the filters refuse such a session anyway)
+            return fail(PT_ERR_INVALID, "pt_init: PT_MOMENTS needs a single-device session that holds the frame; this one tiles it over %d devices", (int)devs.size());
         const int rc = multi_init(d, devs);
         if (rc != PT_OK) {
             char keep[ERR_BYTES];
@@ -960,6 +962,24 @@ int pt_history(float *rgb, float *length) {
 int pt_history_reset(void) {
     if (G.live) return fail(PT_ERR_INVALID, "pt_history_reset: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
     return one::pt_history_reset();
+}
+
+// PT_MOMENTS and its filter: pt_init refuses the flag over several devices, so no such session has it
+int pt_get_moments(float *m1, float *m2) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_get_moments: the session was initialised without PT_MOMENTS (it tiles the frame over %d devices)", G.K);
+    return one::pt_get_moments(m1, m2);
+}
+int pt_set_moments(const float *m1, const float *m2) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_set_moments: the session was initialised without PT_MOMENTS (it tiles the frame over %d devices)", G.K);
+    return one::pt_set_moments(m1, m2);
+}
+int pt_denoise_variance(const pt_variance_params *params, int iter, float *host_rgb, uint8_t *host_rgba) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_denoise_variance: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_denoise_variance(params, iter, host_rgb, host_rgba);
+}
+int pt_variance(float *host_var) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_variance: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_variance(host_var);
 }
 
 int pt_tonemap(uint8_t *host_rgba, int iter) {

@@ -190,6 +190,20 @@ extern "C" int ptdbg_temporal_times(const pt_denoise_params *params, const pt_te
     return one::temporal_times(params, temporal, iter, reps, ms);
 }
 
+// diagnostics (not in include/ptmi355.h): launches of k_atrous_var / k_variance_mean since pt_init (single-device sessions)
+extern "C" int ptdbg_variance(unsigned long long out[2]) {
+    if (!g_single.live) return -1;
+    for (int k = 0; k < 2; ++k) out[k] = g_single.vr_launches[k];
+    return 0;
+}
+
+// diagnostics (not in include/ptmi355.h): device times of every level of k_atrous_var, `reps` rounds (pt_h_denoise.hpp:
+// variance_times; profiles/variance/measure.py).  Single-device sessions.
+extern "C" int ptdbg_variance_times(const pt_variance_params *params, int iter, int reps, float *ms) {
+    if (G.live) return fail(PT_ERR_INVALID, "ptdbg_variance_times: single-device sessions");
+    return one::variance_times(params, iter, reps, ms);
+}
+
 #ifdef PT_WAVE_TIMES
 // diagnostic build only (not in include/ptmi355.h): per-wave start / end ticks and hardware ids of k_bounce's last launches
 extern "C" int ptdbg_wave_times(unsigned long long *times /* [8][8192][2] */, uint32_t *hw /* [8][8192] */) {

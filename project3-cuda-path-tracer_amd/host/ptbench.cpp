@@ -7,7 +7,7 @@
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
 //           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]
-//           [--smooth]
+//           [--smooth] [--variance LEVELS,SL,SN,SP]
 //
 // --smooth: PT_SMOOTH_NORMALS -- the `vn` normals of the scene's mesh files (pthost.h: pth_scene_vertex_normals) are uploaded with
 // pt_set_vertex_normals after pathtraceInit; mesh hits are shaded about the interpolated normal (include/ptmi355.h, DESIGN.md
@@ -42,6 +42,11 @@
 // --denoise LEVELS,SC,SN,SP: after the last iteration, the edge-avoiding A-trous filter (pt_denoise: LEVELS levels, sigmas
 // of colour / normal / position) of the accumulated image; BASE.<N>samp.denoised.png is written beside the image through the
 // same saveImage pipeline (clamp, x255, truncate -- on the denoised mean), and one line reports the filter's time.
+//
+// --variance LEVELS,SL,SN,SP: the session is initialised with PT_MOMENTS and, after the last iteration, the filter steered by the
+// pixels' own measured noise (pt_denoise_variance: LEVELS levels, sigmas of luminance -- in standard deviations -- / normal /
+// position) writes BASE.<N>samp.variance.png beside --denoise's picture, the same way; one line reports its time.  Not with
+// --resume: a saved sum does not carry the moments.
 //
 // --move DX,DY,DZ,ITERS (needs --denoise): what an interactive host does when the camera moves.  After the render and its
 // denoised picture: one pt_denoise_temporal on the finished view (it becomes the history), position and lookAt translated by
@@ -91,7 +96,8 @@ int main(int argc, char **argv) {
                "[--bvh] [--aa] [--lens RADIUS FOCAL] [--pfm] [--device D] [--tile R/K] [--strip-rows S] "
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
-               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo] [--smooth]\n", argv[0]);
+               "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo] [--smooth] "
+               "[--variance LEVELS,SL,SN,SP]\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -100,6 +106,8 @@ int main(int argc, char **argv) {
     int warmup = 64;
     bool denoise = false, albedo = false;
     pt_denoise_params dn = {0, 0.0f, 0.0f, 0.0f};
+    bool variance = false;
+    pt_variance_params vr = {0, 0.0f, 0.0f, 0.0f};
     bool move = false;
     float move_by[3] = {0.0f, 0.0f, 0.0f};
     int move_iters = 0;
@@ -159,6 +167,14 @@ int main(int argc, char **argv) {
             }
             dn.levels = lv; denoise = true;
         }
+        else if (a == "--variance" && i + 1 < argc) {
+            int lv = 0;
+            if (sscanf(argv[++i], "%d,%f,%f,%f", &lv, &vr.sigma_luminance, &vr.sigma_normal, &vr.sigma_position) != 4) {
+                fprintf(stderr, "--variance wants LEVELS,SIGMA_LUMINANCE,SIGMA_NORMAL,SIGMA_POSITION\n");
+                return 1;
+            }
+            vr.levels = lv; variance = true; flags |= PT_MOMENTS;
+        }
         else if (a == "--move" && i + 1 < argc) {
             if (sscanf(argv[++i], "%f,%f,%f,%d", &move_by[0], &move_by[1], &move_by[2], &move_iters) != 4 || move_iters < 1) {
                 fprintf(stderr, "--move wants DX,DY,DZ,ITERS with ITERS >= 1\n");
@@ -194,6 +210,7 @@ int main(int argc, char **argv) {
     if (iters < 0) iters = sc->iterations;
     if (sun && sky_n < 1) { fprintf(stderr, "--sun needs --sky (the map it is painted on)\n"); return 1; }
     if (albedo && !denoise) { fprintf(stderr, "--albedo needs --denoise (the filter it switches to irradiance)\n"); return 1; }
+    if (variance && !resume.empty()) { fprintf(stderr, "--variance does not combine with --resume (a saved sum does not carry the moments)\n"); return 1; }
     if (move && !denoise) { fprintf(stderr, "--move needs --denoise (the filter its pictures go through)\n"); return 1; }
     if (per_call) {
         flags |= PT_PIN_IMAGE | PT_HOST_SPARSE | (lookahead ? PT_LOOKAHEAD : 0u);
@@ -364,6 +381,22 @@ int main(int argc, char **argv) {
                dn.levels, dn.sigma_color, dn.sigma_normal, dn.sigma_position, albedo ? ", albedo demodulated" : "", std::chrono::duration<double, std::milli>(d1 - d0).count(),
                std::chrono::duration<double, std::milli>(d2 - d1).count());
         snprintf(name, sizeof name, "%s.%dsamp.denoised.png", out.c_str(), iteration);
+        pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+    }
+    if (variance) {
+        // as above: the first call may compute the G-buffer (it shares --denoise's), the second is the filter alone
+        std::vector<float> mean((size_t)W * H * 3);
+        const auto d0 = std::chrono::steady_clock::now();
+        if (pt_denoise_variance(&vr, iteration, NULL, NULL) != PT_OK) { fprintf(stderr, "pt_denoise_variance: %s\n", pt_last_error()); return 1; }
+        const auto d1 = std::chrono::steady_clock::now();
+        if (pt_denoise_variance(&vr, iteration, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise_variance: %s\n", pt_last_error()); return 1; }
+        const auto d2 = std::chrono::steady_clock::now();
+        printf("variance: %d levels, sigmas %g / %g / %g: %.3f ms the first call, %.3f ms the filter alone (with the copy of the result)\n",
+               vr.levels, vr.sigma_luminance, vr.sigma_normal, vr.sigma_position, std::chrono::duration<double, std::milli>(d1 - d0).count(),
+               std::chrono::duration<double, std::milli>(d2 - d1).count());
+        snprintf(name, sizeof name, "%s.%dsamp.variance.png", out.c_str(), iteration);
         pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
         if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
         printf("Saved %s.\n", name);
