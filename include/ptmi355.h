@@ -744,13 +744,52 @@ int pt_albedo(float *rgb);
  * sigma_position not a finite number > 0 or with a square that is not a normal number; tiled / multi-device sessions); a session
  * without PT_MOMENTS; sigma_luminance not a finite number > 0, or sigma_luminance * 2^-20 not a normal binary32 number;
  * pt_variance before the first pt_denoise_variance call.
- * Out of scope: moments in tiled or multi-device sessions and under PT_LOOKAHEAD windows; temporal accumulation of the moments
- * across camera moves; albedo-demodulated variance; SVGF's spatial variance estimate for iter < 4. */
+ * Out of scope: moments in tiled or multi-device sessions and under PT_LOOKAHEAD windows; albedo-demodulated variance.
+ * (Temporal accumulation of the moments across camera moves and SVGF's spatial variance estimate: pt_denoise_svgf below.) */
 typedef struct pt_variance_params { int32_t levels; float sigma_luminance, sigma_normal, sigma_position; } pt_variance_params;
 int pt_get_moments(float *m1, float *m2);
 int pt_set_moments(const float *m1, const float *m2);
 int pt_denoise_variance(const pt_variance_params *params, int iter, float *host_rgb, uint8_t *host_rgba);
 int pt_variance(float *host_var);
+
+/* ---- SVGF: the moments reprojected with the colour, and a spatial variance estimate where the history is short -------------------
+ * pt_denoise_temporal carries colour across camera moves but stops at a constant; pt_denoise_variance stops at the measured noise
+ * but its moments start again with every view, and the first sample has no variance at all.  pt_denoise_svgf joins them (Schied et
+ * al. 2017; DESIGN.md section 6.28 has the complete specification; tests/svgf_model.py is its numpy form, equal bit for bit).
+ * Binary32, one rounding per operation in the order written, no FMA, C's fmaxf; lum, exp_neg, d2, the kernel h and the
+ * reprojection tests are those of pt_denoise, pt_denoise_temporal and pt_denoise_variance.
+ * State, its own (not pt_denoise_temporal's): cur = {camera bytes, G-buffer, C[.,3], U1, U2, N} and the history planes Hc, H1, H2,
+ * Hn; after pt_init and after pt_svgf_reset there is no cur and every history plane is 0.  A call with the session's camera K, its
+ * G-buffer g and n = (float)iter:
+ *   1. cur exists with other camera bytes than K: pt_denoise_temporal's reprojection of cur, the same tests in the same order; on
+ *      success Hc[P] = C[Q], H1[P] = U1[Q], H2[P] = U2[Q], Hn[P] = min(N[Q], (float)max_history), otherwise all four are 0.  The same
+ *      camera bytes: the history stays.
+ *   2. N' = n + Hn;  c0 = (sum + Hc * Hn) / N' per channel;  u1 = (M1 + H1 * Hn) / N';  u2 = (M2 + H2 * Hn) / N'.
+ *   3. vt = fmaxf(u2 - u1 * u1, 0) / fmaxf(N' - 1, 1).  Where N'[P] < (float)spatial_below, var_0[P] is the spatial estimate: over the
+ *      taps Q = P + (dx, dy), dy = -3 .. 3 outer, dx = -3 .. 3, those outside the image skipped, w = exp_neg(|dn|^2 / sn^2) *
+ *      exp_neg(|dp|^2 / sp^2) (the levels' squares), s1 += u1[Q] * w, s2 += u2[Q] * w, cum += w from 0; a = s1 / cum, b = s2 / cum;
+ *      var_0[P] = fmaxf(b - a * a, 0) / N'[P].  Elsewhere var_0 = vt.
+ *   4. cur = {K, g, C = c0, U1 = u1, U2 = u2, N = N'}: the history is never filtered.
+ *   5. pt_denoise_variance's levels on (c0, var_0), sigma_luminance not halved; levels = 0 returns c0.  RGBA bytes by pt_denoise's rule.
+ * With spatial_below = 0 and no history the call equals pt_denoise_variance bit for bit at every iter; C and N equal the planes of a
+ * pt_denoise_temporal sequence with the same parameters and calls.  spatial_below = 4 is SVGF's value.
+ * pt_denoise_variance's contract: synchronous, on the session's stream behind everything enqueued; READS the session and changes
+ * nothing in it; ignores the albedo switch; the result stays on the device for pt_denoised_device_image; 100 bytes per pixel (cur
+ * with a copy of its G-buffer, the history, the records level 0 reads, var_0) beside the planes it shares with
+ * pt_denoise_variance are allocated on first use and released by pt_free, which ends the history.  pt_clear_image, pt_set_image,
+ * pt_set_moments and pt_set_camera do not touch the state, and the four filters may be interleaved freely: each returns what it
+ * would have returned without the others, pt_history and pt_variance keep reporting their own calls.
+ * pt_svgf_history: Hc, H1, H2, Hn as the last call used them (host; every pointer optional; W*H*3, W*H, W*H, W*H floats).
+ * pt_svgf_variance: var_0 as the levels of the last call received it (W*H floats, host; NULL copies nothing).  pt_svgf_reset:
+ * forget everything.
+ * PT_ERR_INVALID, in this order: everything pt_denoise_variance refuses (a session without PT_MOMENTS included); everything
+ * pt_denoise_temporal refuses in `temporal`; spatial_below outside [0, 1 << 20]; pt_svgf_history or pt_svgf_variance before the
+ * session's first pt_denoise_svgf call. */
+int pt_denoise_svgf(const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter,
+                    float *host_rgb, uint8_t *host_rgba);
+int pt_svgf_history(float *rgb, float *u1, float *u2, float *length);
+int pt_svgf_variance(float *host_var);
+int pt_svgf_reset(void);
 int pt_get_stats(pt_stats *stats);
 /* rays traced since pt_init, read from the device-side counter (includes
  * asynchronous batches); synchronises the stream.  Negative = pt_status. */

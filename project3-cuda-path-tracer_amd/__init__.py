@@ -20,6 +20,7 @@ from .binding import (  # noqa: F401
     set_bump_map, get_bump_map, studs_bumpmap, bump_normal, probe_bump_normal, probe_shade_scatter_bumped,
     PT_SMOOTH_NORMALS, set_vertex_normals, get_vertex_normals, smooth_normal, probe_smooth_normal,
     PT_MOMENTS, VarianceParams, get_moments, set_moments, denoise_variance, variance,
+    denoise_svgf, svgf_history, svgf_variance, svgf_reset,
 )
 from .build import build  # noqa: F401
 from . import sharding  # noqa: F401,E402

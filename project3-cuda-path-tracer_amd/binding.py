@@ -223,6 +223,9 @@ def library():
             L.pt_set_moments.argtypes = [C.c_void_p, C.c_void_p]
             L.pt_denoise_variance.argtypes = [C.POINTER(VarianceParams), C.c_int, C.c_void_p, C.c_void_p]
             L.pt_variance.argtypes = [C.c_void_p]
+            L.pt_denoise_svgf.argtypes = [C.POINTER(VarianceParams), C.POINTER(TemporalParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            L.pt_svgf_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pt_svgf_variance.argtypes = [C.c_void_p]
         except AttributeError:
             if not os.environ.get("PTMI355_LIB"):        # only an older A/B build (profiles/tools/ab.sh) may lack them
                 raise
@@ -885,6 +888,49 @@ def variance():
     out = np.zeros(w * h, dtype=np.float32)
     _chk(library().pt_variance(_p(out)))
     return out
+
+
+def denoise_svgf(iteration, params=None, temporal=None, spatial_below=4, rgba=False):
+    """denoise_variance() with the colour AND the moments of earlier cameras blended in, and a 7 x 7 spatial variance estimate for
+    pixels with fewer than `spatial_below` samples (include/ptmi355.h: pt_denoise_svgf; a PT_MOMENTS session).  `params`: a
+    VarianceParams (default 5, 4.0, 0.35, 0.5), `temporal`: a TemporalParams (default 64, 0.1, 0.1).  The denoised MEAN as
+    [npix, 3] float32; with rgba=True also its RGBA8 form."""
+    if _scene is None:
+        _chk(library().pt_denoise_svgf(None, None, int(spatial_below), int(iteration), None, None))   # raises "not initialised"
+    w, h = _scene.resolution
+    prm = params if params is not None else VarianceParams(5, 4.0, 0.35, 0.5)
+    tmp = temporal if temporal is not None else TemporalParams(64, 0.1, 0.1)
+    img = np.zeros((w * h, 3), dtype=np.float32)
+    px = np.zeros((w * h, 4), dtype=np.uint8) if rgba else None
+    _chk(library().pt_denoise_svgf(C.byref(prm), C.byref(tmp), int(spatial_below), int(iteration), _p(img), _p(px)))
+    return (img, px) if rgba else img
+
+
+def svgf_history():
+    """The history as the last denoise_svgf() used it, in the grid of that call's camera (include/ptmi355.h: pt_svgf_history):
+    ([npix, 3] colours, [npix] u1, [npix] u2, [npix] sample counts; float32, 0 = no history for the pixel)."""
+    if _scene is None:
+        _chk(library().pt_svgf_history(None, None, None, None))             # raises "not initialised"
+    w, h = _scene.resolution
+    rgb = np.zeros((w * h, 3), dtype=np.float32)
+    u1, u2, length = (np.zeros(w * h, dtype=np.float32) for _ in range(3))
+    _chk(library().pt_svgf_history(_p(rgb), _p(u1), _p(u2), _p(length)))
+    return rgb, u1, u2, length
+
+
+def svgf_variance():
+    """var_0 as the levels of the last denoise_svgf() call received it (include/ptmi355.h: pt_svgf_variance): [npix] float32."""
+    if _scene is None:
+        _chk(library().pt_svgf_variance(None))                              # raises "not initialised"
+    w, h = _scene.resolution
+    out = np.zeros(w * h, dtype=np.float32)
+    _chk(library().pt_svgf_variance(_p(out)))
+    return out
+
+
+def svgf_reset():
+    """Forget denoise_svgf()'s history: the next call starts as the session's first."""
+    _chk(library().pt_svgf_reset())
 
 
 def denoised_device_ptr():

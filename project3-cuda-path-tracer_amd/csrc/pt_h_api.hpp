@@ -82,6 +82,9 @@ void pt_free(void) {
     for (int k = 0; k < 2; ++k) if (R.vr_plane[k]) (void)hipFree(R.vr_plane[k]);
     if (R.vr_var0) (void)hipFree(R.vr_var0);
     if (R.vr_out) (void)hipFree(R.vr_out);
+    if (R.sv_gb) (void)hipFree(R.sv_gb);
+    if (R.sv_rec) (void)hipFree(R.sv_rec);
+    for (float *p : {R.sv_c, R.sv_u1, R.sv_u2, R.sv_n, R.sv_hc, R.sv_h1, R.sv_h2, R.sv_hn, R.sv_var0}) if (p) (void)hipFree(p);
     if (R.dbg_counts) (void)hipFree(R.dbg_counts);
     if (R.copy_stream) (void)hipStreamSynchronize(R.copy_stream);
     for (auto &h : R.host_regs) (void)hipHostUnregister(h.ptr);

@@ -354,8 +354,8 @@ static int ensure_variance(bool rgba) {
 }
 
 // level l of `levels`: step 2^l, from the sum and the moments (l = 0) or the plane the level before wrote, into plane l & 1 --
-// the last one into vr_out (and `rgba`)
-static int launch_atrous_var(int l, int levels, float div, float sl, float sn2, float sp2, uint8_t *rgba) {
+// the last one into vr_out (and `rgba`).  `c0` (l = 0 of pt_denoise_svgf): the blended {colour, var_0} records, read as they are.
+static int launch_atrous_var(int l, int levels, float div, float sl, float sn2, float sp2, uint8_t *rgba, const float4 *c0 = nullptr) {
     const float4 *gA = R.gb_mem, *gB = R.gb_mem + R.npix;
     const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
     const bool last = l == levels - 1;
@@ -363,7 +363,10 @@ static int launch_atrous_var(int l, int levels, float div, float sl, float sn2, 
     float *out3 = last ? R.vr_out : (float *)nullptr;
     const float vdiv = fmaxf(div - 1.0f, 1.0f);
     const float *m1 = R.mom_mem, *m2 = R.mom_mem + R.npix;
-    if (l == 0)
+    if (l == 0 && c0)
+        hipLaunchKernelGGL(k_atrous_var<false>, grid, dim3(BLOCK), 0, R.stream, (const float *)nullptr, m1, m2, c0, gA, gB, out,
+                           (float *)nullptr, out3, last ? rgba : (uint8_t *)nullptr, R.map.W, R.map.H, 1, div, vdiv, sl, sn2, sp2);
+    else if (l == 0)
         hipLaunchKernelGGL(k_atrous_var<true>, grid, dim3(BLOCK), 0, R.stream, (const float *)R.image, m1, m2, (const float4 *)nullptr, gA, gB,
                            out, R.vr_var0, out3, last ? rgba : (uint8_t *)nullptr, R.map.W, R.map.H, 1, div, vdiv, sl, sn2, sp2);
     else
@@ -414,6 +417,210 @@ int pt_variance(float *host_var) {
     if (host_var) HIPCHK(hipMemcpyAsync(host_var, R.vr_var0, (size_t)R.npix * sizeof(float), hipMemcpyDeviceToHost, R.stream));
     HIPCHK(hipStreamSynchronize(R.stream));
     return PT_OK;
+}
+
+// ---- reprojected moments and the spatial variance fallback (pt_denoise_svgf) ------------------------
+// pt_denoise_variance's contract, with a history of its own: cur's planes, a copy of cur's G-buffer, the history and the records
+// level 0 reads (100 bytes per pixel) beside the levels' planes it shares with pt_denoise_variance.  ensure_gbuffer's two-allocation
+// swap is not involved: whatever allocation the current camera's G-buffer is in, cur's copy is refreshed from it once per camera
+// change, after the reprojection has read the old one.
+static int ensure_svgf(void) {
+    if (R.sv_ready) return PT_OK;
+    const size_t n = (size_t)R.npix;
+    if (!R.sv_gb) HIPCHK(hipMalloc((void **)&R.sv_gb, n * 2 * sizeof(float4)));
+    if (!R.sv_rec) HIPCHK(hipMalloc((void **)&R.sv_rec, n * sizeof(float4)));
+    for (float **p : {&R.sv_c, &R.sv_hc})
+        if (!*p) HIPCHK(hipMalloc((void **)p, n * 3 * sizeof(float)));
+    for (float **p : {&R.sv_u1, &R.sv_u2, &R.sv_n, &R.sv_h1, &R.sv_h2, &R.sv_hn, &R.sv_var0})
+        if (!*p) HIPCHK(hipMalloc((void **)p, n * sizeof(float)));
+    HIPCHK(hipMemsetAsync(R.sv_hc, 0, n * 3 * sizeof(float), R.stream));
+    for (float *p : {R.sv_h1, R.sv_h2, R.sv_hn}) HIPCHK(hipMemsetAsync(p, 0, n * sizeof(float), R.stream));
+    R.sv_cur = false;
+    R.sv_ready = true;
+    return PT_OK;
+}
+
+// cur (camera sv_cam, G-buffer sv_gb, planes sv_c / sv_u1 / sv_u2 / sv_n) reprojected into the grid of R.cam, whose G-buffer is R.gb_mem
+static int launch_reproject_svgf(const pt_temporal_params &tp) {
+    const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
+    hipLaunchKernelGGL(k_reproject_svgf, grid, dim3(BLOCK), 0, R.stream, (const float4 *)R.gb_mem, (const float4 *)(R.gb_mem + R.npix),
+                       (const float4 *)R.sv_gb, (const float4 *)(R.sv_gb + R.npix), (const float *)R.sv_c, (const float *)R.sv_u1,
+                       (const float *)R.sv_u2, (const float *)R.sv_n, R.scene.mats, R.scene.nmats, R.sv_cam, R.sv_hc, R.sv_h1, R.sv_h2,
+                       R.sv_hn, R.map.W, R.map.H, (float)tp.max_history, tp.position_tolerance, tp.normal_tolerance * tp.normal_tolerance);
+    HIPCHK(hipGetLastError());
+    R.sv_launches[0]++;
+    return PT_OK;
+}
+
+static int launch_svgf_blend(float div, uint8_t *rgba) {
+    const uint32_t n = (uint32_t)R.npix;
+    const float *m1 = R.mom_mem, *m2 = R.mom_mem + R.npix;
+    const SvgfBlend a{(const float *)R.image, m1, m2, R.sv_hc, R.sv_h1, R.sv_h2, R.sv_hn, R.sv_c, R.sv_u1, R.sv_u2, R.sv_n, R.sv_var0, R.sv_rec, rgba};
+    // (a caller's accumulation buffer may sit anywhere; the second moment plane starts npix floats behind the first)
+    if ((((uintptr_t)R.image | (uintptr_t)m1 | (uintptr_t)m2) & 15) == 0)
+        hipLaunchKernelGGL(k_svgf_blend<true>, dim3((n / 4 + 3 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, a, n, div);
+    else
+        hipLaunchKernelGGL(k_svgf_blend<false>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, R.stream, a, n, div);
+    HIPCHK(hipGetLastError());
+    R.sv_launches[1]++;
+    return PT_OK;
+}
+
+static int launch_svgf_spatial(int below, float sn2, float sp2) {
+    const dim3 grid((unsigned)((R.map.W + 63) / 64), (unsigned)((R.map.H + WAVES - 1) / WAVES));
+    hipLaunchKernelGGL(k_svgf_spatial, grid, dim3(BLOCK), 0, R.stream, (const float *)R.sv_u1, (const float *)R.sv_u2, (const float *)R.sv_n,
+                       (const float4 *)R.gb_mem, (const float4 *)(R.gb_mem + R.npix), R.sv_rec, R.sv_var0, R.map.W, R.map.H, (float)below, sn2, sp2);
+    HIPCHK(hipGetLastError());
+    R.sv_launches[2]++;
+    return PT_OK;
+}
+
+static int svgf_args_ok(const char *who, const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter,
+                        float &sn2, float &sp2) {
+    int rc = variance_args_ok(who, params, iter, sn2, sp2);
+    if (rc) return rc;
+    rc = temporal_args_ok(who, temporal);
+    if (rc) return rc;
+    if (spatial_below < 0 || spatial_below > (1 << 20))
+        return fail(PT_ERR_INVALID, "%s: spatial_below %d outside [0, %d]", who, spatial_below, 1 << 20);
+    return PT_OK;
+}
+
+int pt_denoise_svgf(const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter, float *host_rgb,
+                    uint8_t *host_rgba) {
+    float sn2, sp2;
+    int rc = svgf_args_ok("pt_denoise_svgf", params, temporal, spatial_below, iter, sn2, sp2);
+    if (rc) return rc;
+    rc = ensure_variance(host_rgba != nullptr);
+    if (rc) return rc;
+    rc = ensure_svgf();
+    if (rc) return rc;
+    const int levels = params->levels;
+    const size_t n = (size_t)R.npix;
+    uint8_t *rgba = host_rgba ? R.dn_rgba : (uint8_t *)nullptr;
+    rc = ensure_gbuffer();
+    if (rc) return rc;
+    const bool changed = R.sv_cur && memcmp(&R.sv_cam, &R.cam, sizeof R.cam) != 0;
+    if (changed) {
+        rc = launch_reproject_svgf(*temporal);
+        if (rc) return rc;
+    }
+    if (changed || !R.sv_cur) {                // cur's G-buffer from now on: this camera's
+        HIPCHK(hipMemcpyAsync(R.sv_gb, R.gb_mem, n * 2 * sizeof(float4), hipMemcpyDeviceToDevice, R.stream));
+        R.sv_launches[3]++;
+    }
+    rc = launch_svgf_blend((float)iter, levels == 0 ? rgba : (uint8_t *)nullptr);
+    if (rc) return rc;
+    R.sv_cur = true; R.sv_cam = R.cam;
+    if (spatial_below > 0) {
+        rc = launch_svgf_spatial(spatial_below, sn2, sp2);
+        if (rc) return rc;
+    }
+    for (int l = 0; l < levels; ++l) {
+        rc = launch_atrous_var(l, levels, (float)iter, params->sigma_luminance, sn2, sp2, rgba, R.sv_rec);
+        if (rc) return rc;
+    }
+    R.dn_result = levels == 0 ? R.sv_c : R.vr_out;
+    if (host_rgb) HIPCHK(hipMemcpyAsync(host_rgb, R.dn_result, n * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (host_rgba) HIPCHK(hipMemcpyAsync(host_rgba, R.dn_rgba, n * 4, hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_svgf_history(float *rgb, float *u1, float *u2, float *length) {
+    int rc = denoise_session_ok("pt_svgf_history");
+    if (rc) return rc;
+    if (!R.sv_ready) return fail(PT_ERR_INVALID, "pt_svgf_history: no pt_denoise_svgf call since pt_init");
+    const size_t n = (size_t)R.npix;
+    if (rgb) HIPCHK(hipMemcpyAsync(rgb, R.sv_hc, n * 3 * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (u1) HIPCHK(hipMemcpyAsync(u1, R.sv_h1, n * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (u2) HIPCHK(hipMemcpyAsync(u2, R.sv_h2, n * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    if (length) HIPCHK(hipMemcpyAsync(length, R.sv_hn, n * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_svgf_variance(float *host_var) {
+    int rc = denoise_session_ok("pt_svgf_variance");
+    if (rc) return rc;
+    if (!R.sv_ready) return fail(PT_ERR_INVALID, "pt_svgf_variance: no pt_denoise_svgf call since pt_init");
+    if (host_var) HIPCHK(hipMemcpyAsync(host_var, R.sv_var0, (size_t)R.npix * sizeof(float), hipMemcpyDeviceToHost, R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    return PT_OK;
+}
+
+int pt_svgf_reset(void) {
+    int rc = denoise_session_ok("pt_svgf_reset");
+    if (rc) return rc;
+    if (!R.sv_ready) return PT_OK;              // nothing to forget
+    const size_t n = (size_t)R.npix;
+    HIPCHK(hipMemsetAsync(R.sv_hc, 0, n * 3 * sizeof(float), R.stream));
+    for (float *p : {R.sv_h1, R.sv_h2, R.sv_hn}) HIPCHK(hipMemsetAsync(p, 0, n * sizeof(float), R.stream));
+    HIPCHK(hipStreamSynchronize(R.stream));
+    R.sv_cur = false;
+    return PT_OK;
+}
+
+// diagnostics (ptdbg_svgf_times, not in include/ptmi355.h): device times of the call's launches, HIP events on the session's stream.
+// Called where a call would reproject (cur at another camera exists): after one warm-up round, `reps` rounds of k_reproject_svgf,
+// k_svgf_blend, k_svgf_spatial with every pixel below the threshold (1 << 20) and with none (0: every workgroup leaves), level 0
+// from the records (k_atrous_var<false>, step 1), level 1 (step 2), and device-to-device copies of the bytes the three new kernels
+// move (112, 88 and 52 per pixel; the spatial pass without its halo).  ms[rep * 9 + k] in that order.  The rounds' blends overwrite
+// the planes cur stands for, so the history ends here: the call finishes with pt_svgf_reset.
+int svgf_times(const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter, int reps, float *ms) {
+    float sn2, sp2;
+    int rc = svgf_args_ok("ptdbg_svgf_times", params, temporal, spatial_below, iter, sn2, sp2);
+    if (rc) return rc;
+    if (reps < 1 || !ms || params->levels < 2) return fail(PT_ERR_INVALID, "ptdbg_svgf_times: reps >= 1, levels >= 2 and a buffer");
+    if (!R.sv_ready || !R.sv_cur || memcmp(&R.sv_cam, &R.cam, sizeof R.cam) == 0)
+        return fail(PT_ERR_INVALID, "ptdbg_svgf_times: needs the record of a pt_denoise_svgf call at another camera");
+    constexpr int items = 9;
+    const size_t n = (size_t)R.npix;
+    rc = ensure_variance(false);
+    if (rc) return rc;
+    rc = ensure_gbuffer();
+    if (rc) return rc;
+    const size_t copy_bytes[3] = {n * 112, n * 88, n * 52};
+    void *src = nullptr, *dst = nullptr;
+    std::vector<hipEvent_t> ev((size_t)2 * items, nullptr);
+    auto cleanup = [&] {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (src) (void)hipFree(src);
+        if (dst) (void)hipFree(dst);
+    };
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc(&src, copy_bytes[0]));
+        HIPCHK(hipMalloc(&dst, copy_bytes[0]));
+        HIPCHK(hipMemsetAsync(src, 0, copy_bytes[0], R.stream));
+        for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+        // the blend overwrites the planes the reprojection reads: a round's reprojection sees the round before's blend, which
+        // changes values, not the work
+        for (int rep = -1; rep < reps; ++rep) {
+            int r = PT_OK;
+            for (int k = 0; k < items && r == PT_OK; ++k) {
+                HIPCHK(hipEventRecord(ev[2 * k], R.stream));
+                switch (k) {
+                case 0: r = launch_reproject_svgf(*temporal); break;
+                case 1: r = launch_svgf_blend((float)iter, nullptr); break;
+                case 2: r = launch_svgf_spatial(1 << 20, sn2, sp2); break;
+                case 3: r = launch_svgf_spatial(0, sn2, sp2); break;
+                case 4: r = launch_atrous_var(0, params->levels, (float)iter, params->sigma_luminance, sn2, sp2, nullptr, R.sv_rec); break;
+                case 5: r = launch_atrous_var(1, params->levels, (float)iter, params->sigma_luminance, sn2, sp2, nullptr); break;
+                default: HIPCHK(hipMemcpyAsync(dst, src, copy_bytes[k - 6], hipMemcpyDeviceToDevice, R.stream)); break;
+                }
+                HIPCHK(hipEventRecord(ev[2 * k + 1], R.stream));
+            }
+            if (r) return r;
+            HIPCHK(hipStreamSynchronize(R.stream));
+            if (rep < 0) continue;
+            for (int k = 0; k < items; ++k) HIPCHK(hipEventElapsedTime(&ms[(size_t)rep * items + k], ev[2 * k], ev[2 * k + 1]));
+        }
+        return PT_OK;
+    };
+    rc = run();
+    cleanup();
+    if (rc) return rc;
+    return one::pt_svgf_reset();
 }
 
 // diagnostics (ptdbg_variance_times, not in include/ptmi355.h): device times of every level of k_atrous_var, HIP events on the

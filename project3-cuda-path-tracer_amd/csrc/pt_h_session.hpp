@@ -285,6 +285,17 @@ struct Renderer {
     float *vr_var0 = nullptr, *vr_out = nullptr;
     bool vr_called = false;
     uint64_t vr_launches[2] = {0, 0};      // k_atrous_var / k_variance_mean launches since pt_init (ptdbg_variance)
+    // pt_denoise_svgf (pt_h_denoise.hpp), allocated by its first call: a state of its own, not the temporal
+    // call's.  `cur` = what the last call saw: its camera, a COPY of its G-buffer (sv_gb: ensure_gbuffer's two allocations belong to
+    // pt_denoise_temporal), the blended colour sv_c, the normalised moments sv_u1 / sv_u2 and the sample count sv_n; sv_hc / sv_h1 /
+    // sv_h2 / sv_hn: the history in the grid of cur's camera, all zero whenever there is no cur; sv_rec: the {c0, var_0} records level
+    // 0 reads; sv_var0: var_0 as the levels received it (pt_svgf_variance).  The levels ping-pong through vr_plane into vr_out.
+    bool sv_ready = false, sv_cur = false;
+    pt_camera sv_cam{};
+    float4 *sv_gb = nullptr, *sv_rec = nullptr;
+    float *sv_c = nullptr, *sv_u1 = nullptr, *sv_u2 = nullptr, *sv_n = nullptr;
+    float *sv_hc = nullptr, *sv_h1 = nullptr, *sv_h2 = nullptr, *sv_hn = nullptr, *sv_var0 = nullptr;
+    uint64_t sv_launches[4] = {0, 0, 0, 0};   // k_reproject_svgf / k_svgf_blend / k_svgf_spatial launches, G-buffer copies (ptdbg_svgf)
     void *scratch = nullptr;      // export / import staging
     size_t scratch_bytes = 0;
     // stepping state

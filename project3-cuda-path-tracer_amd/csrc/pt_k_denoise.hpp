@@ -417,4 +417,188 @@ __global__ __launch_bounds__(BLOCK) void k_temporal_blend(const float *__restric
     if (rgba) reinterpret_cast<uchar4 *>(rgba)[P] = tonemap_pixel(r, g, b, 1);
 }
 
+// ---- reprojected moments and the spatial variance estimate (pt_denoise_svgf) ------------------------
+// k_reproject's tests, in its order, with the wider gather at Q: the two G-buffer records, the colour, the two normalised moments
+// u1 = M1 / N, u2 = M2 / N and the sample count of the old view -- 32 + 12 + 4 + 4 + 4 bytes per lane, issued as one group before
+// any test reads them.  The same layout (one lane per pixel, a wave = 64 consecutive pixels of a row), the same bounds: every Q is
+// inside the old grid by the test on fx / fy, a material index outside the table reads nothing.
+__global__ __launch_bounds__(BLOCK) void k_reproject_svgf(const float4 *__restrict__ gA, const float4 *__restrict__ gB,
+                                                          const float4 *__restrict__ oA, const float4 *__restrict__ oB,
+                                                          const float *__restrict__ oC, const float *__restrict__ oU1,
+                                                          const float *__restrict__ oU2, const float *__restrict__ oN,
+                                                          const float *__restrict__ mats, int nmats, pt_camera A,
+                                                          float *__restrict__ Hc, float *__restrict__ H1, float *__restrict__ H2,
+                                                          float *__restrict__ Hn, int W, int H, float cap, float ptol, float ntol2) {
+    const int x = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63);
+    const int y = (int)blockIdx.y * WAVES + (int)(threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t P = (size_t)y * (size_t)W + (size_t)x;
+    const float4 n = gA[P], p = gB[P];
+    const int mat = __float_as_int(p.w);
+    float hr = 0.0f, hg = 0.0f, hb = 0.0f, h1 = 0.0f, h2 = 0.0f, hn = 0.0f;
+    bool ok = mat >= 0 && mat < nmats;
+    if (ok) ok = mats[(size_t)mat * ptd::MAT_WORDS + 6] == 0.0f && mats[(size_t)mat * ptd::MAT_WORDS + 7] == 0.0f;
+    if (ok) {
+        const float vx = p.x - A.position.x, vy = p.y - A.position.y, vz = p.z - A.position.z;
+        const float z = vx * A.view.x + vy * A.view.y + vz * A.view.z;
+        if (z > 0.0f) {
+            const float xs = (float)W * 0.5f - (vx * A.right.x + vy * A.right.y + vz * A.right.z) / (z * A.pixelLength[0]);
+            const float ys = (float)H * 0.5f - (vx * A.up.x + vy * A.up.y + vz * A.up.z) / (z * A.pixelLength[1]);
+            const float fx = floorf(xs + 0.5f), fy = floorf(ys + 0.5f);
+            if (fx >= 0.0f && fx < (float)W && fy >= 0.0f && fy < (float)H) {          // (false on NaN)
+                const size_t Q = (size_t)((int)fy * W + (int)fx);
+                const float4 qn = oA[Q], qp = oB[Q];
+                const float qr = oC[3 * Q + 0], qg = oC[3 * Q + 1], qb = oC[3 * Q + 2];
+                const float q1 = oU1[Q], q2 = oU2[Q], qlen = oN[Q];
+                const float lim = ptol * n.w;
+                if (__float_as_int(qp.w) == mat && dist2(qp.x, qp.y, qp.z, p.x, p.y, p.z) <= lim * lim &&
+                    dist2(qn.x, qn.y, qn.z, n.x, n.y, n.z) <= ntol2) {
+                    hr = qr; hg = qg; hb = qb;
+                    h1 = q1; h2 = q2;
+                    hn = fminf(qlen, cap);
+                }
+            }
+        }
+    }
+    Hc[3 * P + 0] = hr; Hc[3 * P + 1] = hg; Hc[3 * P + 2] = hb;
+    H1[P] = h1; H2[P] = h2;
+    Hn[P] = hn;
+}
+
+// The blend of colour and moments: N' = div + Hn, c0 = (sum + Hc * Hn) / N' per channel (k_temporal_blend's expression), u1 = (M1 +
+// H1 * Hn) / N', u2 = (M2 + H2 * Hn) / N', vt = fmaxf(u2 - u1 * u1, 0) / fmaxf(N' - 1, 1).  Streaming, 44 bytes in and 44 out per
+// pixel: C / U1 / U2 / N (the next camera's history), the record {c0, vt} k_atrous_var<false> reads as `cin`, and vt once more in
+// the var_0 plane (pt_svgf_variance; k_svgf_spatial replaces it where a pixel's history is short).  VEC: a lane takes four
+// consecutive pixels, the packed-float3 planes as three 16-byte accesses and the scalar planes as one (every plane 16-byte aligned:
+// the library's own allocations are, a caller's accumulation buffer and the second moment plane of a frame whose pixel count is no
+// multiple of 4 may not be); the pixels after the last whole group of four go one per lane.
+// `rgba` (levels = 0, optional): tonemap_pixel of c0 with divisor 1.
+struct SvgfBlend {
+    const float *sum, *m1, *m2, *Hc, *H1, *H2, *Hn;
+    float *C, *U1, *U2, *N, *var0;
+    float4 *rec;
+    uint8_t *rgba;
+};
+__device__ __forceinline__ float svgf_vt(float u1, float u2, float nn) { return fmaxf(u2 - u1 * u1, 0.0f) / fmaxf(nn - 1.0f, 1.0f); }
+template <bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_svgf_blend(SvgfBlend a, uint32_t npix, float div) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t groups = VEC ? npix / 4 : 0;
+    if (VEC && i < groups) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(a.sum) + 3 * (size_t)i;
+        const float4 *h4 = reinterpret_cast<const float4 *>(a.Hc) + 3 * (size_t)i;
+        const float4 s0 = s4[0], s1 = s4[1], s2 = s4[2], h0 = h4[0], h1 = h4[1], h2 = h4[2];
+        const float4 l4 = reinterpret_cast<const float4 *>(a.Hn)[i];
+        const float4 m14 = reinterpret_cast<const float4 *>(a.m1)[i], m24 = reinterpret_cast<const float4 *>(a.m2)[i];
+        const float4 g14 = reinterpret_cast<const float4 *>(a.H1)[i], g24 = reinterpret_cast<const float4 *>(a.H2)[i];
+        const float s[12] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
+        const float hc[12] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w, h2.x, h2.y, h2.z, h2.w};
+        const float l[4] = {l4.x, l4.y, l4.z, l4.w};
+        const float m1[4] = {m14.x, m14.y, m14.z, m14.w}, m2[4] = {m24.x, m24.y, m24.z, m24.w};
+        const float g1[4] = {g14.x, g14.y, g14.z, g14.w}, g2[4] = {g24.x, g24.y, g24.z, g24.w};
+        float c[12], d[4], u1[4], u2[4], vt[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            d[k] = div + l[k];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) c[3 * k + ch] = blend1(s[3 * k + ch], hc[3 * k + ch], l[k], d[k]);
+            u1[k] = blend1(m1[k], g1[k], l[k], d[k]);
+            u2[k] = blend1(m2[k], g2[k], l[k], d[k]);
+            vt[k] = svgf_vt(u1[k], u2[k], d[k]);
+        }
+        float4 *o4 = reinterpret_cast<float4 *>(a.C) + 3 * (size_t)i;
+        o4[0] = make_float4(c[0], c[1], c[2], c[3]); o4[1] = make_float4(c[4], c[5], c[6], c[7]); o4[2] = make_float4(c[8], c[9], c[10], c[11]);
+        reinterpret_cast<float4 *>(a.U1)[i] = make_float4(u1[0], u1[1], u1[2], u1[3]);
+        reinterpret_cast<float4 *>(a.U2)[i] = make_float4(u2[0], u2[1], u2[2], u2[3]);
+        reinterpret_cast<float4 *>(a.N)[i] = make_float4(d[0], d[1], d[2], d[3]);
+        reinterpret_cast<float4 *>(a.var0)[i] = make_float4(vt[0], vt[1], vt[2], vt[3]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.rec[4 * (size_t)i + k] = make_float4(c[3 * k + 0], c[3 * k + 1], c[3 * k + 2], vt[k]);
+        if (a.rgba) {
+            uchar4 *px = reinterpret_cast<uchar4 *>(a.rgba) + 4 * (size_t)i;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) px[k] = tonemap_pixel(c[3 * k + 0], c[3 * k + 1], c[3 * k + 2], 1);
+        }
+        return;
+    }
+    // one pixel per lane: everything (not VEC), or the npix % 4 pixels after the groups (the lanes right behind them)
+    const uint32_t P = VEC ? groups * 4 + (i - groups) : i;
+    if (P >= npix) return;
+    const float l = a.Hn[P], d = div + l;
+    const float r = blend1(a.sum[3 * (size_t)P + 0], a.Hc[3 * (size_t)P + 0], l, d), g = blend1(a.sum[3 * (size_t)P + 1], a.Hc[3 * (size_t)P + 1], l, d),
+                b = blend1(a.sum[3 * (size_t)P + 2], a.Hc[3 * (size_t)P + 2], l, d);
+    const float u1 = blend1(a.m1[P], a.H1[P], l, d), u2 = blend1(a.m2[P], a.H2[P], l, d);
+    const float vt = svgf_vt(u1, u2, d);
+    a.C[3 * (size_t)P + 0] = r; a.C[3 * (size_t)P + 1] = g; a.C[3 * (size_t)P + 2] = b;
+    a.U1[P] = u1; a.U2[P] = u2; a.N[P] = d; a.var0[P] = vt;
+    a.rec[P] = make_float4(r, g, b, vt);
+    if (a.rgba) reinterpret_cast<uchar4 *>(a.rgba)[P] = tonemap_pixel(r, g, b, 1);
+}
+
+// The spatial estimate for pixels whose history is short (N' < below): over the 7 x 7 taps Q around P inside the image, dy outer,
+// w = exp_neg(|dn|^2 / sn2) * exp_neg(|dp|^2 / sp2), s1 += u1[Q] * w, s2 += u2[Q] * w, cum += w; var_0 = fmaxf(s2 / cum - (s1 /
+// cum)^2, 0) / N'[P] (the centre tap has w = 1: cum >= 1).  k_atrous's geometry.  Each wave first says whether any of its lanes is
+// short; a workgroup with no such wave leaves before it loads anything, and in the others a wave without one leaves after the staging
+// and before its first tap (both branches are wave-uniform) -- after a camera move only disoccluded regions, mirrors and glass take
+// the loop.  The workgroup stages its tile plus the halo of 3 in LDS, 70 x 10 entries of two float4, {normal, u1} and {position,
+// u2} (the records' t and material are not needed): 22400 bytes, and a ds_read_b128 of 16 consecutive lanes covers the 64 banks
+// once.  A short pixel's estimate replaces .w of its own record and its entry of the var_0 plane; nothing else is written.
+constexpr int SV_R = 3, SV_LW = 64 + 2 * SV_R, SV_LH = WAVES + 2 * SV_R;
+__global__ __launch_bounds__(BLOCK) void k_svgf_spatial(const float *__restrict__ U1, const float *__restrict__ U2,
+                                                        const float *__restrict__ N, const float4 *__restrict__ gA,
+                                                        const float4 *__restrict__ gB, float4 *__restrict__ rec,
+                                                        float *__restrict__ var0, int W, int H, float below, float sn2, float sp2) {
+    __shared__ float4 nrm_lds[SV_LH * SV_LW], pos_lds[SV_LH * SV_LW];
+    __shared__ int wave_short[WAVES];
+    const int tx = (int)(threadIdx.x & 63), ty = (int)(threadIdx.x >> 6);
+    const int x = (int)blockIdx.x * 64 + tx;
+    const int y = (int)blockIdx.y * WAVES + ty;
+    const bool inside = x < W && y < H;
+    const size_t P = inside ? (size_t)y * (size_t)W + (size_t)x : 0;
+    const float nn = inside ? N[P] : 0.0f;
+    const bool low = inside && nn < below;
+    const bool wave_low = __ballot(low) != 0ull;
+    if (tx == 0) wave_short[ty] = wave_low ? 1 : 0;
+    __syncthreads();
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < WAVES; ++k) any = any || wave_short[k] != 0;
+    if (!any) return;                                          // (the same for the whole workgroup)
+    const int x0 = (int)blockIdx.x * 64 - SV_R, y0 = (int)blockIdx.y * WAVES - SV_R;
+    for (int i = (int)threadIdx.x; i < SV_LH * SV_LW; i += BLOCK) {
+        const int ly = i / SV_LW, lx = i - ly * SV_LW;
+        const int gx = x0 + lx, gy = y0 + ly;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t Q = (size_t)gy * (size_t)W + (size_t)gx;
+            const float4 qn = gA[Q], qp = gB[Q];
+            nrm_lds[i] = make_float4(qn.x, qn.y, qn.z, U1[Q]);
+            pos_lds[i] = make_float4(qp.x, qp.y, qp.z, U2[Q]);
+        }
+    }
+    __syncthreads();
+    if (!wave_low) return;                                     // (the same for the whole wave)
+    if (!low) return;
+    const int Pl = (ty + SV_R) * SV_LW + tx + SV_R;            // this pixel's entry
+    const float4 nP = nrm_lds[Pl], pP = pos_lds[Pl];
+    float s1 = 0.0f, s2 = 0.0f, cum = 0.0f;
+#pragma unroll 1
+    for (int dy = -SV_R; dy <= SV_R; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= H) continue;                       // (the same for the whole wave)
+#pragma unroll
+        for (int dx = -SV_R; dx <= SV_R; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= W) continue;
+            const float4 qn = nrm_lds[Pl + dy * SV_LW + dx], qp = pos_lds[Pl + dy * SV_LW + dx];
+            const float w = exp_neg(dist2(nP.x, nP.y, nP.z, qn.x, qn.y, qn.z) / sn2) * exp_neg(dist2(pP.x, pP.y, pP.z, qp.x, qp.y, qp.z) / sp2);
+            s1 = s1 + qn.w * w; s2 = s2 + qp.w * w;
+            cum = cum + w;
+        }
+    }
+    const float am = s1 / cum, bm = s2 / cum;
+    const float v = fmaxf(bm - am * am, 0.0f) / nn;
+    rec[P].w = v;
+    var0[P] = v;
+}
+
 }  // namespace

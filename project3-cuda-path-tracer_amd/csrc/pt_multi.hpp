@@ -981,6 +981,23 @@ int pt_variance(float *host_var) {
     if (G.live) return fail(PT_ERR_INVALID, "pt_variance: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
     return one::pt_variance(host_var);
 }
+int pt_denoise_svgf(const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter, float *host_rgb,
+                    uint8_t *host_rgba) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_denoise_svgf: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_denoise_svgf(params, temporal, spatial_below, iter, host_rgb, host_rgba);
+}
+int pt_svgf_history(float *rgb, float *u1, float *u2, float *length) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_svgf_history: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
+    return one::pt_svgf_history(rgb, u1, u2, length);
+}
+int pt_svgf_variance(float *host_var) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_svgf_variance: this session tiles the frame over %d devices; the filter needs a single-device session", G.K);
+    return one::pt_svgf_variance(host_var);
+}
+int pt_svgf_reset(void) {
+    if (G.live) return fail(PT_ERR_INVALID, "pt_svgf_reset: this session tiles the frame over %d devices; the history needs a single-device session", G.K);
+    return one::pt_svgf_reset();
+}
 
 int pt_tonemap(uint8_t *host_rgba, int iter) {
     if (!G.live) return one::pt_tonemap(host_rgba, iter);

@@ -204,6 +204,22 @@ extern "C" int ptdbg_variance_times(const pt_variance_params *params, int iter, 
     return one::variance_times(params, iter, reps, ms);
 }
 
+// diagnostics (not in include/ptmi355.h): launches of k_reproject_svgf / k_svgf_blend / k_svgf_spatial and copies of the G-buffer
+// into cur since pt_init (single-device sessions); the levels of a pt_denoise_svgf call count in ptdbg_variance's out[0]
+extern "C" int ptdbg_svgf(unsigned long long out[4]) {
+    if (!g_single.live) return -1;
+    for (int k = 0; k < 4; ++k) out[k] = g_single.sv_launches[k];
+    return 0;
+}
+
+// diagnostics (not in include/ptmi355.h): device times of the SVGF call's launches beside two levels of the filter and copies of the
+// bytes they move (pt_h_denoise.hpp: svgf_times; profiles/variance/measure_svgf.py).  Single-device sessions.
+extern "C" int ptdbg_svgf_times(const pt_variance_params *params, const pt_temporal_params *temporal, int spatial_below, int iter, int reps,
+                                float *ms) {
+    if (G.live) return fail(PT_ERR_INVALID, "ptdbg_svgf_times: single-device sessions");
+    return one::svgf_times(params, temporal, spatial_below, iter, reps, ms);
+}
+
 #ifdef PT_WAVE_TIMES
 // diagnostic build only (not in include/ptmi355.h): per-wave start / end ticks and hardware ids of k_bounce's last launches
 extern "C" int ptdbg_wave_times(unsigned long long *times /* [8][8192][2] */, uint32_t *hw /* [8][8192] */) {

@@ -7,7 +7,14 @@
 //           [--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]]
 //           [--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] [--temporal CAP,TOL_P,TOL_N]
 //           [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo]
-//           [--smooth] [--variance LEVELS,SL,SN,SP]
+//           [--smooth] [--variance LEVELS,SL,SN,SP] [--svgf LEVELS,SL,SN,SP[,SPATIAL_BELOW]]
+//
+// --svgf LEVELS,SL,SN,SP[,SPATIAL_BELOW]: the session is initialised with PT_MOMENTS and, after the last iteration, pt_denoise_svgf
+// (--variance's filter on colour and moments blended with the history, a 7 x 7 spatial variance estimate for pixels with fewer than
+// SPATIAL_BELOW samples, default 4; include/ptmi355.h) writes BASE.<N>samp.svgf.png beside --variance's
+// picture.  With --move it also writes BASE.moved.<ITERS>samp.svgf.png: the moved view filtered with the history of the first view.
+// max_history and the two tolerances are --temporal's (default 64,0.1,0.1), the values --move passes to pt_denoise_temporal.  Not
+// with --resume.
 //
 // --smooth: PT_SMOOTH_NORMALS -- the `vn` normals of the scene's mesh files (pthost.h: pth_scene_vertex_normals) are uploaded with
 // pt_set_vertex_normals after pathtraceInit; mesh hits are shaded about the interpolated normal (include/ptmi355.h, DESIGN.md
@@ -97,7 +104,7 @@ int main(int argc, char **argv) {
                "[--gpus K | --devices D0,D1,...] [--save-sum] [--resume SUMFILE.pfm [--start N]] "
                "[--per-call [--warmup W] [--no-lookahead]] [--denoise LEVELS,SC,SN,SP] [--move DX,DY,DZ,ITERS] "
                "[--temporal CAP,TOL_P,TOL_N] [--sky N,ZR,ZG,ZB,HR,HG,HB,GR,GG,GB] [--sun X,Y,Z,COS,R,G,B] [--glossy] [--direct] [--direct-sky] [--textures] [--albedo] [--smooth] "
-               "[--variance LEVELS,SL,SN,SP]\n", argv[0]);
+               "[--variance LEVELS,SL,SN,SP] [--svgf LEVELS,SL,SN,SP[,SPATIAL_BELOW]] (history: --temporal's values, default 64,0.1,0.1)\n", argv[0]);
         return 1;
     }
     int iters = -1, batch = 0, device = 0, tile_index = 0, tile_count = 1, strip_rows = 8;
@@ -108,6 +115,9 @@ int main(int argc, char **argv) {
     pt_denoise_params dn = {0, 0.0f, 0.0f, 0.0f};
     bool variance = false;
     pt_variance_params vr = {0, 0.0f, 0.0f, 0.0f};
+    bool svgf = false;
+    pt_variance_params sv = {0, 0.0f, 0.0f, 0.0f};
+    int spatial_below = 4;
     bool move = false;
     float move_by[3] = {0.0f, 0.0f, 0.0f};
     int move_iters = 0;
@@ -175,6 +185,15 @@ int main(int argc, char **argv) {
             }
             vr.levels = lv; variance = true; flags |= PT_MOMENTS;
         }
+        else if (a == "--svgf" && i + 1 < argc) {
+            int lv = 0;
+            const int got = sscanf(argv[++i], "%d,%f,%f,%f,%d", &lv, &sv.sigma_luminance, &sv.sigma_normal, &sv.sigma_position, &spatial_below);
+            if (got != 4 && got != 5) {
+                fprintf(stderr, "--svgf wants LEVELS,SIGMA_LUMINANCE,SIGMA_NORMAL,SIGMA_POSITION[,SPATIAL_BELOW]\n");
+                return 1;
+            }
+            sv.levels = lv; svgf = true; flags |= PT_MOMENTS;
+        }
         else if (a == "--move" && i + 1 < argc) {
             if (sscanf(argv[++i], "%f,%f,%f,%d", &move_by[0], &move_by[1], &move_by[2], &move_iters) != 4 || move_iters < 1) {
                 fprintf(stderr, "--move wants DX,DY,DZ,ITERS with ITERS >= 1\n");
@@ -211,6 +230,7 @@ int main(int argc, char **argv) {
     if (sun && sky_n < 1) { fprintf(stderr, "--sun needs --sky (the map it is painted on)\n"); return 1; }
     if (albedo && !denoise) { fprintf(stderr, "--albedo needs --denoise (the filter it switches to irradiance)\n"); return 1; }
     if (variance && !resume.empty()) { fprintf(stderr, "--variance does not combine with --resume (a saved sum does not carry the moments)\n"); return 1; }
+    if (svgf && !resume.empty()) { fprintf(stderr, "--svgf does not combine with --resume (a saved sum does not carry the moments)\n"); return 1; }
     if (move && !denoise) { fprintf(stderr, "--move needs --denoise (the filter its pictures go through)\n"); return 1; }
     if (per_call) {
         flags |= PT_PIN_IMAGE | PT_HOST_SPARSE | (lookahead ? PT_LOOKAHEAD : 0u);
@@ -401,6 +421,20 @@ int main(int argc, char **argv) {
         if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
         printf("Saved %s.\n", name);
     }
+    if (svgf) {
+        // the session's first call: no history yet, every pixel below SPATIAL_BELOW samples takes the spatial estimate
+        std::vector<float> mean((size_t)W * H * 3);
+        const auto d0 = std::chrono::steady_clock::now();
+        if (pt_denoise_svgf(&sv, &tp, spatial_below, iteration, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise_svgf: %s\n", pt_last_error()); return 1; }
+        const auto d1 = std::chrono::steady_clock::now();
+        printf("svgf: %d levels, sigmas %g / %g / %g, spatial below %d, max_history %d, tolerances %g / %g: %.3f ms (with the copy of the result)\n",
+               sv.levels, sv.sigma_luminance, sv.sigma_normal, sv.sigma_position, spatial_below, tp.max_history, tp.position_tolerance,
+               tp.normal_tolerance, std::chrono::duration<double, std::milli>(d1 - d0).count());
+        snprintf(name, sizeof name, "%s.%dsamp.svgf.png", out.c_str(), iteration);
+        pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+        if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+        printf("Saved %s.\n", name);
+    }
     if (pfm) {
         snprintf(name, sizeof name, "%s.%dsamp.pfm", out.c_str(), iteration);
         pth_write_pfm(name, image.data(), W, H, (float)iteration);
@@ -448,6 +482,17 @@ int main(int argc, char **argv) {
         pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
         if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
         printf("Saved %s.\n", name);
+        if (svgf) {                                        // the first view's call above is the history
+            const auto s0 = std::chrono::steady_clock::now();
+            if (pt_denoise_svgf(&sv, &tp, spatial_below, move_iters, mean.data(), NULL) != PT_OK) { fprintf(stderr, "pt_denoise_svgf: %s\n", pt_last_error()); return 1; }
+            const auto s1 = std::chrono::steady_clock::now();
+            snprintf(name, sizeof name, "%s.moved.%dsamp.svgf.png", out.c_str(), move_iters);
+            pth_image_to_rgb8(mean.data(), W, H, 1.0f, rgb.data());
+            if (pth_write_png(name, rgb.data(), W, H) != 0) { fprintf(stderr, "%s\n", pth_last_error()); return 1; }
+            printf("Saved %s.\n", name);
+            printf("svgf, moved view: %.3f ms pt_denoise_svgf with the reprojection (with the copy of the result)\n",
+                   std::chrono::duration<double, std::milli>(s1 - s0).count());
+        }
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double, std::milli>(b - a).count();
         };
