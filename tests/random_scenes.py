@@ -5,7 +5,9 @@ scale (no finite inverse: the primitive is never hit), enclosing shells, an eye 
 
 `scene(pt, seed, w, h)` draws from default_rng(seed) in the order the fuzz tool always drew: seed N is the scene it always was.
 Everything newer -- the GGX exponents, textures, bump maps, the sky -- comes from a second stream, default_rng([seed, 1]), in
-`features()`, so the first stream never moves."""
+`features()`, so the first stream never moves.  Further streams follow the same rule: default_rng([seed, 2]) is the mesh session's
+soup (`mesh_of`), [seed, 3] the camera's jitter and lens (`camera_features`), [seed, 4] the soup's vertex normals (`normals_of`),
+[seed, 5] the sky that is sampled as a light and whether the lamps are off (`sky_of`)."""
 import os
 
 import numpy as np
@@ -168,6 +170,26 @@ STATE_FRAME = (64, 16)
 STATE_DIRECT_SEEDS = (1009, 1110, 1136, 1087, 1089, 1127, 1153, 1100)
 STATE_DIRECT_MIN_DEPTH = 3                                           # below it bounce 1 is one of the session's DIRECT bounces
 STATE_KINDS = ("drawn", "fixed", "coloured", "zero")                 # FS_DIFFUSE, FS_FIXED, FS_CONST, FS_ZERO
+# The smooth sessions (PT_SMOOTH_NORMALS): the soup of mesh_of with normals_of's vertex normals.  Smoothed
+# matte hits: 1029 (the soup fills much of the frame; depth 11, 21 primitives) and 1191 (25 primitives); smoothed mirror hits:
+# 1002, 1008 and 1022 (depth 2, 31 primitives); smoothed glass hits: 1003 and 1024.  1000 has depth 1: its only bounce is the
+# last one, which reads no normal -- steps 4 and 5 still refuse records there, and removing the normals changes nothing.
+SMOOTH_SEEDS = (1029, 1002, 1003, 1022, 1191, 1008, 1024, 1000)
+# The sampled-sky sessions (PT_DIRECT_SKY).  In the generator's scenes a sample aimed at the sky rarely
+# leaves: the primitives of scale 30 and 100 enclose the rest (1029: some 800 aimed final rays, every one occluded).  So the
+# seeds of SKY_OPENED run on opened(): the same draw without the primitives whose largest scale component is 30 or more.
+# Closed: 1165 (depth 1, 26 primitives, lamps and a 4-texel sky), 1079 (depth 1, lamps off, a 1-texel map), 1392 (two
+# primitives), 1029, 1231 (depth 5, lamps off), 1377 (depth 2, lamps off, 1 texel), 1086 (depth 7, 1 texel).  Opened: 1000, 1018,
+# 1306 (depth 1, 16 texels; 1000 lamps off), 1060 (38 primitives, depth 2, lamps off, 1 texel), 1291 (1 texel), 1284, 1358
+# (depth 4, lamps off), 1283 (depth 6), 1327 (depth 1, lamps off).  A seed's second map is sky_of(seed + 1)'s.
+SKY_SEEDS = (1165, 1079, 1392, 1029, 1000, 1018, 1060, 1291, 1231, 1358, 1283, 1377, 1306, 1284, 1086, 1327)
+SKY_OPENED = (1000, 1018, 1060, 1291, 1358, 1283, 1306, 1284, 1327)
+# The sessions under camera_features(): a lens and no jitter on 1067 (0.35 focused at 0.5; 16 primitives, no refractive material:
+# its pinhole stretch reads the first-state table), 1024 (the same lens; glass: the first-hit table alone), 1068 (2.0 at 1000; 25
+# primitives, no refractive material) and 1000 (0.05 at 0.5; depth 1, 28 primitives: bounce 0 of its direct sessions is a DIRECT
+# bounce that generates its rays); jitter and no lens on 1053 (no refractive material) and 1120 (17 primitives, depth 7); both on
+# 1073 (2.0 at 0.5; depth 2, no refractive material) and 1030 (0.35 at 0.5; depth 9, 25 primitives, no refractive material).
+CAMERA_SEEDS = (1067, 1024, 1053, 1073, 1068, 1000, 1120, 1030)
 
 
 def groups(seeds):
@@ -227,51 +249,112 @@ def mesh_of(pt, seed, geoms, n_materials):
     return pt.meshes.add_mesh(geoms, tris, material_id=int(rng.integers(n_materials)))
 
 
-def plain_run(po, pt, seed, w, h, oflags, cam=None, mesh=False, last=9):
-    """po.Tracer over iterations 1 .. last; cam: another camera than the seed's own."""
+RADII, FOCALS = (0.0, 0.05, 0.35, 2.0), (0.5, 9.0, 1e3)
+
+
+def camera_features(seed):
+    """The fourth stream, default_rng([seed, 3]): (aa, (lens radius, focal distance)) -- PT_AA_JITTER or not, a thin lens from a
+    pinprick to one two units wide focused in front of the scene, inside it or far behind it.  A radius of 0 is no lens."""
+    rng = np.random.default_rng([seed, 3])
+    aa = bool(rng.random() < 0.5)
+    radius, focal = float(rng.choice(RADII)), float(rng.choice(FOCALS))
+    return aa, (radius, focal)
+
+
+def lens_only(seed):
+    aa, lens = camera_features(seed)
+    return lens[0] > 0 and not aa
+
+
+class CameraPlan:
+    """How a run of a session uses the seed's camera features.  camera=False: the pinhole, iterations 1 .. last.  camera=True: `aa`
+    and `lens` for the model, then iteration last + 1 -- the one the GPU module steps: `Run.stepped` keeps its live paths after
+    bounce 0 --; a seed with a lens and no jitter goes on with last + 2 and last + 3 under the pinhole (pt_set_lens(0, 0)) and
+    last + 4 and last + 5 under its lens again: `switch` = {iteration: the lens from the iteration after it on}."""
+
+    def __init__(self, seed, camera, last):
+        self.aa, self.lens, self.last, self.end, self.step, self.switch = False, (0.0, 0.0), last, last, None, {}
+        if camera:
+            self.aa, self.lens = camera_features(seed)
+            self.step = last + 1
+            self.end = last + 1
+            if lens_only(seed):
+                self.end = last + 5
+                self.switch = {last + 1: (0.0, 0.0), last + 3: self.lens}
+
+    def kw(self):
+        return dict(aa=self.aa, lens=self.lens if self.lens[0] > 0 else (0.0, 0.0))
+
+    def its(self):
+        return range(1, self.end + 1)
+
+
+def plain_run(po, pt, seed, w, h, oflags, cam=None, mesh=False, last=9, camera=False):
+    """po.Tracer over iterations 1 .. last; cam: another camera than the seed's own; camera: CameraPlan."""
     def make():
         geoms, mats, c, depth = scene(pt, seed, w, h)
         tris = meshes = None
         if mesh:
             geoms, tris, meshes = mesh_of(pt, seed, geoms, len(mats))
             tris, meshes = tris.view(po.TRI_DT), meshes.view(po.MESH_DT)
+        plan = CameraPlan(seed, camera, last)
         ref = po.Tracer(np.ascontiguousarray(geoms).view(po.GEOM_DT), mats.view(po.MATERIAL_DT), c if cam is None else cam, depth,
-                        flags=oflags, trig=po.TRIG_SHARED, tris=tris, meshes=meshes)
+                        flags=oflags | (po.F_AA if plan.aa else 0), trig=po.TRIG_SHARED, tris=tris, meshes=meshes, lens=plan.kw()["lens"])
         run = Run(w * h)
-        for it in range(1, last + 1):
+        run.plan, run.rays, run.moments = plan, {}, {}
+        acc = np.zeros((w * h, 3), dtype=F32)
+        m1, m2 = np.zeros(w * h, dtype=F32), np.zeros(w * h, dtype=F32)
+        for it in plan.its():
             snaps = []
+            if camera:                                                   # per-sample colours, as tests/test_gpu_variance_random_scenes.py
+                import variance_model                                    # takes them: the sum is the same sum, and PT_MOMENTS' planes
+                ref.image[:] = 0
             st = ref.iterate(it, snapshots=snaps)
+            if camera:
+                acc = (acc + ref.image).astype(F32)
+                m1, m2 = variance_model.accumulate(m1, m2, ref.image)
+                run.moments[it] = (m1, m2)
             alive = [s["paths"]["pixelIndex"][s["paths"]["remainingBounces"] > 0] for s in snaps]
-            run.record(it, ref.image, alive, live=list(st.live[:depth]))
-            run.rays = getattr(run, "rays", {})
+            run.record(it, acc if camera else ref.image, alive, live=list(st.live[:depth]))
             run.rays[it] = int(st.rays)
+            if it == plan.step:
+                p = snaps[0]["paths"]
+                run.stepped = p[p["remainingBounces"] > 0].copy()
+            if it in plan.switch:
+                ref.scene.lensRadius, ref.scene.focalDistance = plan.switch[it]
         return run
-    return _cached(("plain", seed, w, h, oflags, None if cam is None else cam.tobytes(), mesh, last), make)
+    return _cached(("plain", seed, w, h, oflags, None if cam is None else cam.tobytes(), mesh, last, camera), make)
 
 
-def _model_run(m, n, depth, its, after=None, direct=False):
+def _model_run(m, n, depth, its, after=None, direct=False, plan=None):
     run = Run(n)
+    run.plan = plan
     for it in its:
         snaps = []
         m.iterate(it, snaps)
         run.record(it, m.image, [s["pixelIndex"] for s in snaps], live=list(m.live) if direct and m.direct else None)
         run.live[it] = (run.live[it] + [0] * (depth + 1))[:depth + 1 if direct and m.direct else depth]
+        if plan is not None and it == plan.step:
+            run.stepped = snaps[0].copy()
+        if plan is not None and it in plan.switch:
+            m.lens = plan.switch[it]
         if after is not None:
             after(it, m)
     return run
 
 
-def glossy_run(po, pt, seed, w, h):
+def glossy_run(po, pt, seed, w, h, camera=False, last=9):
     """glossy_model.Model with the seed's sky over iterations 1 .. 9: (run, counts, features)."""
     def make():
         import glossy_model as gm
         geoms, mats, cam, depth = scene(pt, seed, w, h)
         f = features(seed, mats, depth)
-        m = gm.Model(po, geoms, f.materials, cam, depth, glossy=True)
+        plan = CameraPlan(seed, camera, last)
+        m = gm.Model(po, geoms, f.materials, cam, depth, glossy=True, **plan.kw())
         m.set_environment(f.sky)
-        run = _model_run(m, w * h, depth, range(1, 10))
+        run = _model_run(m, w * h, depth, plan.its(), plan=plan)
         return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, f
-    return _cached(("glossy", seed, w, h), make)
+    return _cached(("glossy", seed, w, h, camera, last), make)
 
 
 def dropped(f):
@@ -279,7 +362,7 @@ def dropped(f):
     return (min(f.bump_maps) if f.bump_maps else None), (min(f.textures) if f.textures else None)
 
 
-def textured_run(po, pt, seed, w, h, mesh=False):
+def textured_run(po, pt, seed, w, h, mesh=False, camera=False, last=5):
     """bump_model.Model with the seed's textures, bump maps, sky and exponents: iterations 1-3, one bump map and one texture
     removed, iterations 4-5.  (run, counts, features); counts: tinted, bumped, guarded and the lobe's."""
     def make():
@@ -288,7 +371,8 @@ def textured_run(po, pt, seed, w, h, mesh=False):
         tris = meshes = None
         if mesh:
             geoms, tris, meshes = mesh_of(pt, seed, geoms, len(mats))
-        m = bm.Model(po, geoms, f.materials, cam, depth, tris=tris, meshes=meshes, glossy=True)
+        plan = CameraPlan(seed, camera, last)
+        m = bm.Model(po, geoms, f.materials, cam, depth, tris=tris, meshes=meshes, glossy=True, **plan.kw())
         for k, t in f.textures.items():
             m.set_texture(k, t)
         for k, t in f.bump_maps.items():
@@ -302,24 +386,25 @@ def textured_run(po, pt, seed, w, h, mesh=False):
                     m.set_bump_map(b, None)
                 if t is not None:
                     m.set_texture(t, None)
-        run = _model_run(m, w * h, depth, range(1, 6), after)
+        run = _model_run(m, w * h, depth, plan.its(), after, plan=plan)
         counts = {k: v for k, v in m.counts.items() if isinstance(v, int)}
         counts.update(tinted=m.tinted, bumped=m.bumped, guarded=m.guarded)
         return run, counts, f
-    return _cached(("textured", seed, w, h, mesh), make)
+    return _cached(("textured", seed, w, h, mesh, camera, last), make)
 
 
-def direct_run(po, pt, seed, w, h):
+def direct_run(po, pt, seed, w, h, camera=False, last=9):
     """direct_model.Model with the seed's sky and exponents over iterations 1 .. 9: (run, counts, features, light elements)."""
     def make():
         import direct_model as dm
         geoms, mats, cam, depth = scene(pt, seed, w, h)
         f = features(seed, mats, depth)
-        m = dm.Model(po, geoms, f.materials, cam, f.direct_depth, glossy=True)
+        plan = CameraPlan(seed, camera, last)
+        m = dm.Model(po, geoms, f.materials, cam, f.direct_depth, glossy=True, **plan.kw())
         m.set_environment(f.sky)
-        run = _model_run(m, w * h, f.direct_depth, range(1, 10), direct=True)
+        run = _model_run(m, w * h, f.direct_depth, plan.its(), direct=True, plan=plan)
         return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, f, len(m.table)
-    return _cached(("direct", seed, w, h), make)
+    return _cached(("direct", seed, w, h, camera, last), make)
 
 
 def plain_direct_run(po, pt, seed, w, h):
@@ -333,6 +418,147 @@ def plain_direct_run(po, pt, seed, w, h):
         run = _model_run(m, w * h, depth, range(1, 10), direct=True)
         return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, len(m.table)
     return _cached(("plain direct", seed, w, h), make)
+
+
+def normals_of(pt, seed, tris):
+    """Vertex normals for the mesh session's soup from default_rng([seed, 4]), [T, 3, 3] float32: the facet normal (0 where a
+    zero-area triangle or a sliver has none that is finite) plus a lean of N(0, 0.5) per corner and component, then
+    smooth_cases.scene_arrays("hostile")'s treatment: every 7th triangle faces away (step 4 refuses it), every 11th is zero, one
+    NaN component, one infinite corner, one triangle of length 1e-20 and one of 1e20, one with a single zero corner."""
+    import smooth_model
+    rng = np.random.default_rng([seed, 4])
+    fn = smooth_model.facet_normals(tris)
+    fn = np.where(np.isfinite(fn).all(axis=1)[:, None], fn, F32(0)).astype(F32)
+    vn = (fn[:, None, :] + rng.normal(0.0, 0.5, (len(tris), 3, 3))).astype(F32)
+    vn[0::7] *= F32(-1)
+    vn[3::11] = 0
+    vn[2, 1, 0] = np.nan
+    vn[4, 2] = np.inf
+    vn[6] *= F32(1e-20)
+    vn[8] *= F32(1e20)
+    vn[10, 2] = 0
+    return vn
+
+
+def sky_of(pt, seed):
+    """The sampled sky of a seed from default_rng([seed, 5]): (texels, lamps_off).  A gradient of 1, 4 or 16 texels a side
+    (sky_model.gradient) with a sun of the stream's direction, width and colour, or -- one draw in four, where the seed has
+    one -- the seed's features().sky.  lamps_off: the session runs on materials whose emittance is 0, the sky its only light."""
+    import sky_model
+    rng = np.random.default_rng([seed, 5])
+    n = int(rng.choice([1, 4, 16]))
+    own = bool(rng.random() < 0.25)
+    lamps_off = bool(rng.random() < 0.3)
+    direction = rng.normal(size=3)
+    direction[1] = abs(direction[1]) + 0.2                              # above the horizon
+    cos_half = float(rng.choice([0.97, 0.8]))
+    rgb = rng.uniform(10.0, 60.0, 3)
+    _, mats, _, depth = scene(pt, seed, W, H)
+    f = features(seed, mats, depth)
+    if own and f.sky is not None:
+        return f.sky, lamps_off
+    return pt.sun_on_cubemap(sky_model.gradient(pt, n), direction, cos_half, rgb), lamps_off
+
+
+def opened(geoms):
+    """The scene without its enclosing primitives -- those whose largest scale component is 30 or more --, the first primitive
+    kept where every one is such: no new draw."""
+    keep = np.asarray(geoms["scale"]).max(axis=1) < 30
+    if not keep.any():
+        keep[0] = True
+    return np.ascontiguousarray(geoms[keep])
+
+
+class SkySession:
+    """What the sampled-sky session of a seed runs on: geoms (opened for the seeds of SKY_OPENED), materials (exponents drawn,
+    emittance 0 where lamps_off), cam, depth, texels, lamps_off, other (the next seed's map, set for iterations 6-7)."""
+
+
+def sky_session(pt, seed, w, h):
+    s = SkySession()
+    geoms, mats, s.cam, depth = scene(pt, seed, w, h)
+    f = features(seed, mats, depth)
+    s.geoms = opened(geoms) if seed in SKY_OPENED else geoms
+    s.depth = f.direct_depth
+    s.texels, s.lamps_off = sky_of(pt, seed)
+    s.materials = f.materials.copy()
+    if s.lamps_off:
+        s.materials["emittance"] = 0
+    s.other = sky_of(pt, seed + 1)[0]
+    return s
+
+
+def sky_run(po, pt, seed, w, h, camera=False, last=7):
+    """sky_model.Model with PT_GLOSSY on sky_session(): iterations 1-3 under the seed's map, 4-5 without a map (direct_model's
+    session; the plain one where the lamps are off), 6-7 under the next seed's map.  (run, counts, session, light elements with
+    the sky's)."""
+    def make():
+        import sky_model
+        s = sky_session(pt, seed, w, h)
+        plan = CameraPlan(seed, camera, last)
+        m = sky_model.Model(po, s.geoms, s.materials, s.cam, s.depth, glossy=True, **plan.kw())
+        m.set_environment(s.texels)
+        elements = len(m.table)
+
+        def after(it, m):
+            if it == 3:
+                m.set_environment(None)
+            if it == 5:
+                m.set_environment(s.other)
+        run = _model_run(m, w * h, s.depth, plan.its(), after, direct=True, plan=plan)
+        return run, {k: v for k, v in m.counts.items() if isinstance(v, int)}, s, elements
+    return _cached(("sky", seed, w, h, camera, last), make)
+
+
+class SmoothSession:
+    """What the smooth session of a seed runs on: geoms (with the soup's primitive), materials (exponents drawn), cam, depth, tris,
+    meshes, normals (normals_of), sky (features().sky)."""
+
+
+def smooth_session(pt, seed, w, h):
+    s = SmoothSession()
+    geoms, mats, s.cam, s.depth = scene(pt, seed, w, h)
+    f = features(seed, mats, s.depth)
+    s.geoms, s.tris, s.meshes = mesh_of(pt, seed, geoms, len(mats))
+    s.materials, s.sky = f.materials, f.sky
+    s.normals = normals_of(pt, seed, s.tris)
+    return s
+
+
+def smooth_run(po, pt, seed, w, h, camera=False, last=7, keep=False):
+    """smooth_model.Model with PT_GLOSSY on smooth_session(): iterations 1-3 with the normals, 4-5 without them (keep: with them),
+    6-7 with them again.  (run, stats, session); stats: smooth_model.Model.stats."""
+    def make():
+        import smooth_model
+        s = smooth_session(pt, seed, w, h)
+        plan = CameraPlan(seed, camera, last)
+        m = smooth_model.Model(po, s.geoms, s.materials, s.cam, s.depth, tris=s.tris, meshes=s.meshes, glossy=True, **plan.kw())
+        m.set_vertex_normals(s.normals)
+        m.set_environment(s.sky)
+
+        def after(it, m):
+            if it == 3 and not keep:
+                m.set_vertex_normals(None)
+            if it == 5:
+                m.set_vertex_normals(s.normals)
+        run = _model_run(m, w * h, s.depth, plan.its(), after, plan=plan)
+        return run, dict(m.stats), s
+    return _cached(("smooth", seed, w, h, camera, last, keep), make)
+
+
+# the sessions that run under camera_features(); "moments" is the plain compacting one with PT_MOMENTS, the two smooth ones share a model
+CAMERA_KINDS = ("plain compact", "plain non-compacting", "plain sorted", "moments", "sky + glossy", "textures + bumps",
+                "direct + sky + glossy", "sampled sky", "smooth loop", "smooth hierarchy")
+
+
+def camera_run(po, pt, kind, seed, w, h, camera=True, last=None):
+    """The model's run of one of CAMERA_KINDS (last: shorter than the session's own sequence)."""
+    kw = dict(camera=camera) if last is None else dict(camera=camera, last=last)
+    if kind.startswith("plain") or kind == "moments":
+        oflags = {"plain non-compacting": 0, "plain sorted": po.F_COMPACT | po.F_SORT}.get(kind, po.F_COMPACT)
+        return plain_run(po, pt, seed, w, h, oflags, **kw)
+    models = {"sky + glossy": glossy_run, "textures + bumps": textured_run, "direct + sky + glossy": direct_run, "sampled sky": sky_run}
+    return models.get(kind, smooth_run)(po, pt, seed, w, h, **kw)[0]
 
 
 def light_table_size(po, pt, seed, w, h):

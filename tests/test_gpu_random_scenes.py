@@ -11,6 +11,12 @@ live and ray counters wherever the model counts them.  A test item is one group 
 The first-state table (k_bounce<MODE_STATE2>) has a list of its own, rs.STATE_SEEDS: scenes without a
 refractive material, which also run at 64 x 16 -- whole 64-pixel tiles, so the ended-tile words are read -- and every such session
 asks ptdbg_first_state whether each launch of bounces 0 and 1 was the table form.
+Three more lists run what the lists above never carried: rs.SMOOTH_SEEDS puts vertex normals on the mesh session's soup
+(PT_SMOOTH_NORMALS: normals that lean, face away, vanish, are NaN or infinite, and go and come back in mid-session); rs.SKY_SEEDS
+samples the sky as a light (PT_DIRECT_SKY: maps of 1 to 16 texels, with the lamps and without, a map that leaves and another that
+arrives, so that nlights changes under the session); rs.CAMERA_SEEDS runs every kind of session under PT_AA_JITTER and the thin
+lens -- the GEN forms of every shader, k_raygen through the stepping interface, and pt_set_lens switching between a lens and the
+pinhole while ptdbg_first_two and ptdbg_first_state say whether the tables of repeating camera rays were used --, PT_MOMENTS included.
 tests/test_random_scenes_cpu.py shows from the models alone that the seed lists reach the branches named above.
 
 A failure names the seed, the session, the number of differing pixels, the first of them with both values, and the bounce at which
@@ -69,6 +75,24 @@ class Report:
     def equal(self, seed, what, got, want):
         if got != want:
             self.lines.append("seed %d, %s [%s], %s: got %r, want %r" % (seed, self.session, self.plan, what, got, want))
+
+    def paths(self, seed, w, what, got, want):
+        """The live paths of two pools, each ordered by its pixelIndex: every field, bit for bit."""
+        got, want = (p[p["remainingBounces"] > 0] for p in (got, want))
+        got, want = (p[np.argsort(p["pixelIndex"], kind="stable")] for p in (got, want))
+        if len(got) != len(want) or (got["pixelIndex"] != want["pixelIndex"]).any():
+            self.lines.append("seed %d, %s [%s], %s: %d live paths, want %d; pixels that are live on one side only: %s" %
+                              (seed, self.session, self.plan, what, len(got), len(want),
+                               sorted(set(got["pixelIndex"].tolist()) ^ set(want["pixelIndex"].tolist()))[:8]))
+            return
+        bad = got["remainingBounces"] != want["remainingBounces"]
+        for f in ("origin", "direction", "color"):
+            bad |= (bits(got[f]) != bits(want[f])).any(axis=1)
+        if bad.any():
+            k = int(np.nonzero(bad)[0][0])
+            p = int(got["pixelIndex"][k])
+            self.lines.append("seed %d, %s [%s], %s: %d of %d paths differ; first pixel %d (x %d, y %d): got %r, want %r" %
+                              (seed, self.session, self.plan, what, int(bad.sum()), len(bad), p, p % w, p // w, got[k].tolist(), want[k].tolist()))
 
     def done(self):
         assert not self.lines, "\n".join(self.lines)
@@ -356,6 +380,231 @@ def test_sessions_with_a_mesh(pt, po, launch_plan, session, hierarchy):
         else:
             run, _, f = rs.textured_run(po, pt, seed, W, H, mesh=True)
             textured_session(pt, rep, seed, W, H, run, f, geoms, cam, depth, pt.PT_COMPACT | extra, True, tris, meshes)
+    rep.done()
+
+
+# ---- smooth normals, the sampled sky, jitter and the lens --------------------------------------------------------------------------
+def init_session(pt, scene, flags, run, **kw):
+    """pt_init for a model's run: PT_AA_JITTER where its camera jitters, lens= where it has a lens (rs.CameraPlan)."""
+    plan = run.plan
+    pt.pathtraceInit(scene, flags=flags | (pt.PT_AA_JITTER if plan.aa else 0), max_batch=2, lens=plan.kw()["lens"], **kw)
+
+
+def on_the_lanes(pt, batches):
+    for it0, count in batches:
+        pt.trace_batch_async(it0, count)
+    pt.synchronize()
+
+
+def table_counters(pt):
+    return first_two(pt), first_state(pt)
+
+
+def camera_tail(pt, rep, seed, w, h, run, stepped, tables=None):
+    """What follows a camera session's own sequence (rs.CameraPlan).  Iteration last + 1: through pt_trace_begin / pt_trace_bounce /
+    pt_trace_end where `stepped` -- k_raygen generates the rays there, not a bounce kernel's GEN form -- with pt_export_paths after
+    bounce 0 against the model's live paths; through pt_trace elsewhere.  A session with a lens and no jitter then calls
+    pt_set_lens(0, 0), runs two iterations that the pinhole model continues on the same running sum, sets its lens again and runs two
+    more.  tables = (depth, glass_free, launch plan) in the plain compacting session: with a kernel per bounce and depth >= 2 the
+    pinhole stretch must take bounces 0 and 1 from the first-hit table (and from the first-state table where no material refracts),
+    and no stretch under the lens may."""
+    plan, n = run.plan, w * h
+    it = plan.step
+    if stepped:
+        pt.trace_begin(it, 1)
+        for d in range(len(run.live[it])):
+            pt.trace_bounce(d)
+            if d == 0:
+                rep.paths(seed, w, "pt_export_paths after the stepped bounce 0 of iteration %d" % it, pt.export_paths(n)[0], run.stepped)
+        pt.trace_end()
+        rep.image(seed, w, "after the stepped iteration %d" % it, pt.get_image(n), run.images[it], run, (it,))
+    else:
+        rep.image(seed, w, "pathtrace(%d)" % it, pt.pathtrace(None, 0, it), run.images[it], run, (it,))
+    if not plan.switch:
+        return
+    fused = tables is not None and tables[2] == "one launch per bounce" and tables[0] >= 2
+    img = np.zeros((n, 3), dtype=F32)
+    c0 = table_counters(pt)
+    pt.set_lens(0.0, 0.0)
+    pt.trace_batch(it + 1, 2, img)
+    rep.image(seed, w, "two iterations after pt_set_lens(0, 0)", img, run.images[it + 2], run, (it + 1, it + 2))
+    c1 = table_counters(pt)
+    pt.set_lens(*plan.lens)
+    pt.trace_batch(it + 3, 2, img)
+    rep.image(seed, w, "two iterations after pt_set_lens%r" % (plan.lens,), img, run.images[it + 4], run, (it + 3, it + 4))
+    c2 = table_counters(pt)
+    if tables is not None:
+        rep.equal(seed, "launches of bounces 0 and 1 from the tables under the lens (before, after the pinhole stretch)", (c0, c2), ((0, 0), c1))
+        if fused:
+            rep.equal(seed, "launches from the first-hit table rose in the pinhole stretch", c1[0] > 0, True)
+            rep.equal(seed, "launches from the first-state table in the pinhole stretch", c1[1], c1[0] if tables[1] else 0)
+
+
+def smooth_session(pt, po, rep, seed, w, h, flags, counters=True, camera=False, stepped=False, extras=False):
+    """PT_SMOOTH_NORMALS | PT_GLOSSY on the soup with rs.normals_of and the seed's sky against smooth_model.Model: iterations 1-3,
+    the normals removed, 4-5 on the lanes, the normals set again, 6-7 on the lanes.  extras: pt_get_vertex_normals returns the bytes
+    that were set (NaN payloads included), and pt_gbuffer and pt_albedo are those of the same session without normals."""
+    run, _, s = rs.smooth_run(po, pt, seed, w, h, camera=camera)
+    scene = pt.Scene(s.geoms, s.materials, s.cam, s.depth, triangles=s.tris, meshes=s.meshes)
+    planes = []
+    for normals in ((True, False) if extras else (True,)):
+        init_session(pt, scene, flags | pt.PT_SMOOTH_NORMALS | pt.PT_GLOSSY, run)
+        try:
+            if s.sky is not None:
+                pt.set_environment(s.sky)
+            if normals:
+                pt.set_vertex_normals(s.normals)
+                trace_sequence(pt, rep, seed, w, h, run, s.depth, counters=counters, last=3)
+                pt.set_vertex_normals(None)
+                on_the_lanes(pt, ((4, 1), (5, 1)))
+                rep.image(seed, w, "after the normals were removed", pt.get_image(w * h), run.images[5], run, (4, 5))
+                pt.set_vertex_normals(s.normals)
+                on_the_lanes(pt, ((6, 2),))
+                rep.image(seed, w, "after the normals were set again", pt.get_image(w * h), run.images[7], run, (6, 7))
+                if camera:
+                    camera_tail(pt, rep, seed, w, h, run, stepped)
+            else:
+                pt.pathtrace(None, 0, 1)
+            if extras:
+                got = pt.get_vertex_normals()
+                if normals:
+                    rep.equal(seed, "pt_get_vertex_normals returns the bytes that were set", got is not None and got.tobytes() == s.normals.tobytes(), True)
+                else:
+                    rep.equal(seed, "pt_get_vertex_normals without normals is None", got is None, True)
+                g = pt.gbuffer()
+                planes.append([(k, g[k]) for k in sorted(g)] + [("albedo", pt.albedo())])
+        finally:
+            pt.pathtraceFree()
+    if extras:
+        for (k, got), (_, want) in zip(*planes):
+            planes_equal(rep, seed, w, "with normals and without: " + k, got.reshape(w * h, -1), want.reshape(w * h, -1))
+
+
+SMOOTH = {"loop": lambda pt: pt.PT_COMPACT, "hierarchy": lambda pt: pt.PT_COMPACT | pt.PT_MESH_BVH}
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.SMOOTH_SEEDS))
+@pytest.mark.parametrize("mesh", list(SMOOTH))
+def test_smooth_sessions(pt, po, launch_plan, mesh, group):
+    """The SH_SMOOTH forms on the hostile soup: slivers and metre-sized triangles under normals that lean, face away, vanish, are NaN,
+    infinite, 1e-20 and 1e20 long; mirror and glass hits about smoothed normals with the guard behind them; normals that go and
+    come back between batches on the lanes.  The first group also runs non-compacting and through the fused sort."""
+    rep = Report("smooth, " + mesh, launch_plan)
+    for seed, w, h in frames(rs.SMOOTH_SEEDS, group):
+        smooth_session(pt, po, rep, seed, w, h, SMOOTH[mesh](pt), extras=True)
+        if rs.SMOOTH_SEEDS[0] in group and (w, h) == (W, H):
+            extra = pt.PT_MESH_BVH if mesh == "hierarchy" else 0
+            rep.session = "smooth, %s, non-compacting" % mesh
+            smooth_session(pt, po, rep, seed, w, h, extra, counters=False)
+            if mesh == "loop":                                           # (with the hierarchy the sort takes its two-kernel form: refused)
+                rep.session = "smooth, loop, sorted"
+                smooth_session(pt, po, rep, seed, w, h, pt.PT_COMPACT | pt.PT_SORT_MATERIAL)
+            rep.session = "smooth, " + mesh
+    rep.done()
+
+
+def sampled_sky_session(pt, po, rep, seed, w, h, camera=False, stepped=False):
+    """PT_COMPACT | PT_DIRECT_LIGHT | PT_DIRECT_SKY | PT_GLOSSY against sky_model.Model on rs.sky_session(): iterations 1-3 under
+    the seed's map, 4-5 without a map -- nlights falls back to the lamps', to 0 where the lamps are off: then no bounce D is traced
+    --, 6-7 on the lanes under the next seed's map.  D + 1 live counts wherever a call is waited for."""
+    run, _, s, _ = rs.sky_run(po, pt, seed, w, h, camera=camera)
+    init_session(pt, pt.Scene(s.geoms, s.materials, s.cam, s.depth), pt.PT_COMPACT | pt.PT_DIRECT_LIGHT | pt.PT_DIRECT_SKY | pt.PT_GLOSSY, run)
+    try:
+        pt.set_environment(s.texels)
+        trace_sequence(pt, rep, seed, w, h, run, s.depth + 1, last=3)
+        pt.set_environment(None)
+        img = np.zeros((w * h, 3), dtype=F32)
+        pt.trace_batch(4, 2, img)
+        rep.image(seed, w, "after the map was removed", img, run.images[5], run, (4, 5))
+        live = (run.live_sum((4, 5), s.depth + 1) + [0])[:s.depth + 1]
+        rep.equal(seed, "live counts without a map", list(pt.get_stats().live[:s.depth + 1]), live)
+        if s.lamps_off:
+            rep.equal(seed, "final rays without a map and without lamps", live[s.depth], 0)
+        pt.set_environment(s.other)
+        on_the_lanes(pt, ((6, 1), (7, 1)))
+        rep.image(seed, w, "under the map of seed %d" % (seed + 1), pt.get_image(w * h), run.images[7], run, (6, 7))
+        if camera:
+            camera_tail(pt, rep, seed, w, h, run, stepped)
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.SKY_SEEDS))
+def test_sampled_sky_sessions(pt, po, launch_plan, group):
+    """The sky as a light on the random scenes: maps of 1, 4 and 16 texels a side, with the lamps and as the only light, final rays
+    that leave through gaps between primitives and final rays that do not, a map that goes and another that arrives."""
+    rep = Report("sampled sky", launch_plan)
+    for seed, w, h in frames(rs.SKY_SEEDS, group):
+        sampled_sky_session(pt, po, rep, seed, w, h)
+    rep.done()
+
+
+def camera_session(pt, po, rep, kind, seed, w, h, stepped, launch_plan):
+    """One of rs.CAMERA_KINDS under the seed's rs.camera_features(): the session's own sequence, then camera_tail."""
+    if kind.startswith("smooth"):
+        return smooth_session(pt, po, rep, seed, w, h, SMOOTH[kind.split()[1]](pt), camera=True, stepped=stepped)
+    if kind == "sampled sky":
+        return sampled_sky_session(pt, po, rep, seed, w, h, camera=True, stepped=stepped)
+    geoms, mats, cam, depth = rs.scene(pt, seed, w, h)
+    run = rs.camera_run(po, pt, kind, seed, w, h)
+    if kind.startswith("plain") or kind == "moments":
+        flags = PLAIN[kind[6:]](pt, po)[0] if kind != "moments" else pt.PT_COMPACT | pt.PT_MOMENTS
+        init_session(pt, pt.Scene(geoms, mats, cam, depth), flags, run, **(dict(pin_image=False) if kind == "moments" else {}))
+        try:
+            trace_sequence(pt, rep, seed, w, h, run, depth, counters=kind != "plain non-compacting", rays=run.rays)
+            if kind == "moments":
+                for name, got, want in zip(("M1", "M2"), pt.get_moments(), run.moments[run.plan.last]):
+                    planes_equal(rep, seed, w, name + " after iteration %d" % run.plan.last, got.reshape(-1, 1), want.reshape(-1, 1))
+            glass_free = not (mats["hasRefractive"] > 0).any()
+            camera_tail(pt, rep, seed, w, h, run, stepped, (depth, glass_free, launch_plan) if kind == "plain compact" else None)
+            if kind == "moments":
+                for name, got, want in zip(("M1", "M2"), pt.get_moments(), run.moments[run.plan.end]):
+                    planes_equal(rep, seed, w, name + " after iteration %d" % run.plan.end, got.reshape(-1, 1), want.reshape(-1, 1))
+        finally:
+            pt.pathtraceFree()
+        return
+    f = rs.features(seed, mats, depth)
+    if kind == "textures + bumps":
+        scene, flags, last = pt.Scene(geoms, f.materials, cam, depth), pt.PT_COMPACT | pt.PT_TEXTURES | pt.PT_GLOSSY, 3
+    elif kind == "sky + glossy":
+        scene, flags, last = pt.Scene(geoms, f.materials, cam, depth), pt.PT_COMPACT | pt.PT_GLOSSY, 9
+    else:
+        assert kind == "direct + sky + glossy"
+        depth = f.direct_depth
+        scene, flags, last = pt.Scene(geoms, f.materials, cam, depth), pt.PT_COMPACT | pt.PT_DIRECT_LIGHT | pt.PT_GLOSSY, 9
+    init_session(pt, scene, flags, run)
+    try:
+        if kind == "textures + bumps":
+            for k, t in f.bump_maps.items():
+                pt.set_bump_map(k, t)
+            for k, t in f.textures.items():
+                pt.set_texture(k, t)
+        if f.sky is not None:
+            pt.set_environment(f.sky)
+        trace_sequence(pt, rep, seed, w, h, run, len(run.live[1]), last=last)
+        if kind == "textures + bumps":
+            b, t = rs.dropped(f)
+            if b is not None:
+                pt.set_bump_map(b, None)
+            if t is not None:
+                pt.set_texture(t, None)
+            on_the_lanes(pt, ((4, 1), (5, 1)))
+            rep.image(seed, w, "after a bump map and a texture were removed", pt.get_image(w * h), run.images[5], run, (4, 5))
+        camera_tail(pt, rep, seed, w, h, run, stepped)
+    finally:
+        pt.pathtraceFree()
+
+
+@pytest.mark.parametrize("group", rs.groups(rs.CAMERA_SEEDS))
+@pytest.mark.parametrize("kind", rs.CAMERA_KINDS)
+def test_camera_sessions(pt, po, launch_plan, kind, group):
+    """PT_AA_JITTER and the thin lens under every shading feature: the GEN forms of SH_DIRECT, SH_TEX and SH_SMOOTH, a depth-1 direct
+    session whose bounce 0 is a DIRECT bounce that generates its rays, k_raygen through the stepping interface for the group's first
+    seed, and pt_set_lens switching the camera's rays between a lens and the pinhole in the middle of a session: the tables that
+    depend on rays that repeat (the first-hit and first-state tables, the camera masks) come and go with it."""
+    rep = Report("camera, " + kind, launch_plan)
+    for seed, w, h in frames(rs.CAMERA_SEEDS, group):
+        camera_session(pt, po, rep, kind, seed, w, h, seed == group[0] and (w, h) == (W, H), launch_plan)
     rep.done()
 
 

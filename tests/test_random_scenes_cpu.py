@@ -2,7 +2,9 @@
 the kernels with cannot be vacuous.  The generator is deterministic and builds, seed by seed, the scene the fuzz tool's inline code
 always built; every model image, G-buffer, albedo plane and filter output of the chosen seeds is finite (zero-scale primitives
 stay in, so the device's byte comparison is never one of NaN payloads); and, summed over each session's seed list, the scenes reach
-the branches the sessions are there for -- stated as floors, not as measurements."""
+the branches the sessions are there for -- stated as floors, not as measurements.  The same for the lists of the newer streams:
+smoothed hits on every kind of material and every refusal (SMOOTH_SEEDS), sky samples that score and that are occluded (SKY_SEEDS),
+and images that are not the pinhole's (CAMERA_SEEDS)."""
 import os
 import sys
 
@@ -104,7 +106,9 @@ def test_the_second_stream_is_deterministic_and_leaves_the_scene_alone(pt):
     for seed in rs.TEXTURED_SEEDS[:4]:
         geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
         before = mats.tobytes()
-        a, b = rs.features(seed, mats, depth), rs.features(seed, mats, depth)
+        a = rs.features(seed, mats, depth)
+        rs.camera_features(seed), rs.sky_of(pt, seed), rs.normals_of(pt, seed, rs.mesh_of(pt, seed, rs.scene(pt, seed, W, H)[0], len(mats))[1])
+        b = rs.features(seed, mats, depth)                               # (the newer streams in between: they are streams of their own)
         assert mats.tobytes() == before
         assert a.materials.tobytes() == b.materials.tobytes() and sorted(a.textures) == sorted(b.textures)
         assert all(a.textures[k].tobytes() == b.textures[k].tobytes() for k in a.textures)
@@ -279,6 +283,162 @@ def test_mesh_session_images_are_finite(pt, po):
         run, c, f = rs.textured_run(po, pt, seed, W, H, mesh=True)
         assert finite(*run.images.values()), seed
     assert sum(rs.textured_run(po, pt, s, W, H, mesh=True)[1]["tinted"] for s in rs.MESH_SEEDS) > 0
+
+
+# ---- the newer streams: camera features, vertex normals, sampled skies ----------------------------------------------------------
+NEW_LISTS = (rs.SMOOTH_SEEDS, rs.SKY_SEEDS, rs.CAMERA_SEEDS)
+
+
+def test_new_seed_lists_are_literal_and_group_in_fours():
+    assert len(rs.SMOOTH_SEEDS) == 8 and len(rs.CAMERA_SEEDS) == 8 and len(rs.SKY_SEEDS) == 16
+    for seeds in NEW_LISTS:
+        assert all(type(s) is int for s in seeds) and len(set(seeds)) == len(seeds)
+        assert len(seeds) % 4 == 0 and all(len(g) == 4 for g in rs.groups(seeds))
+    assert set(rs.SKY_OPENED) <= set(rs.SKY_SEEDS) and len(set(rs.SKY_OPENED)) == len(rs.SKY_OPENED)
+
+
+def test_the_newer_streams_are_deterministic_and_leave_the_scene_alone(pt):
+    """camera_features, normals_of, sky_of and opened(): the same values twice, and scene() and features() byte for byte what they
+    were before the call."""
+    def snapshot(seed):
+        geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
+        f = rs.features(seed, mats, depth)
+        parts = [geoms.tobytes(), mats.tobytes(), cam.tobytes(), bytes([depth]), f.materials.tobytes(), b"" if f.sky is None else f.sky.tobytes()]
+        parts += [f.textures[k].tobytes() for k in sorted(f.textures)] + [f.bump_maps[k].tobytes() for k in sorted(f.bump_maps)]
+        return parts
+
+    for seed in sorted(set(rs.SMOOTH_SEEDS[:3] + rs.SKY_SEEDS[:5] + rs.CAMERA_SEEDS[:3])):
+        before = snapshot(seed)
+        geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
+        kept = geoms.tobytes()
+        a, b = rs.camera_features(seed), rs.camera_features(seed)
+        assert a == b and type(a[0]) is bool and a[1][0] in rs.RADII and a[1][1] in rs.FOCALS
+        _, tris, _ = rs.mesh_of(pt, seed, geoms, len(mats))
+        tri_bytes = tris.tobytes()
+        n1, n2 = rs.normals_of(pt, seed, tris), rs.normals_of(pt, seed, tris)
+        assert n1.dtype == np.float32 and n1.shape == (len(tris), 3, 3) and n1.tobytes() == n2.tobytes() and tris.tobytes() == tri_bytes
+        s1, s2 = rs.sky_of(pt, seed), rs.sky_of(pt, seed)
+        assert s1[0].tobytes() == s2[0].tobytes() and s1[1] is s2[1] and type(s1[1]) is bool
+        assert s1[0].dtype == np.float32 and s1[0].shape[1] in (1, 4, 16) and s1[0].shape == (6, s1[0].shape[1], s1[0].shape[1], 3)
+        assert np.isfinite(s1[0]).all() and (s1[0] >= 0).all()
+        o1, o2 = rs.opened(geoms), rs.opened(geoms)
+        assert o1.tobytes() == o2.tobytes() and geoms.tobytes() == kept and 1 <= len(o1) <= len(geoms)
+        assert (o1["scale"].max(axis=1) < 30).all() or len(o1) == 1
+        assert snapshot(seed) == before
+
+
+def test_normals_of_is_hostile(pt):
+    """What smooth_cases' hostile scene does to its normals, on the soup: every 7th triangle faces away, every 11th is zero, a NaN,
+    an infinite corner, lengths of 1e-20 and 1e20, a single zero corner; no facet normal that is not finite gets in."""
+    import smooth_model
+    seed = rs.SMOOTH_SEEDS[0]
+    geoms, mats, cam, depth = rs.scene(pt, seed, W, H)
+    _, tris, _ = rs.mesh_of(pt, seed, geoms, len(mats))
+    vn = rs.normals_of(pt, seed, tris)
+    fn = smooth_model.facet_normals(tris)
+    flat = tris.copy()                                                                    # a zero-area triangle has no facet normal:
+    flat["v1"][20] = flat["v2"][20] = flat["v0"][20]                                      # its base is 0, its corners the lean alone
+    assert not np.isfinite(smooth_model.facet_normals(flat)[20]).any()
+    vf = rs.normals_of(pt, seed, flat)
+    assert np.isfinite(vf[20]).all() and vf[20].any() and np.abs(vf[20]).max() < 4 and vf[21].tobytes() == vn[21].tobytes()
+    bad = ~np.isfinite(vn).all(axis=(1, 2))
+    assert sorted(np.nonzero(bad)[0].tolist()) == [2, 4]                                  # only the two that were put there
+    assert np.isnan(vn[2, 1, 0]) and np.isinf(vn[4, 2]).all()
+    assert not vn[3::11].any() and not vn[10, 2].any() and vn[10, 0].any() and vn[10, 1].any()
+    ok = np.isfinite(fn).all(axis=1)
+    mean = vn.astype(np.float64).mean(axis=1)
+    with np.errstate(all="ignore"):
+        side = (mean * fn).sum(axis=1)
+    plain = np.ones(len(tris), dtype=bool)
+    plain[[2, 4, 6, 8, 10]] = False
+    plain[3::11] = False
+    away = np.zeros(len(tris), dtype=bool)
+    away[0::7] = True
+    assert (side[ok & plain & away] < 0).mean() > 0.9 and (side[ok & plain & ~away] > 0).mean() > 0.9
+    assert 0 < np.abs(vn[6]).max() < 1e-18 and np.abs(vn[8]).max() > 1e18
+
+
+def test_smooth_session_floors(pt, po):
+    stats, differ = [], 0
+    for seed in rs.SMOOTH_SEEDS:
+        run, st, s = rs.smooth_run(po, pt, seed, W, H)
+        assert sorted(run.images) == list(range(1, 8)) and finite(*run.images.values()), seed
+        kept = rs.smooth_run(po, pt, seed, W, H, last=5, keep=True)[0]
+        assert kept.images[3].tobytes() == run.images[3].tobytes()
+        differ += kept.images[5].tobytes() != run.images[5].tobytes()
+        stats.append(st)
+    for kind in ("smoothed matte", "smoothed mirror", "smoothed glass"):
+        assert sum(st.get(kind, 0) > 0 for st in stats) >= 2, kind
+    assert total(stats, "guarded") >= 100
+    assert total(stats, "refused2") > 0 and total(stats, "refused4") > 0 and total(stats, "refused5") > 0
+    assert differ >= 6                                                                    # the removal takes something away
+    scenes = [rs.scene(pt, s, W, H) for s in rs.SMOOTH_SEEDS]
+    assert max(len(g) for g, _, _, _ in scenes) >= 17 and min(d for _, _, _, d in scenes) <= 2
+    assert finite(*rs.smooth_run(po, pt, rs.SMOOTH_SEEDS[0], *rs.WIDE)[0].images.values())
+
+
+def test_sky_session_floors(pt, po):
+    import glossy_model as gm
+    counts, sessions = [], []
+    for seed in rs.SKY_SEEDS:
+        run, c, s, elements = rs.sky_run(po, pt, seed, W, H)
+        assert sorted(run.images) == list(range(1, 8)) and finite(*run.images.values()), seed
+        assert 1 <= elements <= 1024, seed                                                # the lamps' elements and the sky's: no seed is ever skipped
+        assert c.get("negative or nan weights", 0) == 0, seed
+        assert len(run.live[1]) == s.depth + 1 and len(run.live[7]) == s.depth + 1         # D + 1 bounces while a map is set
+        assert len(run.live[4]) == (s.depth + 1 if elements > 1 else s.depth), seed           # ... or lamps' elements exist
+        assert not s.lamps_off or elements == 1, seed
+        assert s.lamps_off == (not (s.materials["emittance"] > 0).any())
+        assert (seed in rs.SKY_OPENED) == (len(s.geoms) < len(rs.scene(pt, seed, W, H)[0])), seed
+        if s.lamps_off:                                                                   # without its map the session is the plain one
+            m = gm.Model(po, s.geoms, s.materials, s.cam, s.depth, glossy=True)
+            m.image = run.images[3].copy()
+            for it in (4, 5):
+                m.iterate(it)
+            assert m.image.tobytes() == run.images[5].tobytes(), seed
+        counts.append(c)
+        sessions.append(s)
+    assert total(counts, "sky aimed") >= 1000 and total(counts, "lamp aimed") >= 1000
+    assert total(counts, "sky scored") >= 100 and sum(c.get("sky scored", 0) > 0 for c in counts) >= 4
+    assert total(counts, "sky occluded") > 0
+    assert sum(s.lamps_off for s in sessions) >= 2
+    assert any(s.texels.shape[1] == 1 for s in sessions) and any(s.depth == 1 for s in sessions)
+    assert finite(*rs.sky_run(po, pt, rs.SKY_SEEDS[0], *rs.WIDE)[0].images.values())
+
+
+def test_camera_list_floors(pt, po):
+    feats = [rs.camera_features(s) for s in rs.CAMERA_SEEDS]
+    assert sum(aa and not lens[0] > 0 for aa, lens in feats) >= 2                         # jitter only
+    assert sum(lens[0] > 0 and not aa for aa, lens in feats) >= 2                         # a lens only: the sessions that call pt_set_lens
+    assert sum(aa and lens[0] > 0 for aa, lens in feats) >= 2
+    assert any(lens[0] == 2.0 for _, lens in feats) and any(lens[0] > 0 and lens[1] == 0.5 for _, lens in feats)
+    scenes = [rs.scene(pt, s, W, H) for s in rs.CAMERA_SEEDS]
+    assert max(len(g) for g, _, _, _ in scenes) >= 17
+    # depth 1 with lamps: bounce 0 of the direct session is a DIRECT bounce that generates its rays
+    assert any(d == 1 and 0 < rs.light_table_size(po, pt, s, W, H) <= 1024 for s, (_, _, _, d) in zip(rs.CAMERA_SEEDS, scenes))
+    assert all(rs.light_table_size(po, pt, s, W, H) <= 1024 for s in rs.CAMERA_SEEDS)     # no direct session of the list is refused
+    glass_free = [s for s, (_, m, _, _) in zip(rs.CAMERA_SEEDS, scenes) if not (m["hasRefractive"] > 0).any()]
+    assert len(glass_free) >= 2
+    # ... of which one has a lens only and depth 2 or more: its pinhole stretch takes the first-state table
+    assert any(rs.lens_only(s) and rs.scene(pt, s, W, H)[3] >= 2 for s in glass_free)
+
+
+@pytest.mark.parametrize("kind", rs.CAMERA_KINDS)
+def test_camera_sessions_depend_on_the_camera(pt, po, kind):
+    """Every image of every camera run is finite, and after iteration 3 it is not the pinhole session's: no comparison on the
+    device can pass by ignoring the jitter or the lens.  A seed with a lens and no jitter goes on for five iterations, the others
+    for one."""
+    for seed in rs.CAMERA_SEEDS:
+        run = rs.camera_run(po, pt, kind, seed, W, H)
+        plan = run.plan
+        assert sorted(run.images) == list(range(1, plan.last + (6 if rs.lens_only(seed) else 2))), seed
+        assert finite(*run.images.values()), seed
+        pinhole = rs.camera_run(po, pt, kind, seed, W, H, camera=False, last=3)
+        assert pinhole.images[3].tobytes() != run.images[3].tobytes(), seed
+        assert len(run.stepped) == run.live[plan.step][1] if len(run.live[plan.step]) > 1 else True
+        if kind == "moments":
+            assert finite(*run.moments[plan.last])
+    assert finite(*rs.camera_run(po, pt, kind, rs.CAMERA_SEEDS[0], *rs.WIDE).images.values())
 
 
 def test_wide_frames_are_finite(pt, po):

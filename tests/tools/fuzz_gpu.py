@@ -4,7 +4,9 @@ rotations, thin slabs, enclosing shells, tiny and huge primitives, random materi
 under every pipeline, and the cull-stress rays of tests/cull_model.py through pt_intersect_once -- all compared with
 the CPU oracle bit for bit.  The scenes are tests/random_scenes.py's (`draw`: seed N is the scene it always was), which the suite
 runs too (tests/test_gpu_random_scenes.py, with the shading features and the filters this tool knows nothing of).  `mesh` mode: PT_MESH_BVH on random soups and smooth meshes incl. grazing rays.
-Usage: python tests/tools/fuzz_gpu.py [first_seed] [count]   |   python tests/tools/fuzz_gpu.py mesh [first_seed] [count]"""
+`--smooth`, `--sky-light`, `--camera`: the suite's smooth-normal, sampled-sky and jitter / lens sessions over a seed range.
+Usage: python tests/tools/fuzz_gpu.py [first_seed] [count]   |   python tests/tools/fuzz_gpu.py mesh [first_seed] [count]   |
+python tests/tools/fuzz_gpu.py --smooth | --sky-light | --camera [first_seed] [count]"""
 import os
 import sys
 import time
@@ -77,7 +79,44 @@ def mesh_fuzz(pt, first, count):
     return bad
 
 
+def feature_fuzz(pt, switch, first, count):
+    """--smooth, --sky-light, --camera: the sessions of tests/test_gpu_random_scenes.py for rs.SMOOTH_SEEDS, rs.SKY_SEEDS and
+    rs.CAMERA_SEEDS over a seed range at 40 x 26, under both launch plans, against the numpy models (seconds per seed)."""
+    import test_gpu_random_scenes as tg
+    bad = 0
+    t0 = time.time()
+    for seed in range(first, first + count):
+        random_scenes._refs.clear()
+        for plan in ("one launch per bounce", "small batches in one launch"):
+            if plan == "one launch per bounce":
+                os.environ["PTMI355_WHOLE_MAX"] = "0"
+            else:
+                os.environ.pop("PTMI355_WHOLE_MAX", None)
+            rep = tg.Report(switch[2:], plan)
+            try:
+                if switch == "--smooth":
+                    for flags in (pt.PT_COMPACT, pt.PT_COMPACT | pt.PT_MESH_BVH):
+                        tg.smooth_session(pt, po, rep, seed, tg.W, tg.H, flags, extras=True)
+                elif switch == "--sky-light":
+                    tg.sampled_sky_session(pt, po, rep, seed, tg.W, tg.H)
+                else:
+                    for kind in random_scenes.CAMERA_KINDS:
+                        rep.session = "camera, " + kind
+                        tg.camera_session(pt, po, rep, kind, seed, tg.W, tg.H, True, plan)
+            except ValueError as e:                                     # (direct_model: more than 1024 light elements)
+                print("seed %d: skipped, %s" % (seed, e), flush=True)
+            bad += len(rep.lines)
+            for line in rep.lines:
+                print(line, flush=True)
+    print("%s fuzz: seeds %d..%d, %d mismatches, %.0f s" % (switch, first, first + count - 1, bad, time.time() - t0))
+    return bad
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] in ("--smooth", "--sky-light", "--camera"):
+        pt = ge.load_package()
+        po.build()
+        return 1 if feature_fuzz(pt, sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 1000, int(sys.argv[3]) if len(sys.argv) > 3 else 20) else 0
     if len(sys.argv) > 1 and sys.argv[1] == "mesh":
         pt = ge.load_package()
         po.build()
